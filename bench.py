@@ -2,7 +2,7 @@
 """Headline benchmark: attention-layer tokens/s of the fused HIP kernel on the reference's OPT-125m
 configuration (opt-12L12H: 12 layers, 12 heads, d=64, S=512; B=16 per GPU), fp16 storage, softmax1, causal.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload opt_softmax1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload opt_softmax1] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 step       = one pass of the attention core over one synthetic batch through the model's 12 attention layers
@@ -96,7 +96,35 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(unused since round 5: the CPU leg is 3 warm-up + 10 timed full-batch passes)")
     ap.add_argument("--no-check", action="store_true", help="N > 1: skip the shard-parity check (all_gather of the ranks' layer-0 outputs "
                     "over RCCL, each compared bit for bit with rank 0's own run of that shard)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "as DIR/<name>.npy (float32, at most 64 MB: layer 0's output in full, a fixed seeded sample of every layer's; rank 0's shard)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_BUDGET = 60_000_000  # array bytes written by --dump-outputs, all files together (under 64 MB with the .npy headers)
+DUMP_SAMPLE = 65536     # sampled elements per layer (fewer when many layers would exceed the budget)
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs: `outs` are the (B,H,S,d) outputs of the last timed step, one per layer, as a caller of
+    oeh_attn_fwd receives them.  Writes out_layer0.npy (layer 0 in full, float32) and out_layers_sample.npy
+    (L, n): the same n flat (B,H,S,d) positions of every layer, drawn by a fixed seed, so that runs with the same
+    arguments can be compared element for element."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    first = outs[0].float().contiguous().cpu().numpy()
+    numel = first.size
+    n = min(numel, DUMP_SAMPLE, max(1, (DUMP_BUDGET - first.nbytes) // (4 * len(outs))))
+    idx = torch.randperm(numel, generator=torch.Generator().manual_seed(20260))[:n].sort().values.to(outs[0].device)
+    sample = torch.stack([o.float().contiguous().view(-1)[idx] for o in outs]).cpu().numpy()
+    assert first.nbytes + sample.nbytes <= DUMP_BUDGET
+    np.save(os.path.join(dirname, "out_layer0.npy"), first)
+    np.save(os.path.join(dirname, "out_layers_sample.npy"), sample)
 
 
 def cpu_baseline(w, layer0, pad, gate_w):
@@ -620,6 +648,8 @@ def main():
     t1 = time.perf_counter()
     wall = t1 - t0
     dev_ms = ev0.elapsed_time(ev1)
+    # the outputs of the last timed step, copied before anything below launches again into the same buffers
+    last_outs = [s_[3].clone() for s_ in sets] if a.dump_outputs and rank == 0 else None
     # spread of the per-launch time: 40 separately timed steps after the timed region (reported, never part of `value`)
     spread = []
     for _ in range(40):
@@ -750,6 +780,9 @@ def main():
             rec["cpu_baseline"]["fp16_vs_reference"] = fp16_check()
         if shard_check is not None:
             rec["shard_check"] = shard_check
+        if last_outs is not None:
+            dump_outputs(a.dump_outputs, last_outs)
+            del last_outs
         print(json.dumps(rec), flush=True)
     if dist is not None:
         dist.barrier()

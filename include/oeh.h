@@ -327,6 +327,26 @@ typedef struct {
 int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* bias, int64_t B, int32_t S, int32_t K, int32_t E, int32_t n_seg,
                       const oeh_proj_seg* segs, int64_t lda, int64_t ldw, void* stream);
 
+/* Attention core for TRAINING (oeh_attn_bwd.hip): the forward with its row statistic, and the fused backward that recomputes the
+ * probabilities from it - nothing of size Sq x Sk is stored.  Replaces the torch-op chain opt_attention.py:204-263 /
+ * bert_attention.py:222-292 under autograd.  `desc` as for oeh_attn_fwd with: dtype OEH_F16 | OEH_BF16, D == 64, softmax_base and
+ * clip (gamma, eta), scale / scale_div, key_pad_mask, full_mask, causal, clamp_min + mask_min; fp32 or INT8 storage, another head
+ * dim, a gate (gate or gate_hidden) or o_dtype OEH_F32: OEH_ENOTSUP (the gate stays outside the differentiable core, as a torch
+ * multiply; fake-quant has no parameter here).  q, k, v, o (and do_, dq, dk, dv) rows must be 16-byte aligned: OEH_EALIGN.
+ *
+ * oeh_attn_fwd_train: o as oeh_attn_fwd (o_stride), and lse (B,H,Sq) fp32 contiguous: the per-row statistic
+ *   lse = m' + log(sum_k e^(x_k - m') + [softmax_1] e^(-m')),  m' = max(m, 0) for softmax_1, m for softmax
+ * so that p = e^(x - lse) for either base (a fully masked softmax_1 row: p = 0; a fully masked vanilla row: uniform).
+ * oeh_attn_bwd: do_, dq, dk, dv in desc->dtype with their own (batch, head, seq) element strides; o and lse from
+ *   oeh_attn_fwd_train; work: caller-provided fp32 scratch of oeh_attn_bwd_work_bytes(desc) bytes (the row term delta).  Two kernels
+ *   (dq, then dk / dv), no allocation, no atomics: the gradients are bitwise reproducible; graph-capture safe.
+ * oeh_attn_bwd_work_bytes: bytes of `work`, or the negative OEH_E* code of an unsupported / invalid descriptor. */
+int oeh_attn_fwd_train(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, float* lse, void* stream);
+int64_t oeh_attn_bwd_work_bytes(const oeh_attn_desc* desc);
+int oeh_attn_bwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, const void* o, const void* do_,
+                 const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk, const int64_t dk_stride[3],
+                 void* dv, const int64_t dv_stride[3], void* work, void* stream);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -68,6 +68,7 @@ class oeh_proj_seg(C.Structure):
 # every symbol include/oeh.h declares (tests/test_abi.py checks the .so exports exactly these)
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
+    "oeh_attn_fwd_train", "oeh_attn_bwd_work_bytes", "oeh_attn_bwd",
     "oeh_abi_version", "oeh_build_info", "oeh_strerror", "oeh_attn_variant",
 )
 
@@ -116,6 +117,13 @@ def load() -> C.CDLL:
     lib.oeh_split_triples.restype = C.c_int
     lib.oeh_proj_quant_i8.argtypes = [vp, i32, vp, vp, i64, i32, i32, i32, i32, C.POINTER(oeh_proj_seg), i64, i64, vp]
     lib.oeh_proj_quant_i8.restype = C.c_int
+    lib.oeh_attn_fwd_train.argtypes = [C.POINTER(oeh_attn_desc), vp, vp, vp, vp, vp, vp]
+    lib.oeh_attn_fwd_train.restype = C.c_int
+    lib.oeh_attn_bwd_work_bytes.argtypes = [C.POINTER(oeh_attn_desc)]
+    lib.oeh_attn_bwd_work_bytes.restype = C.c_int64
+    lib.oeh_attn_bwd.argtypes = [C.POINTER(oeh_attn_desc), vp, vp, vp, vp, vp, C.POINTER(i64), vp, vp, C.POINTER(i64), vp, C.POINTER(i64), vp,
+                                 C.POINTER(i64), vp, vp]
+    lib.oeh_attn_bwd.restype = C.c_int
     lib.oeh_abi_version.restype = C.c_int
     lib.oeh_build_info.restype = C.c_char_p
     lib.oeh_strerror.argtypes = [C.c_int]

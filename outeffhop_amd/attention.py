@@ -422,6 +422,41 @@ def attention_core(
     return out.permute(0, 2, 1, 3).reshape(B, Sq, H * D)
 
 
+# ---- training on the fused kernels (opt-in): with FUSED_BACKWARD on, a module whose forward has to be differentiable and needs none of
+# the observable path's features (dropout > 0 in training, output_attentions, hooks on the taps, head_mask, fake-quant, user callables)
+# runs its core through autograd_attention.fused_attention - the HIP training forward and backward, nothing of size Sq x Sk saved -
+# instead of unfused_core.  fp16 / bf16, head dim 64; anything else keeps the torch-op path.  Off by default.
+FUSED_BACKWARD = False
+
+
+def set_fused_backward(on: bool = True) -> None:
+    """Switch the modules' differentiable path to the fused HIP backward (True) or back to the torch-op path (False, the default)."""
+    global FUSED_BACKWARD
+    FUSED_BACKWARD = bool(on)
+
+
+def fused_train_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax_fn, scale: float = 1.0, scale_div: float = 0.0,
+                     attention_mask: Optional[torch.Tensor] = None, clamp_min: bool = False, detect_causal: bool = False) -> Optional[torch.Tensor]:
+    """The differentiable core on the fused training kernels: logical (B,H,Sq,d) context, or None when FUSED_BACKWARD is off or the
+    problem is not one the kernels take (the caller then runs unfused_core).  Same score chain as unfused_core: the clamp floor is
+    finfo of the scores' dtype; a decoder mask becomes the analytic causal mask plus a key-padding vector."""
+    from .autograd_attention import fused_attention, fused_supported
+
+    if not FUSED_BACKWARD or not fused_supported(q, k, v, softmax_fn):
+        return None
+    B, H, Sq, _ = q.shape
+    Sk = k.shape[2]
+    pad, full = split_mask(attention_mask, B, Sq, Sk)
+    causal = False
+    if full is not None and detect_causal and Sq <= Sk:
+        causal, padvec = classify_causal(full)
+        if causal:
+            full, pad = None, padvec
+    clamp = clamp_min and attention_mask is not None
+    return fused_attention(q, k, v, softmax=spec_of(softmax_fn), scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full,
+                           causal=causal, clamp_min=clamp, mask_min=float(torch.finfo(q.dtype).min))
+
+
 def unfused_core(
     q, k, v, *, softmax_fn, scale: float = 1.0, scale_div: float = 0.0, attention_mask=None, clamp_min: bool = False,
     scores_tap=None, probs_tap=None, dropout=None, probs_after_tap=None, head_mask=None, extra_scores=None,

@@ -14,7 +14,8 @@ from typing import Optional, Tuple
 import torch
 from torch import nn
 
-from .attention import AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_qkv, has_hooks, unfused_core
+from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_qkv, fused_train_core, has_hooks,
+                        unfused_core)
 from .softmax import make_clipped_softmax, spec_of
 
 
@@ -136,6 +137,19 @@ class BertSelfAttentionWithExtras(GateBookkeeping, nn.Module):
             if gp is not None:
                 GateState.finish_predictor(self, gp, self.num_attention_heads)
         else:
+            ctx = None
+            if (self.position_embedding_type == "absolute" and head_mask is None and not output_attentions and not (self.training and self.dropout.p > 0.0)
+                    and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout)):
+                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported)
+                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale_div=div, attention_mask=attention_mask)
+            if ctx is not None:
+                if gate is not None:
+                    ctx = ctx * gate.to(ctx.dtype)
+                context = ctx.permute(0, 2, 1, 3).reshape(ctx.shape[0], ctx.shape[2], self.all_head_size)
+                outputs = (context,)
+                if self.is_decoder:
+                    outputs = outputs + (new_past,)
+                return outputs
             extra = None
             if self.position_embedding_type in ("relative_key", "relative_key_query"):
                 extra = self._relative_scores(q, k, use_cache, hidden_states.device)

@@ -848,3 +848,102 @@ def minmax(x: torch.Tensor) -> torch.Tensor:
         rc = _lib.load().oeh_minmax(_ptr(xc), xc.numel(), _DT[x.dtype], _ptr(out), _stream())
     _lib.check(rc, "oeh_minmax")
     return out
+
+
+# ---- training: the forward with its row statistic and the fused backward (include/oeh.h: oeh_attn_fwd_train / oeh_attn_bwd)
+def _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min):
+    """Descriptor + the mask views it points into, for the training entry points (fp16 / bf16, D = 64; the library refuses the rest)."""
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if k.shape != (B, H, Sk, D) or v.shape != (B, H, Sk, D):
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in _DT:
+        raise ValueError(f"q/k/v dtypes must match and be fp16/bf16/fp32, got {q.dtype}, {k.dtype}, {v.dtype}")
+    d = oeh_attn_desc()
+    d.B, d.H, d.Sq, d.Sk, d.D = B, H, Sq, Sk, D
+    d.dtype = _DT[q.dtype]
+    d.o_dtype = d.dtype
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
+        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    d.scale, d.scale_div = float(scale), float(scale_div)
+    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    keep = []
+    if key_pad_mask is not None:
+        m = key_pad_mask.detach().reshape(B, Sk)
+        m = (m if m.dtype in (torch.float16, torch.float32) else m.float()).contiguous()
+        keep.append(m)
+        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
+    if full_mask is not None:
+        if full_mask.shape != (B, 1, Sq, Sk):
+            raise ValueError(f"Attention mask should be of size {(B, 1, Sq, Sk)}, but is {tuple(full_mask.shape)}")
+        m = full_mask.detach()
+        m = m if m.dtype in (torch.float16, torch.float32) else m.float()
+        m = m if m.stride(3) == 1 else m.contiguous()
+        keep.append(m)
+        d.full_mask, d.full_mask_dtype = m.data_ptr(), _DT[m.dtype]
+        d.full_mask_stride[:] = [m.stride(0), m.stride(2)]
+    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
+    d.mask_min = float(torch.finfo(q.dtype).min if mask_min is None else mask_min)
+    return d, keep
+
+
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """A (B,H,S,D) view the training kernels can read: unit head-dim stride and 16-byte aligned rows (else a contiguous copy)."""
+    eb = t.element_size()
+    if t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * eb) % 16 == 0 for i in range(3)):
+        return t
+    return t.contiguous()
+
+
+def train_supported(q: torch.Tensor, softmax: SoftmaxSpec) -> bool:
+    """What oeh_attn_fwd_train / oeh_attn_bwd take (include/oeh.h): fp16 / bf16 storage, head dim 64, a registry softmax."""
+    return q.dtype in (torch.float16, torch.bfloat16) and q.dim() == 4 and q.shape[3] == 64 and softmax is not None
+
+
+def attn_fwd_train(q, k, v, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0, key_pad_mask=None,
+                   full_mask=None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None):
+    """The attention core's forward for training: (o, lse).  o is the logical (B,H,Sq,D) result stored (B,Sq,H,D)-contiguous as attn_fwd's;
+    lse (B,H,Sq) fp32 is the row statistic the backward recomputes the probabilities from.  No autograd here (see `fused_attention`)."""
+    dev = _need_gpu(q, k, v, key_pad_mask, full_mask, allow_grad=True)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k, v must be 4-D (B,H,S,D) views")
+    q, k, v = _rows16(q.detach()), _rows16(k.detach()), _rows16(v.detach())
+    B, H, Sq, D = q.shape
+    o = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    d, keep = _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min)
+    lib = _lib.load()
+    with _on_device(dev):
+        rc = lib.oeh_attn_fwd_train(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream())
+    _lib.check(rc, "oeh_attn_fwd_train")
+    del keep
+    return o, lse
+
+
+def attn_bwd(q, k, v, o, do, lse, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0, key_pad_mask=None,
+             full_mask=None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None):
+    """(dq, dk, dv) of the attention core from the forward's o and lse (attn_fwd_train) and the output gradient do; same options as that
+    call.  Two HIP kernels, deterministic (no atomics); the gradients are (B,S,H,D)-contiguous (B,H,S,D) views in the input dtype."""
+    dev = _need_gpu(q, k, v, o, do, lse, key_pad_mask, full_mask, allow_grad=True)
+    q, k, v, o, do = (_rows16(t.detach()) for t in (q, k, v, o, do))
+    if do.shape != o.shape or do.dtype != o.dtype:
+        do = _rows16(do.to(o.dtype))
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("lse must be the contiguous fp32 (B,H,Sq) statistic of attn_fwd_train")
+    new = lambda S: torch.empty((B, S, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)  # noqa: E731
+    dq, dk, dv = new(Sq), new(Sk), new(Sk)
+    d, keep = _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min)
+    lib = _lib.load()
+    nbytes = lib.oeh_attn_bwd_work_bytes(C.byref(d))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "oeh_attn_bwd_work_bytes")
+    work = torch.empty((max(1, nbytes // 4),), dtype=torch.float32, device=q.device)
+    st = lambda t: (C.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2))  # noqa: E731
+    with _on_device(dev):
+        rc = lib.oeh_attn_bwd(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), st(do), _ptr(lse), _ptr(dq), st(dq), _ptr(dk), st(dk),
+                              _ptr(dv), st(dv), _ptr(work), _stream())
+    _lib.check(rc, "oeh_attn_bwd")
+    del keep
+    return dq, dk, dv

@@ -16,7 +16,8 @@ from typing import Optional, Tuple
 import torch
 from torch import nn
 
-from .attention import AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_qkv, has_hooks, linear_fp32, unfused_core
+from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_qkv, fused_train_core, has_hooks,
+                        linear_fp32, unfused_core)
 from .softmax import make_clipped_softmax, make_clipped_softmax1, spec_of
 
 
@@ -123,6 +124,16 @@ class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
             if gp is not None:
                 GateState.finish_predictor(self, gp, self.num_heads)
         else:
+            ctx = None
+            if (layer_head_mask is None and not output_attentions and not (self.training and self.dropout > 0.0)
+                    and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout)):
+                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported)
+                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=True, detect_causal=True)
+            if ctx is not None:
+                if gate is not None:
+                    ctx = ctx * gate.to(ctx.dtype)
+                merged = ctx.transpose(1, 2).reshape(bsz, tgt_len, self.embed_dim)
+                return linear_fp32(self.out_proj, merged), None, new_past
             hm = None if layer_head_mask is None else layer_head_mask.view(1, -1, 1, 1)
             drop = (lambda p: nn.functional.dropout(p, p=self.dropout, training=self.training))
             fn = self.softmax_fn

@@ -12,7 +12,8 @@ from functools import partial
 import torch
 from torch import nn
 
-from .attention import AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, has_hooks, linear_fp32, unfused_core
+from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_train_core, has_hooks, linear_fp32,
+                        unfused_core)
 from .softmax import spec_of
 
 
@@ -76,6 +77,14 @@ class ViTSelfAttentionWithExtras(GateBookkeeping, nn.Module):
             if gp is not None:
                 GateState.finish_predictor(self, gp, H)
         else:
+            ctx = None
+            if not (self.training and self.attn_drop.p > 0.0) and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout):
+                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported)
+                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale)
+            if ctx is not None:
+                if gate is not None:
+                    ctx = ctx * gate.to(ctx.dtype)
+                return self.proj_drop(linear_fp32(self.proj, ctx.transpose(1, 2).reshape(B, N, C)))
             ctx, _, _ = unfused_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale, scores_tap=self.attn_scores,
                                      probs_tap=self.attn_probs_before_dropout, dropout=self.attn_drop,
                                      probs_after_tap=self.attn_probs_after_dropout)

@@ -347,6 +347,27 @@ int oeh_attn_bwd(const oeh_attn_desc* desc, const void* q, const void* k, const 
                  const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk, const int64_t dk_stride[3],
                  void* dv, const int64_t dv_stride[3], void* work, void* stream);
 
+/* Attention dropout inside the training kernels (oeh_attn_bwd.hip, oeh_philox.h): the probabilities after the clip (y, or p without
+ * the clip) are multiplied by keep / (1 - p) before the product with V - where nn.Dropout sits in bert_attention.py /
+ * opt_attention.py - and both backward kernels regenerate the same bits; nothing of size Sq x Sk is stored and lse is unchanged.
+ * The keep bit of element (b, h, i, j) (query row i, key column j of the logical problem) is Philox4x32-10 with key
+ * (seed & 0xffffffff, seed >> 32), counter (j >> 2, i, b * H + h, 0), output word j & 3: kept iff word >= floor(p * 2^32).
+ * p outside [0, 1) or NaN: OEH_EINVAL, before any other check or device work; p == 0: exactly the entry points above.
+ * oeh_attn_fwd_train_dropout / oeh_attn_bwd_dropout: as oeh_attn_fwd_train / oeh_attn_bwd (same scope rules, same scratch
+ *   oeh_attn_bwd_work_bytes(desc)); the backward must get the forward's drop.
+ * oeh_attn_dropout_mask: the (B,H,Sq,Sk) contiguous keep mask (1 kept, 0 dropped) of desc's B, H, Sq, Sk from the same generator. */
+typedef struct oeh_dropout {
+  float p;
+  uint32_t reserved;
+  uint64_t seed;
+} oeh_dropout;
+int oeh_attn_fwd_train_dropout(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, void* o, float* lse,
+                               void* stream);
+int oeh_attn_bwd_dropout(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, const void* o,
+                         const void* do_, const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk,
+                         const int64_t dk_stride[3], void* dv, const int64_t dv_stride[3], void* work, void* stream);
+int oeh_attn_dropout_mask(const oeh_attn_desc* desc, const oeh_dropout* drop, uint8_t* keep, void* stream);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -59,6 +59,11 @@ class oeh_attn_desc(C.Structure):
     ]
 
 
+class oeh_dropout(C.Structure):
+    """include/oeh.h: attention dropout of the training kernels (p in [0, 1), Philox key seed)."""
+    _fields_ = [("p", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class oeh_proj_seg(C.Structure):
     """include/oeh.h: one column segment (a projection) of oeh_proj_quant_i8."""
     _fields_ = [("alpha", C.c_float), ("scale", C.c_float), ("zero_point", C.c_float), ("out", C.c_void_p), ("y", C.c_void_p),
@@ -69,6 +74,7 @@ class oeh_proj_seg(C.Structure):
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
     "oeh_attn_fwd_train", "oeh_attn_bwd_work_bytes", "oeh_attn_bwd",
+    "oeh_attn_fwd_train_dropout", "oeh_attn_bwd_dropout", "oeh_attn_dropout_mask",
     "oeh_abi_version", "oeh_build_info", "oeh_strerror", "oeh_attn_variant",
 )
 
@@ -124,6 +130,13 @@ def load() -> C.CDLL:
     lib.oeh_attn_bwd.argtypes = [C.POINTER(oeh_attn_desc), vp, vp, vp, vp, vp, C.POINTER(i64), vp, vp, C.POINTER(i64), vp, C.POINTER(i64), vp,
                                  C.POINTER(i64), vp, vp]
     lib.oeh_attn_bwd.restype = C.c_int
+    lib.oeh_attn_fwd_train_dropout.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_dropout), vp, vp, vp, vp, vp, vp]
+    lib.oeh_attn_fwd_train_dropout.restype = C.c_int
+    lib.oeh_attn_bwd_dropout.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_dropout), vp, vp, vp, vp, vp, C.POINTER(i64), vp, vp, C.POINTER(i64), vp,
+                                         C.POINTER(i64), vp, C.POINTER(i64), vp, vp]
+    lib.oeh_attn_bwd_dropout.restype = C.c_int
+    lib.oeh_attn_dropout_mask.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_dropout), vp, vp]
+    lib.oeh_attn_dropout_mask.restype = C.c_int
     lib.oeh_abi_version.restype = C.c_int
     lib.oeh_build_info.restype = C.c_char_p
     lib.oeh_strerror.argtypes = [C.c_int]

@@ -423,8 +423,8 @@ def attention_core(
 
 
 # ---- training on the fused kernels (opt-in): with FUSED_BACKWARD on, a module whose forward has to be differentiable and needs none of
-# the observable path's features (dropout > 0 in training, output_attentions, hooks on the taps, head_mask, fake-quant, user callables)
-# runs its core through autograd_attention.fused_attention - the HIP training forward and backward, nothing of size Sq x Sk saved -
+# the observable path's features (dropout > 0 in training unless FUSED_DROPOUT, output_attentions, hooks on the taps, head_mask,
+# fake-quant, user callables) runs its core through autograd_attention.fused_attention - the HIP training forward and backward, nothing of size Sq x Sk saved -
 # instead of unfused_core.  fp16 / bf16, head dim 64; anything else keeps the torch-op path.  Off by default.
 FUSED_BACKWARD = False
 
@@ -435,14 +435,33 @@ def set_fused_backward(on: bool = True) -> None:
     FUSED_BACKWARD = bool(on)
 
 
+# ---- attention dropout on the fused kernels (opt-in on top of FUSED_BACKWARD): with FUSED_DROPOUT on as well, a module training with
+# attention dropout 0 < p < 1 (and none of the other observable-path features) runs it inside the kernels - a counter-based mask from
+# a seed (autograd_attention), nothing of size Sq x Sk stored.  Off by default: the fused mask is a different random stream from
+# nn.Dropout's, so turning it on changes which probabilities a seeded run drops.
+FUSED_DROPOUT = False
+
+
+def set_fused_dropout(on: bool = True) -> None:
+    """Run the modules' attention dropout inside the fused training kernels (True; needs set_fused_backward(True) too) or keep it on the
+    torch-op path (False, the default)."""
+    global FUSED_DROPOUT
+    FUSED_DROPOUT = bool(on)
+
+
 def fused_train_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax_fn, scale: float = 1.0, scale_div: float = 0.0,
-                     attention_mask: Optional[torch.Tensor] = None, clamp_min: bool = False, detect_causal: bool = False) -> Optional[torch.Tensor]:
+                     attention_mask: Optional[torch.Tensor] = None, clamp_min: bool = False, detect_causal: bool = False,
+                     dropout_p: float = 0.0) -> Optional[torch.Tensor]:
     """The differentiable core on the fused training kernels: logical (B,H,Sq,d) context, or None when FUSED_BACKWARD is off or the
     problem is not one the kernels take (the caller then runs unfused_core).  Same score chain as unfused_core: the clamp floor is
-    finfo of the scores' dtype; a decoder mask becomes the analytic causal mask plus a key-padding vector."""
+    finfo of the scores' dtype; a decoder mask becomes the analytic causal mask plus a key-padding vector.  dropout_p: the attention
+    dropout the module applies now (0 in eval); p > 0 needs FUSED_DROPOUT and p < 1, else None."""
     from .autograd_attention import fused_attention, fused_supported
 
     if not FUSED_BACKWARD or not fused_supported(q, k, v, softmax_fn):
+        return None
+    dropout_p = float(dropout_p)
+    if dropout_p != 0.0 and not (FUSED_DROPOUT and 0.0 < dropout_p < 1.0):
         return None
     B, H, Sq, _ = q.shape
     Sk = k.shape[2]
@@ -454,7 +473,7 @@ def fused_train_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softm
             full, pad = None, padvec
     clamp = clamp_min and attention_mask is not None
     return fused_attention(q, k, v, softmax=spec_of(softmax_fn), scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full,
-                           causal=causal, clamp_min=clamp, mask_min=float(torch.finfo(q.dtype).min))
+                           causal=causal, clamp_min=clamp, mask_min=float(torch.finfo(q.dtype).min), dropout_p=dropout_p)
 
 
 def unfused_core(

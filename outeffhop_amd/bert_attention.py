@@ -138,10 +138,12 @@ class BertSelfAttentionWithExtras(GateBookkeeping, nn.Module):
                 GateState.finish_predictor(self, gp, self.num_attention_heads)
         else:
             ctx = None
-            if (self.position_embedding_type == "absolute" and head_mask is None and not output_attentions and not (self.training and self.dropout.p > 0.0)
+            if (self.position_embedding_type == "absolute" and head_mask is None and not output_attentions
                     and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout)):
-                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported)
-                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale_div=div, attention_mask=attention_mask)
+                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
+                # also needs attention.FUSED_DROPOUT)
+                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale_div=div, attention_mask=attention_mask,
+                                       dropout_p=self.dropout.p if self.training else 0.0)
             if ctx is not None:
                 if gate is not None:
                     ctx = ctx * gate.to(ctx.dtype)

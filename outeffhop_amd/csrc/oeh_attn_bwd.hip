@@ -23,7 +23,9 @@
 // or 16 t1 + 4 g + j - 4, and the other operand is read from a TRANSPOSED LDS image in that order (two ds_read_b64).
 #include "../../include/oeh.h"
 #include "oeh_common.h"
+#include "oeh_philox.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -55,6 +57,8 @@ struct Params {
   float mask_min;
   int skip_ok;
   int nQT, nKT;
+  unsigned drop_k0, drop_k1, drop_thr;  // dropout (the DROP instantiations): Philox key, keep threshold (oeh_philox.h),
+  float drop_scale;                     // and 1 / (1 - p)
 };
 
 template <int IN>
@@ -162,8 +166,39 @@ __device__ __forceinline__ int first_query_tile(const Params& P, int kt) {
   return first_visible_q <= 0 ? 0 : first_visible_q / T;
 }
 
+// dropout factors keep / (1 - p) (0 where dropped) of keys key0 .. key0 + 3 (key0 % 4 == 0) of query qi: the fwd / dq layout, where a
+// lane holds 4 consecutive keys of one query - one Philox block
+__device__ __forceinline__ f4 drop4(const Params& P, int bh, int qi, int key0) {
+  const Philox4 r = dropout_words((unsigned)key0 >> 2, (unsigned)qi, (unsigned)bh, P.drop_k0, P.drop_k1);
+  return f4{r.x[0] >= P.drop_thr ? P.drop_scale : 0.0f, r.x[1] >= P.drop_thr ? P.drop_scale : 0.0f, r.x[2] >= P.drop_thr ? P.drop_scale : 0.0f,
+            r.x[3] >= P.drop_thr ? P.drop_scale : 0.0f};
+}
+
+// the dkdv layout: a lane holds ONE key ki and queries q0 + 16 t + 4 g + i (t, i < 4), and the 4 keys of a Philox block sit in the 4
+// lanes of a DPP quad (lane & 3 == ki & 3, same g).  Lane r of the quad draws the blocks of queries q0 + 16 t + 4 g + r and turns each
+// into a keep nibble (bit m: key 4 (ki >> 2) + m); two quad_perm xor exchanges give every lane all 16 nibbles - 4 Philox calls per
+// lane per tile instead of 16.  Returned shifted by r: keep(t, i) of the lane's own key is bit 16 (t & 1) + 4 i of word t >> 1.
+__device__ __forceinline__ u2 drop_bits_quad(const Params& P, int bh, int q0, int g, int ki) {
+  const int r = ki & 3;
+  unsigned thr = P.drop_thr;
+  asm volatile("" : "+v"(thr));  // (held in a vector register: the kernel is at the scalar register limit)
+  unsigned x[2] = {0u, 0u};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const Philox4 w = dropout_words((unsigned)ki >> 2, (unsigned)(q0 + 16 * t + 4 * g + r), (unsigned)bh, P.drop_k0, P.drop_k1);
+    const unsigned nib = (unsigned)(w.x[0] >= thr) | ((unsigned)(w.x[1] >= thr) << 1) | ((unsigned)(w.x[2] >= thr) << 2) | ((unsigned)(w.x[3] >= thr) << 3);
+    x[t >> 1] |= nib << (16 * (t & 1) + 4 * r);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    x[j] |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x[j], 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+    x[j] |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x[j], 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+  }
+  return u2{x[0] >> r, x[1] >> r};
+}
+
 // ---------------------------------------------------------------- forward (training): O and lse
-template <int IN>
+template <int IN, bool DROP>
 __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
   __shared__ __attribute__((aligned(16))) unsigned short Ks[T * LD];
   __shared__ __attribute__((aligned(16))) unsigned short Vt[D * LD];
@@ -247,6 +282,12 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
         for (int t = 0; t < 4; ++t) ls += (p[t][0] + p[t][1]) + (p[t][2] + p[t][3]);
         l = l * alpha + ls;
       }
+      if constexpr (DROP) {  // z = keep y / (1 - p) into the product only: the row statistics stay those of the undropped row
+        if (pv) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) p[t] = p[t] * drop4(P, bh, qi, kt * T + 16 * t + 4 * g);
+        }
+      }
       if (pv) {
         if (!P.clip) {
 #pragma unroll
@@ -283,7 +324,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
 }
 
 // ---------------------------------------------------------------- dQ (and the row term delta)
-template <int IN>
+template <int IN, bool DROP>
 __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
   __shared__ __attribute__((aligned(16))) unsigned short Ks[T * LD];
   __shared__ __attribute__((aligned(16))) unsigned short Vs[T * LD];
@@ -347,6 +388,7 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
           s = mma<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
           dy = mma<IN>(a_rows(Vs, 16 * t, kc, lane), df[kc], dy);
         }
+        if constexpr (DROP) dy = dy * drop4(P, bh, qi, kt * T + 16 * t + 4 * g);  // dY = keep / (1 - p) dZ
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int kl = 16 * t + 4 * g + i, ki = kt * T + kl;
@@ -385,7 +427,7 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
 }
 
 // ---------------------------------------------------------------- dK and dV
-template <int IN>
+template <int IN, bool DROP>
 __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
   __shared__ __attribute__((aligned(16))) unsigned short Qs[T * LD];
   __shared__ __attribute__((aligned(16))) unsigned short Qt[D * LD];
@@ -423,6 +465,8 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
       deltaS[threadIdx.x] = qq < P.Sq ? P.delta[(long)bh * P.Sq + qq] : 0.0f;
     }
     __syncthreads();
+    u2 kb = u2{0u, 0u};
+    if constexpr (DROP) kb = drop_bits_quad(P, bh, qt * T, g, ki);
     f4 y[4], dx[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -439,6 +483,13 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
         const float x = score(P, s[i], b, qi, ki, padv);
         const float p = ok ? expf(x - lseS[ql]) : 0.0f;
         float yy;
+        if constexpr (DROP) {  // dV takes z = keep y / (1 - p), dX takes dY = keep / (1 - p) dZ
+          const float f = ((kb[t >> 1] >> (16 * (t & 1) + 4 * i)) & 1u) ? P.drop_scale : 0.0f;
+          const float d = dx_of(P, p, dy[i] * f, deltaS[ql], yy);
+          y[t][i] = ok ? yy * f : 0.0f;
+          dx[t][i] = ok ? d * clamp_pass(P, s[i], b, qi, ki, padv) : 0.0f;
+          continue;
+        }
         const float d = dx_of(P, p, dy[i], deltaS[ql], yy);
         y[t][i] = ok ? yy : 0.0f;
         dx[t][i] = ok ? d * clamp_pass(P, s[i], b, qi, ki, padv) : 0.0f;
@@ -522,15 +573,37 @@ void fill(Params& P, const oeh_attn_desc* d) {
 
 int launched() { return hipGetLastError() == hipSuccess ? OEH_OK : OEH_ELAUNCH; }
 
-}  // namespace bwd
-}  // namespace oeh
+// the dropout descriptor (include/oeh.h: oeh_dropout): p in [0, 1), NaN refused; checked before anything else of an entry point
+int check_drop(const oeh_dropout* drop) {
+  if (drop == nullptr) return OEH_EINVAL;
+  if (!(drop->p >= 0.0f && drop->p < 1.0f)) return OEH_EINVAL;
+  return OEH_OK;
+}
+void fill_drop(Params& P, const oeh_dropout* drop) {
+  P.drop_k0 = (unsigned)(drop->seed & 0xffffffffu);
+  P.drop_k1 = (unsigned)(drop->seed >> 32);
+  P.drop_thr = dropout_threshold(drop->p);
+  P.drop_scale = 1.0f / (1.0f - drop->p);
+}
 
-using namespace oeh;
-using namespace oeh::bwd;
+// the (B,H,Sq,Sk) keep mask, one Philox block (4 keys of one query) per thread, grid-stride
+__global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char* keep, int BH, int Sq, int Sk, unsigned k0, unsigned k1, unsigned thr) {
+  const int nc = (Sk + 3) >> 2;
+  const long n = (long)BH * Sq * nc;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+    const long row = e / nc;
+    const int c = (int)(e - row * nc);
+    const int qi = (int)(row % Sq), bh = (int)(row / Sq);
+    const Philox4 w = dropout_words((unsigned)c, (unsigned)qi, (unsigned)bh, k0, k1);
+    unsigned char* o = keep + row * Sk + 4 * c;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+      if (4 * c + m < Sk) o[m] = w.x[m] >= thr ? 1 : 0;
+  }
+}
 
-extern "C" {
-
-int oeh_attn_fwd_train(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, float* lse, void* stream) {
+// the entry points' bodies; drop == nullptr (or p == 0): the DROP = false kernels
+int fwd_train(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, void* o, float* lse, void* stream) {
   int rc = check_desc(desc);
   if (rc != OEH_OK) return rc;
   if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || lse == nullptr) return OEH_EINVAL;
@@ -540,22 +613,23 @@ int oeh_attn_fwd_train(const oeh_attn_desc* desc, const void* q, const void* k, 
   Params P;
   fill(P, desc);
   P.q = q; P.k = k; P.v = v; P.out = o; P.lse = lse;
+  const bool dr = drop != nullptr && drop->p > 0.0f;
+  if (dr) fill_drop(P, drop);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(P.nQT * P.B * P.H));
-  if (desc->dtype == OEH_BF16) hipLaunchKernelGGL(fwd_kernel<IN_BF16>, grid, dim3(256), 0, st, P);
-  else hipLaunchKernelGGL(fwd_kernel<IN_F16>, grid, dim3(256), 0, st, P);
+  if (desc->dtype == OEH_BF16) {
+    if (dr) hipLaunchKernelGGL((fwd_kernel<IN_BF16, true>), grid, dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((fwd_kernel<IN_BF16, false>), grid, dim3(256), 0, st, P);
+  } else {
+    if (dr) hipLaunchKernelGGL((fwd_kernel<IN_F16, true>), grid, dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((fwd_kernel<IN_F16, false>), grid, dim3(256), 0, st, P);
+  }
   return launched();
 }
 
-int64_t oeh_attn_bwd_work_bytes(const oeh_attn_desc* desc) {
-  const int rc = check_desc(desc);
-  if (rc != OEH_OK) return rc;
-  return (int64_t)desc->B * desc->H * desc->Sq * (int64_t)sizeof(float);
-}
-
-int oeh_attn_bwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, const void* o, const void* do_,
-                 const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk, const int64_t dk_stride[3],
-                 void* dv, const int64_t dv_stride[3], void* work, void* stream) {
+int bwd_run(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, const void* o, const void* do_,
+            const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk, const int64_t dk_stride[3], void* dv,
+            const int64_t dv_stride[3], void* work, void* stream) {
   int rc = check_desc(desc);
   if (rc != OEH_OK) return rc;
   if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || do_ == nullptr || lse == nullptr || dq == nullptr || dk == nullptr ||
@@ -574,16 +648,83 @@ int oeh_attn_bwd(const oeh_attn_desc* desc, const void* q, const void* k, const 
   P.dqs_b = dq_stride[0]; P.dqs_h = dq_stride[1]; P.dqs_s = dq_stride[2];
   P.dks_b = dk_stride[0]; P.dks_h = dk_stride[1]; P.dks_s = dk_stride[2];
   P.dvs_b = dv_stride[0]; P.dvs_h = dv_stride[1]; P.dvs_s = dv_stride[2];
+  const bool dr = drop != nullptr && drop->p > 0.0f;
+  if (dr) fill_drop(P, drop);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 gq((unsigned)(P.nQT * P.B * P.H)), gk((unsigned)(P.nKT * P.B * P.H));
   // dq first: it writes delta, which dkdv reads (stream order)
   if (desc->dtype == OEH_BF16) {
-    hipLaunchKernelGGL(dq_kernel<IN_BF16>, gq, dim3(256), 0, st, P);
-    hipLaunchKernelGGL(dkdv_kernel<IN_BF16>, gk, dim3(256), 0, st, P);
+    if (dr) {
+      hipLaunchKernelGGL((dq_kernel<IN_BF16, true>), gq, dim3(256), 0, st, P);
+      hipLaunchKernelGGL((dkdv_kernel<IN_BF16, true>), gk, dim3(256), 0, st, P);
+    } else {
+      hipLaunchKernelGGL((dq_kernel<IN_BF16, false>), gq, dim3(256), 0, st, P);
+      hipLaunchKernelGGL((dkdv_kernel<IN_BF16, false>), gk, dim3(256), 0, st, P);
+    }
   } else {
-    hipLaunchKernelGGL(dq_kernel<IN_F16>, gq, dim3(256), 0, st, P);
-    hipLaunchKernelGGL(dkdv_kernel<IN_F16>, gk, dim3(256), 0, st, P);
+    if (dr) {
+      hipLaunchKernelGGL((dq_kernel<IN_F16, true>), gq, dim3(256), 0, st, P);
+      hipLaunchKernelGGL((dkdv_kernel<IN_F16, true>), gk, dim3(256), 0, st, P);
+    } else {
+      hipLaunchKernelGGL((dq_kernel<IN_F16, false>), gq, dim3(256), 0, st, P);
+      hipLaunchKernelGGL((dkdv_kernel<IN_F16, false>), gk, dim3(256), 0, st, P);
+    }
   }
+  return launched();
+}
+
+}  // namespace bwd
+}  // namespace oeh
+
+using namespace oeh;
+using namespace oeh::bwd;
+
+extern "C" {
+
+int oeh_attn_fwd_train(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, float* lse, void* stream) {
+  return fwd_train(desc, nullptr, q, k, v, o, lse, stream);
+}
+
+int oeh_attn_fwd_train_dropout(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, void* o, float* lse,
+                               void* stream) {
+  const int rc = check_drop(drop);
+  if (rc != OEH_OK) return rc;
+  return fwd_train(desc, drop, q, k, v, o, lse, stream);
+}
+
+int64_t oeh_attn_bwd_work_bytes(const oeh_attn_desc* desc) {
+  const int rc = check_desc(desc);
+  if (rc != OEH_OK) return rc;
+  return (int64_t)desc->B * desc->H * desc->Sq * (int64_t)sizeof(float);
+}
+
+int oeh_attn_bwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, const void* o, const void* do_,
+                 const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk, const int64_t dk_stride[3],
+                 void* dv, const int64_t dv_stride[3], void* work, void* stream) {
+  return bwd_run(desc, nullptr, q, k, v, o, do_, do_stride, lse, dq, dq_stride, dk, dk_stride, dv, dv_stride, work, stream);
+}
+
+int oeh_attn_bwd_dropout(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, const void* o,
+                         const void* do_, const int64_t do_stride[3], const float* lse, void* dq, const int64_t dq_stride[3], void* dk,
+                         const int64_t dk_stride[3], void* dv, const int64_t dv_stride[3], void* work, void* stream) {
+  const int rc = check_drop(drop);
+  if (rc != OEH_OK) return rc;
+  return bwd_run(desc, drop, q, k, v, o, do_, do_stride, lse, dq, dq_stride, dk, dk_stride, dv, dv_stride, work, stream);
+}
+
+int oeh_attn_dropout_mask(const oeh_attn_desc* desc, const oeh_dropout* drop, uint8_t* keep, void* stream) {
+  int rc = check_drop(drop);
+  if (rc != OEH_OK) return rc;
+  if (desc == nullptr || keep == nullptr) return OEH_EINVAL;
+  if (desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0) return OEH_EINVAL;
+  if ((int64_t)desc->B * desc->H >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
+  Params P;
+  std::memset(&P, 0, sizeof(P));
+  if (drop->p > 0.0f) fill_drop(P, drop);  // (p == 0: threshold 0, every element kept)
+  const int64_t n = (int64_t)desc->B * desc->H * desc->Sq * ((desc->Sk + 3) / 4);
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 16384);
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), keep, desc->B * desc->H, desc->Sq,
+                     desc->Sk, P.drop_k0, P.drop_k1, P.drop_thr);
   return launched();
 }
 

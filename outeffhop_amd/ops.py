@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import OEH_BF16, OEH_F16, OEH_F32, oeh_attn_desc, oeh_fq, oeh_fq_desc
+from ._lib import OEH_BF16, OEH_F16, OEH_F32, oeh_attn_desc, oeh_dropout, oeh_fq, oeh_fq_desc
 
 _DT = {torch.float16: OEH_F16, torch.bfloat16: OEH_BF16, torch.float32: OEH_F32}
 
@@ -900,10 +900,27 @@ def train_supported(q: torch.Tensor, softmax: SoftmaxSpec) -> bool:
     return q.dtype in (torch.float16, torch.bfloat16) and q.dim() == 4 and q.shape[3] == 64 and softmax is not None
 
 
+def _dropout(p, seed):
+    """oeh_dropout of (dropout_p, dropout_seed), or None for p == 0 (the entry points without dropout).  The library validates p
+    (outside [0, 1) or NaN: OEH_EINVAL); the seed is a uint64 and has to be given with p != 0."""
+    p = float(p)
+    if p == 0.0:
+        return None
+    if seed is None:
+        raise ValueError("dropout_p != 0 needs a dropout_seed (uint64)")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"dropout_seed must be a uint64, got {seed}")
+    return oeh_dropout(p, 0, seed)
+
+
 def attn_fwd_train(q, k, v, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0, key_pad_mask=None,
-                   full_mask=None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None):
+                   full_mask=None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None, dropout_p: float = 0.0,
+                   dropout_seed: Optional[int] = None):
     """The attention core's forward for training: (o, lse).  o is the logical (B,H,Sq,D) result stored (B,Sq,H,D)-contiguous as attn_fwd's;
-    lse (B,H,Sq) fp32 is the row statistic the backward recomputes the probabilities from.  No autograd here (see `fused_attention`)."""
+    lse (B,H,Sq) fp32 is the row statistic the backward recomputes the probabilities from.  No autograd here (see `fused_attention`).
+    dropout_p > 0: attention dropout inside the kernel (include/oeh.h: oeh_attn_fwd_train_dropout), its mask drawn from dropout_seed -
+    the backward needs the same two values; lse does not depend on them."""
     dev = _need_gpu(q, k, v, key_pad_mask, full_mask, allow_grad=True)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k, v must be 4-D (B,H,S,D) views")
@@ -912,18 +929,24 @@ def attn_fwd_train(q, k, v, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: floa
     o = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     d, keep = _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min)
+    drop = _dropout(dropout_p, dropout_seed)
     lib = _lib.load()
     with _on_device(dev):
-        rc = lib.oeh_attn_fwd_train(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream())
-    _lib.check(rc, "oeh_attn_fwd_train")
+        if drop is None:
+            rc = lib.oeh_attn_fwd_train(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream())
+        else:
+            rc = lib.oeh_attn_fwd_train_dropout(C.byref(d), C.byref(drop), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream())
+    _lib.check(rc, "oeh_attn_fwd_train" if drop is None else "oeh_attn_fwd_train_dropout")
     del keep
     return o, lse
 
 
 def attn_bwd(q, k, v, o, do, lse, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0, key_pad_mask=None,
-             full_mask=None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None):
+             full_mask=None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None, dropout_p: float = 0.0,
+             dropout_seed: Optional[int] = None):
     """(dq, dk, dv) of the attention core from the forward's o and lse (attn_fwd_train) and the output gradient do; same options as that
-    call.  Two HIP kernels, deterministic (no atomics); the gradients are (B,S,H,D)-contiguous (B,H,S,D) views in the input dtype."""
+    call, dropout_p / dropout_seed included.  Two HIP kernels, deterministic (no atomics); the gradients are (B,S,H,D)-contiguous (B,H,S,D)
+    views in the input dtype."""
     dev = _need_gpu(q, k, v, o, do, lse, key_pad_mask, full_mask, allow_grad=True)
     q, k, v, o, do = (_rows16(t.detach()) for t in (q, k, v, o, do))
     if do.shape != o.shape or do.dtype != o.dtype:
@@ -941,9 +964,32 @@ def attn_bwd(q, k, v, o, do, lse, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale
         _lib.check(int(nbytes), "oeh_attn_bwd_work_bytes")
     work = torch.empty((max(1, nbytes // 4),), dtype=torch.float32, device=q.device)
     st = lambda t: (C.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2))  # noqa: E731
+    drop = _dropout(dropout_p, dropout_seed)
     with _on_device(dev):
-        rc = lib.oeh_attn_bwd(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), st(do), _ptr(lse), _ptr(dq), st(dq), _ptr(dk), st(dk),
-                              _ptr(dv), st(dv), _ptr(work), _stream())
-    _lib.check(rc, "oeh_attn_bwd")
+        if drop is None:
+            rc = lib.oeh_attn_bwd(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), st(do), _ptr(lse), _ptr(dq), st(dq), _ptr(dk), st(dk),
+                                  _ptr(dv), st(dv), _ptr(work), _stream())
+        else:
+            rc = lib.oeh_attn_bwd_dropout(C.byref(d), C.byref(drop), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), st(do), _ptr(lse), _ptr(dq),
+                                          st(dq), _ptr(dk), st(dk), _ptr(dv), st(dv), _ptr(work), _stream())
+    _lib.check(rc, "oeh_attn_bwd" if drop is None else "oeh_attn_bwd_dropout")
     del keep
     return dq, dk, dv
+
+
+def attn_dropout_mask(B: int, H: int, Sq: int, Sk: int, p: float, seed: int, device) -> torch.Tensor:
+    """The keep mask the training kernels apply for (p, seed): a (B,H,Sq,Sk) bool tensor on `device`, True where an attention
+    probability is kept (and scaled by 1 / (1 - p)).  include/oeh.h: oeh_attn_dropout_mask; p == 0 keeps everything."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    d = oeh_attn_desc()
+    d.B, d.H, d.Sq, d.Sk = int(B), int(H), int(Sq), int(Sk)
+    p = float(p)
+    drop = oeh_dropout(p, 0, int(seed) if seed is not None else 0) if p == 0.0 else _dropout(p, seed)
+    keep = torch.empty((B, H, Sq, Sk), dtype=torch.uint8, device=device)
+    lib = _lib.load()
+    with _on_device(device):
+        rc = lib.oeh_attn_dropout_mask(C.byref(d), C.byref(drop), _ptr(keep), _stream())
+    _lib.check(rc, "oeh_attn_dropout_mask")
+    return keep.view(torch.bool)

@@ -125,10 +125,12 @@ class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
                 GateState.finish_predictor(self, gp, self.num_heads)
         else:
             ctx = None
-            if (layer_head_mask is None and not output_attentions and not (self.training and self.dropout > 0.0)
+            if (layer_head_mask is None and not output_attentions
                     and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout)):
-                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported)
-                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=True, detect_causal=True)
+                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
+                # also needs attention.FUSED_DROPOUT)
+                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=True, detect_causal=True,
+                                       dropout_p=self.dropout if self.training else 0.0)
             if ctx is not None:
                 if gate is not None:
                     ctx = ctx * gate.to(ctx.dtype)

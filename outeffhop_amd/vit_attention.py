@@ -78,9 +78,10 @@ class ViTSelfAttentionWithExtras(GateBookkeeping, nn.Module):
                 GateState.finish_predictor(self, gp, H)
         else:
             ctx = None
-            if not (self.training and self.attn_drop.p > 0.0) and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout):
-                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported)
-                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale)
+            if not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout):
+                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
+                # also needs attention.FUSED_DROPOUT)
+                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale, dropout_p=self.attn_drop.p if self.training else 0.0)
             if ctx is not None:
                 if gate is not None:
                     ctx = ctx * gate.to(ctx.dtype)

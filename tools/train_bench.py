@@ -10,7 +10,12 @@ beyond the inputs (torch.cuda.max_memory_allocated), and the fused path's roofli
   bytes = (q, k, v, o, dO in + dq, dk, dv out) = 8 B H S D x 2 bytes;
   roofline = max(FLOPs / 2500 TFLOP/s, bytes / 8 TB/s) (MI355X fp16 / bf16 dense MFMA and HBM peaks), frac = roofline / measured.
 
-    python tools/train_bench.py [--iters 50] [--warmup 10] [--only opt|bert]
+With --attn-dropout P (0 < P < 1) two more paths run attention dropout at P, as the modules do in training:
+  fused_drop    fused_attention(dropout_p=P): the mask drawn inside the kernels (a fresh seed per call), still nothing S x S stored
+  torchop_drop  unfused_core with nn.functional.dropout on the probabilities (the observable path's dropout)
+and every row carries "attn_dropout" (0 for the paths without it).
+
+    python tools/train_bench.py [--iters 50] [--warmup 10] [--only opt|bert] [--attn-dropout 0.1]
 """
 import argparse
 import json
@@ -61,15 +66,19 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--paths", default="fused,torchop,sdpa")
+    ap.add_argument("--paths", default=None, help="comma list (default: fused,torchop,sdpa and, with --attn-dropout, fused_drop,torchop_drop)")
+    ap.add_argument("--attn-dropout", type=float, default=0.0)
     a = ap.parse_args()
+    if not 0.0 <= a.attn_dropout < 1.0:
+        raise SystemExit("--attn-dropout must be in [0, 1)")
     if not torch.cuda.is_available():
         raise SystemExit("train_bench needs a GPU (there is no CPU timing of HIP kernels)")
     from outeffhop_amd import SOFTMAX_MAPPING, fused_attention
     from outeffhop_amd.attention import unfused_core
     from outeffhop_amd.softmax import spec_of
 
-    paths = a.paths.split(",")
+    pd = a.attn_dropout
+    paths = (a.paths or ("fused,torchop,sdpa" + (",fused_drop,torchop_drop" if pd > 0 else ""))).split(",")
     dt = torch.float16
     for name, B, H, S, causal, padded, sms in SHAPES:
         if a.only and name != a.only:
@@ -102,6 +111,12 @@ def main():
                 "torchop": lambda: torch.autograd.grad(
                     unfused_core(q, k, v, softmax_fn=up, attention_mask=am, clamp_min=causal)[0], (q, k, v), do),
             }
+            if pd > 0:
+                drop = (lambda t: torch.nn.functional.dropout(t, p=pd, training=True))
+                runs["fused_drop"] = lambda: torch.autograd.grad(
+                    fused_attention(q, k, v, softmax=spec, key_pad_mask=pad, causal=causal, clamp_min=causal, dropout_p=pd), (q, k, v), do)
+                runs["torchop_drop"] = lambda: torch.autograd.grad(
+                    unfused_core(q, k, v, softmax_fn=up, attention_mask=am, clamp_min=causal, dropout=drop)[0], (q, k, v), do)
             if spec.base == 0 and not spec.clip:
                 runs["sdpa"] = lambda: torch.autograd.grad(
                     torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=None if causal else am, is_causal=causal, scale=1.0),
@@ -114,7 +129,9 @@ def main():
                 rec = {"shape": name, "B": B, "H": H, "S": S, "D": 64, "causal": causal, "key_pad": padded, "softmax": smname, "path": path,
                        "dtype": "f16", "us_fwd_bwd": round(med, 1), "us_min": round(lo, 1), "us_max": round(hi, 1), "iters": a.iters,
                        "peak_mem_mb": round(mem / 2 ** 20, 1)}
-                if path == "fused":
+                if pd > 0:
+                    rec["attn_dropout"] = pd if path.endswith("_drop") else 0.0
+                if path in ("fused", "fused_drop"):
                     rec["roofline"] = {"flops": flops, "bytes": nbytes, "bound": "mfma" if flops / (PEAK_TFLOPS * 1e12) >= nbytes / (PEAK_TBS * 1e12)
                                        else "hbm", "roofline_us": round(roof_us, 2), "frac": round(roof_us / med, 4),
                                        "tflops": round(flops / med * 1e-6, 1)}

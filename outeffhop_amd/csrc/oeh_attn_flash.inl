@@ -25,17 +25,6 @@
 #pragma once
 #include "oeh_attn_fast.inl"
 
-// Knock-out ladder of the one-pass kernel (diagnostic builds only: make -C outeffhop_amd/csrc knockout KO=n; profiles/r05_headline_floor.txt).
-// 0 (production): everything.  1: return at entry.  2: + the prologue and the whole LDS-DMA stream with its waits and barriers, nothing else.
-// 3: + both products' MFMAs and their LDS fragment reads (the second product on the raw bits of the scores).  4: + the softmax arithmetic (the full
-// tile).  2 - 4 skip the epilogue (its stores sit behind a never-true test of an accumulator, so that nothing above is dead code).
-#ifndef OEH_KO
-#define OEH_KO 0
-#endif
-#ifndef OEH_NSUB_MASK
-#define OEH_NSUB_MASK 1
-#endif
-
 #include <type_traits>
 
 namespace oeh {
@@ -113,9 +102,6 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
   if (SRC32 && P.head_major) block_to_tile(bid, P.nBHpad, P.nQT, P.head_major, qt_rev, bh);
   else div_magic((unsigned)bid, (unsigned)P.nBHpad, P.magic_nbh, qt_rev, bh);
   if (bh >= P.nBH) return;
-#if OEH_KO == 1
-  return;
-#endif
   int b, h;
   div_magic((unsigned)bh, (unsigned)P.H, P.magic_h, b, h);
 
@@ -202,19 +188,6 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
 #pragma unroll
       for (int j = 0; j < G; ++j) glds16_s(vcur, voff[j], slot + TILEB + j * 1024);
     }
-    kcur += kstep;
-    vcur += vstep;
-    ++nx_tile;
-    nx_slot = (nx_slot == R - 1) ? 0 : nx_slot + 1;
-  };
-  // (round 6, OEH_PIPE_QK == 1: the same stage request in its 2 G pieces, so that the placed tile can put one behind each sub-tile's score MFMAs;
-  // full stages only - the ragged last stage is never requested from inside a tile: the caller tests `nx_tile * 64 + 64 <= Sk`)
-  [[maybe_unused]] auto issue_piece = [&](const int p) {
-    const unsigned slot = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(nx_slot * STAGEB + wave * G * 1024));
-    if (p < G) glds16_s(kcur, koff[p], slot + p * 1024);
-    else glds16_s(vcur, voff[p - G], slot + TILEB + (p - G) * 1024);
-  };
-  [[maybe_unused]] auto issue_advance = [&]() {
     kcur += kstep;
     vcur += vstep;
     ++nx_tile;
@@ -468,128 +441,34 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
   // the ones operand of the row-sum MFMAs, kept in registers across the tile loop (round 6: it was rebuilt - five v_mov - in every tile)
   u4 ones_live = ones;
   asm volatile("" : "+v"(ones_live));
-  // Issue priority of the wave's two kinds of phase (matrix-core / vector).  OEH_PRIO_MODE (round 6 experiment, not landed: profiles/r06_headline_tile_asm.txt):
-  // 0 = production (1 / 0 for every wave); 1 = the workgroups of the upper half of the causal q tiles outrank the others in both phases (3 / 2 against 1 / 0);
-  // 2 = only the heaviest q tile's; 3 = a constant level by q tile, no boost for the matrix-core phases
-#ifndef OEH_PRIO_MODE
-#define OEH_PRIO_MODE 0
-#endif
-#if OEH_PRIO_MODE == 0
+  // issue priority of the wave's two kinds of phase: matrix-core phases at 1, vector phases at 0
   auto prio_hi = [&]() { __builtin_amdgcn_s_setprio(1); };
   auto prio_lo = [&]() { __builtin_amdgcn_s_setprio(0); };
-#else
-#if OEH_PRIO_MODE == 1
-  const bool prio_heavy = causal && 2 * qt >= P.nQT;
-#elif OEH_PRIO_MODE == 2
-  const bool prio_heavy = causal && qt == P.nQT - 1;
-#else
-  const int prio_lvl = causal ? min(3, (4 * qt) / max(1, P.nQT)) : 0;
-#endif
-#if OEH_PRIO_MODE == 3
-  auto prio_set = [&]() { if (prio_lvl == 3) __builtin_amdgcn_s_setprio(3); else if (prio_lvl == 2) __builtin_amdgcn_s_setprio(2); else if (prio_lvl == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); };
-  prio_set();
-  auto prio_hi = [&]() {};
-  auto prio_lo = [&]() {};
-#else
-  auto prio_hi = [&]() { if (prio_heavy) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(1); };
-  auto prio_lo = [&]() { if (prio_heavy) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0); };
-#endif
-#endif
   // ---- one 64-key tile for blocks J0..MQ-1 of this wave (J0 = 1: block 0's rows end before this tile)
   // MODE 0: the one-pass tile; CLIP: 1 = statistics pass (no second product), 2 = final pass (final reference, clip)
-  auto tile = [&](auto j0c, auto firstc, auto modec, auto nsc, const int i, const int soff, const bool in_tile_issue = false) {
+  auto tile = [&](auto j0c, auto firstc, auto modec, auto nsc, const int i, const int soff) {
     constexpr int J0 = decltype(j0c)::value;
     constexpr bool FIRST = decltype(firstc)::value;  // tile 0: V tile 0 is awaited between the two products
     constexpr int MODE = decltype(modec)::value;
-    // Round 6: NSa[j] = how many of the tile's four 16-key sub-tiles hold a key that ANY row of block j may see (4 = all; the caller passes
-    // fewer only for the placed order below).  The sub-tiles behind are masked for the whole block (the causal diagonal, the ragged last
-    // tile): their scores would be set to the sentinel, their exponentials are exactly 0 and their products add exactly 0 - so the MFMAs,
-    // the scale / max / exp / convert steps and the K fragment reads of those sub-tiles are simply not issued; results bit for bit the same.
+    // Round 6: NSa[j] = how many of the tile's four 16-key sub-tiles hold a key that ANY row of block j may see (4 = all).  The caller passes
+    // fewer only for block 1 alone on the MQ == 2 causal diagonal (placed order below; block 0 is then inactive, every other call is a full
+    // tile).  The sub-tiles behind are masked for the whole block: their scores would be set to the sentinel, their exponentials are exactly 0
+    // and their products add exactly 0 - so the MFMAs, the scale / max / exp / convert steps and the K fragment reads of those sub-tiles are
+    // simply not issued; results bit for bit the same.
     constexpr int NSP = decltype(nsc)::value;
     constexpr int NSa[2] = {NSP & 15, (NSP >> 4) & 15};
-    constexpr int NSMAX = (MQ == 2) ? ((J0 == 0 && NSa[0] > NSa[1]) ? NSa[0] : NSa[1]) : NSa[0];
+    constexpr int NSMAX = NSa[MQ - 1];    // (the last block is the partial one, if any)
     // Round 5: the plain one-pass tile on 16-bit storage, tiles after the first: the exponentials in two halves - keys 0-31 of every block, then the first
     // half's MFMAs (O^T += V^T P^T over those keys) with the exponentials of keys 32-63 placed BETWEEN them - instead of all 32 v_exp_f32 + 16 conversions
     // in one lump in front of 20 back-to-back MFMAs (the compiler's schedule; profiles/r05_headline_tile_order.txt).
-#ifdef OEH_NO_PIPE_PV
-    constexpr bool PIPE_PV = false;
-#else
-    constexpr bool PIPE_PV = (MODE == 0) && !SRC32 && !FIRST && D <= 64 && OEH_KO == 0;   // (D = 128: 1.045 of the plain order - one wave per SIMD there, other limits)
-#endif
-    static_assert(NSP == 0x44 || PIPE_PV, "partial tiles: the placed order only");
-#if OEH_KO == 2
-    if constexpr (FIRST) {
-      if (!GATE && 1 < n_kt) wait_vm(std::integral_constant<int, 2>{});
-      else wait_vm(std::integral_constant<int, 0>{});
-      barrier_mem();
-      if (GATE && 1 < n_kt) issue_next();
-      if (2 < n_kt) issue_next();
-    }
-    return;
-#endif
+    constexpr bool PIPE_PV = (MODE == 0) && !SRC32 && !FIRST && D <= 64;   // (D = 128: 1.045 of the plain order - one wave per SIMD there, other limits)
+    static_assert(NSP == 0x44 || (PIPE_PV && MQ == 2 && J0 == 1 && NSa[0] == 4), "partial tiles: block 1 alone, the placed order only");
     // S^T = K Q^T; every K fragment is read once and used by all active blocks
     prio_hi();  // matrix-core phases at a higher issue priority than the other waves' softmax arithmetic (dense S=512: -2.7 %)
     f4 s[MQ][4];
-#ifdef OEH_PIPE_QK
-    // Round 6, measured and NOT landed (profiles/r06_headline_tile_asm.txt): the FIRST half of the steady-state tile as a placed order too - the scale /
-    // reference step of sub-tile s between the score MFMAs of sub-tile s + 1 (pinned by scheduling barriers; the compiler keeps its own hazard distances),
-    // and (OEH_PIPE_QK == 1) the next stage's LDS-DMA requests one piece behind each sub-tile's MFMAs instead of all four at the top of the tile.
-    constexpr bool PIPE_QK = PIPE_PV && NSP == 0x44 && !has_pad && D == 64;
-#else
-    constexpr bool PIPE_QK = false;
-#endif
-    if constexpr (PIPE_QK) {
-      auto score_sub = [&](const int sub) {
-        u4 kf[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) kf[ks] = *reinterpret_cast<const u4*>(kaddr[ks] + soff + sub * 16 * ROWB);
-#pragma unroll
-        for (int j = J0; j < MQ; ++j) {
-          f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-          for (int ks = 0; ks < KS; ++ks) acc = mfma16<IN>(kf[ks], qf[j][ks], acc);
-          s[j][sub] = acc;
-        }
-      };
-      auto scale_sub = [&](const int sub) {
-#pragma unroll
-        for (int j = J0; j < MQ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) s[j][sub][r] = __builtin_fmaf(s[j][sub][r], c1, mcneg[j]);
-#pragma unroll
-        for (int j = J0; j < MQ; ++j) asm volatile("" : "+v"(s[j][sub]));   // (pins the step HERE: the compiler otherwise sinks it to its first use behind the last MFMA)
-      };
-      auto piece = [&](const int p) {
-#if OEH_PIPE_QK == 1
-        if (in_tile_issue) issue_piece(p);
-#endif
-      };
-      score_sub(0);
-      __builtin_amdgcn_sched_barrier(0);
-      piece(0);
-      score_sub(1);
-      __builtin_amdgcn_sched_barrier(0);
-      scale_sub(0);
-      piece(1);
-      __builtin_amdgcn_sched_barrier(0);
-      score_sub(2);
-      __builtin_amdgcn_sched_barrier(0);
-      scale_sub(1);
-      piece(2);
-      __builtin_amdgcn_sched_barrier(0);
-      score_sub(3);
-      __builtin_amdgcn_sched_barrier(0);
-      scale_sub(2);
-      piece(3);
-#if OEH_PIPE_QK == 1
-      if (in_tile_issue) issue_advance();
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      prio_lo();
-      scale_sub(3);
-    }
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
-      if (PIPE_QK || sub >= NSMAX) continue;
+      if (sub >= NSMAX) continue;
       u4 kf[KS], kl[SRC32 ? KS : 1];
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -613,14 +492,8 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
         s[j][sub] = acc;
       }
     }
-    if constexpr (!PIPE_QK) prio_lo();
+    prio_lo();
     u4 pb[MQ][2];
-#if OEH_KO == 3
-#pragma unroll
-    for (int j = J0; j < MQ; ++j)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) pb[j][u] = u4{f32_bits(s[j][2 * u][0]), f32_bits(s[j][2 * u][1]), f32_bits(s[j][2 * u + 1][0]), f32_bits(s[j][2 * u + 1][1])};
-#else
     // exponent arguments t = (s - reference) * log2e  [key padding: BERT order scale*s + pad first]
     f4 padflag[(has_pad && MODE >= 3) ? 4 : 1];  // the grid chain with key padding (key_pad_boolean): +big for a visible key, the sentinel for a padded one
     if constexpr (has_pad) {
@@ -678,7 +551,7 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
       for (int sub = 0; sub < 4; ++sub)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (!PIPE_QK && sub < NSa[j]) s[j][sub][r] = __builtin_fmaf(s[j][sub][r], c1, mcneg[j]);
+          if (sub < NSa[j]) s[j][sub][r] = __builtin_fmaf(s[j][sub][r], c1, mcneg[j]);
     }
     // causal / tail mask, classified per 16x16 sub-tile with wave-uniform tests: untouched, all masked, or mixed
 #pragma unroll
@@ -770,21 +643,10 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
       // row maximum of the exponent arguments (fma / select results: no canonicalising v_max is needed in front)
       // (v_max3 written out: from fmaxf the compiler puts two canonicalising v_max x,x,x in front of every chain)
       float mt;
-#ifdef OEH_R5_MAXCHAIN
-      mt = max3_raw(s[j][0][0], s[j][0][1], s[j][0][2]);
-      mt = max3_raw(mt, s[j][0][3], s[j][1][0]);
-      mt = max3_raw(mt, s[j][1][1], s[j][1][2]);
-      mt = max3_raw(mt, s[j][1][3], s[j][2][0]);
-      mt = max3_raw(mt, s[j][2][1], s[j][2][2]);
-      mt = max3_raw(mt, s[j][2][3], s[j][3][0]);
-      mt = max3_raw(mt, s[j][3][1], s[j][3][2]);
-      mt = max3_raw(mt, s[j][3][3], s[j][3][3]);
-#else
       if (NSa[j] == 1) mt = max_first<1>(s[j]);        // (one statement each: oeh_common.h)
       else if (NSa[j] == 2) mt = max_first<2>(s[j]);
       else if (NSa[j] == 3) mt = max_first<3>(s[j]);
       else mt = max16_tree(s[j]);
-#endif
       // Move the reference: always on the first tile (to that tile's row maximum, unless every key of it is masked),
       // later only for rows whose maximum exceeds it by 2^8.  The common case is decided on the LANE maxima (no cross-lane
       // step); the row maximum is formed only when some row moves.  Decided per ROW, so that a row's result depends on
@@ -847,7 +709,6 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
         else pb[j][u] = u4{pack2_f16(a[0], a[1]), pack2_f16(a[2], a[3]), pack2_f16(bb[0], bb[1]), pack2_f16(bb[2], bb[3])};
       }
     }
-#endif  // OEH_KO == 3
     if constexpr (FIRST) {
       // V tile 0 landed for every wave (stage 1 may still be in flight); every wave has its Q operands, so the Q stage
       // can now be refilled with stage 2
@@ -892,12 +753,7 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
       // vector instruction in the two issue slots in front of it (the compiler keeps that distance for its own MFMAs: the s_nop it puts behind a v_mov of
       // the ones operand).  The ones operand is therefore materialised ahead (round 6: once, in front of the tile loop), the packed P
       // of a half is followed by the half's V^T reads, and the second half's conversions by an explicit s_nop.  (Found as NaN row sums at MQ == 1.)
-#ifdef OEH_R5_ONES_PER_TILE
-      u4 ones_v = ones;
-      asm volatile("" : "+v"(ones_v));
-#else
       const u4 ones_v = ones_live;
-#endif
       // keys 0-31 of every block: exponentials, packed
 #pragma unroll
       for (int j = J0; j < MQ; ++j) {
@@ -919,7 +775,7 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
       prio_hi();
       // first half's NB (DT + 1) MFMAs, the exponentials of keys 32-63 (8 per block with all four sub-tiles, 4 with three, none with fewer) between them
       // (about one per gap: a v_exp_f32 is the 8 issue cycles an MFMA of this shape leaves), the conversions behind
-      constexpr int E2_0 = (J0 == 0) ? 4 * (NSa[0] > 2 ? NSa[0] - 2 : 0) : 0;             // block 0's exponentials of the second half (not active: none)
+      constexpr int E2_0 = (J0 == 0) ? 8 : 0;             // block 0's exponentials of the second half (active: always a full tile; not active: none)
       constexpr int E2_1 = (MQ == 2) ? 4 * (NSa[1] > 2 ? NSa[1] - 2 : 0) : 0;
       {
         constexpr int NM = NB * (DT + 1), NE = E2_0 + E2_1;     // MFMAs of the half; exponentials to place (block-major: block 0's E2_0 first)
@@ -1018,12 +874,10 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
   using J0_1 = std::integral_constant<int, 1>;
   using NS_FULL = std::integral_constant<int, 0x44>;
   // bodies specialised for partly masked tiles exist where the placed order does (tile: PIPE_PV)
-#if defined(OEH_NO_PIPE_PV) || defined(OEH_NO_NSUB) || defined(OEH_R5_MAXCHAIN) || OEH_KO != 0
-  constexpr bool NSV = false;
-#else
   constexpr bool NSV = (TP == 0) && !SRC32 && D <= 64;
-#endif
-  int lh[MQ];   // last key any row of block j may see: a 16-key sub-tile that starts behind it is masked for the whole block
+  // last key any row of block j may see: a 16-key sub-tile that starts behind it is masked for the whole block.  Only block 1's is read; block 0's
+  // stays because dropping it reorders the compiled prologue.
+  int lh[MQ];
 #pragma unroll
   for (int j = 0; j < MQ; ++j) lh[j] = causal ? min(rb[j] + 15 + off, Sk - 1) : Sk - 1;
   if constexpr (SRC32) {
@@ -1066,45 +920,27 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
     // into the stage every wave finished reading one iteration ago.  (Requesting it later, behind the score MFMAs just
     // queued - a wave spends ~350 cycles per tile issuing its four 1-KiB pieces - measured no better: 21.9-22.4 vs 21.5-21.7 us
     // on dense S=512, equal on the causal shape.)
-#if defined(OEH_PIPE_QK) && OEH_PIPE_QK == 1
-    // the request rides inside the tile (one piece behind each sub-tile's score MFMAs) where the tile is a full placed one; elsewhere here, as before
-    const bool full_tile = (TP == 0) && !SRC32 && !PAD && D == 64 && i < nkb[MQ - 1] && !(MQ == 2 && i >= nkb[0] && NSV && ((lh[1] - 64 * i) >> 4) + 1 < 4);
-    const bool ride = (i + 2 < n_kt) && full_tile && (nx_tile * 64 + 64 <= Sk);
-    if (i + 2 < n_kt && !ride) issue_next();
-#else
-    constexpr bool ride = false;
     if (i + 2 < n_kt) issue_next();
-#endif
     if (i < 8) OEH_STAMP(5 + 3 * i);
     const int soff = slot_i * STAGEB;
     slot_i = (slot_i == R - 1) ? 0 : slot_i + 1;
     if (i >= nkb[MQ - 1]) continue;  // this wave's rows end before this tile (causal): nothing to compute
-    // Round 6: a tile in which only the first n < 4 sixteen-key sub-tiles hold a key the block may see (every block's causal diagonal tile, the ragged last
-    // tile) runs a body specialised for n: for the block that ends in this tile (block 0 beside a full block 1; or block 1 alone; or the only block)
+    // Round 6: on the MQ == 2 causal diagonal, block 1 runs alone (block 0's rows end before this tile); when only its first n < 4 sixteen-key
+    // sub-tiles hold a key it may see, it runs a body specialised for n (tile: NSa).  Every other tile runs the full body.
     if (MQ == 2 && i >= nkb[0]) {
       if constexpr (MQ == 2) {
-        const int n1 = NSV ? ((lh[1] - 64 * i) >> 4) + 1 : 4;
-        if constexpr (NSV && (OEH_NSUB_MASK & 1)) {
+        if constexpr (NSV) {
+          const int n1 = ((lh[1] - 64 * i) >> 4) + 1;
           if (n1 == 1) tile(J0_1{}, std::false_type{}, MODE_A{}, std::integral_constant<int, 0x14>{}, i, soff);
           else if (n1 == 2) tile(J0_1{}, std::false_type{}, MODE_A{}, std::integral_constant<int, 0x24>{}, i, soff);
           else if (n1 == 3) tile(J0_1{}, std::false_type{}, MODE_A{}, std::integral_constant<int, 0x34>{}, i, soff);
-          else tile(J0_1{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff, ride);
+          else tile(J0_1{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff);
         } else {
-          tile(J0_1{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff, ride);
+          tile(J0_1{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff);
         }
       }
     } else {
-      if constexpr (NSV && (OEH_NSUB_MASK & 28) != 0) {
-        const int n0 = ((lh[0] - 64 * i) >> 4) + 1;
-        const int nl = ((lh[MQ - 1] - 64 * i) >> 4) + 1;   // the last block: full, or (MQ == 1) the block itself
-        if (MQ == 2 && nl < 4) tile(J0_0{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff);   // (both blocks partial - Sq != Sk layouts: the general body)
-        else if (n0 == 1 && (OEH_NSUB_MASK & 4)) tile(J0_0{}, std::false_type{}, MODE_A{}, std::integral_constant<int, 0x41>{}, i, soff);
-        else if (n0 <= 2 && (OEH_NSUB_MASK & 8)) tile(J0_0{}, std::false_type{}, MODE_A{}, std::integral_constant<int, 0x42>{}, i, soff);
-        else if (n0 == 3 && (OEH_NSUB_MASK & 16)) tile(J0_0{}, std::false_type{}, MODE_A{}, std::integral_constant<int, 0x43>{}, i, soff);
-        else tile(J0_0{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff, ride);
-      } else {
-        tile(J0_0{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff, ride);
-      }
+      tile(J0_0{}, std::false_type{}, MODE_A{}, NS_FULL{}, i, soff);
     }
     if (i < 8) OEH_STAMP(6 + 3 * i);
   }
@@ -1138,18 +974,13 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
   }
   }
   OEH_STAMP(2);
-#ifndef OEH_NO_PIPE_PV
   if constexpr (!SRC32 && TP == 0) asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // (the in-place MFMAs of the last tile, written as inline asm, against the epilogue's vector reads of their results)
-#endif
 
   // ---- epilogue: denominators and gate, O^T staged through a free LDS stage so that global stores are whole rows
   // (per-lane stores of the MFMA layout would touch 16 rows x 32 B per instruction).  Stage n_kt % R is free: its
   // last reader was tile n_kt - 3 and no DMA is in flight.  Each wave owns 16*MQ rows of it: no workgroup barrier.
   // (lane-derived addresses come from an opaque copy of the lane id: formed here, not kept live across the loop where
   // the MQ=2 variant has no register to spare)
-#if OEH_KO >= 2 && OEH_KO <= 4
-  if (!(o[0][0][0] == 1.2345e-31f && lacc[0][1] == 5.4321e-30f)) return;  // (never true: the accumulators stay live, the epilogue does not run)
-#endif
   constexpr int XM = (CPR < 8 ? CPR : 8) - 1;
   unsigned char* ebase = lds + (n_kt % R) * STAGEB + wave * (16 * MQ * ROWB);
   int lane_e = lane;

@@ -202,27 +202,12 @@ __device__ __forceinline__ u4 load8_as16(const void* base, long elem_off) {
 // far inside).  Kernels that split call fp16_overflow_clamp() first: with MODE.FP16_OVFL set the conversions SATURATE at the
 // fp16 range instead of producing inf, so that a stray larger value costs accuracy (the excess is dropped) and never turns a
 // whole row into NaN - at no instruction cost (two v_med3 per element in the load path measured +15 % on the fp32 kernels).
-// OEH_PAIR_RAW (round 5 experiment -> see profiles/r05_pair_raw_ab.txt): the attention kernels' operand pairs with the UNSCALED residual (split8_raw below) -
-// the factor that brings the lo products back is then 1.
-#ifdef OEH_PAIR_RAW
-constexpr float kSplitUp = 1.0f, kSplitDown = 1.0f;
-#else
-constexpr float kSplitUp = 2048.0f, kSplitDown = 1.0f / 2048.0f;
-#endif
+constexpr float kSplitDown = 1.0f / 2048.0f;  // brings the lo products back
 __device__ __forceinline__ void fp16_overflow_clamp() {
   __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);  // hwreg(HW_REG_MODE, 23, 1): FP16_OVFL
 }
 __device__ __forceinline__ h2 sat_h2(float x, float y) { return __builtin_convertvector((f2{x, y}), h2); }
-__device__ __forceinline__ void split8_ref(const f4 a, const f4 b, u4& hi, u4& lo) {
-  const h2 h0 = sat_h2(a[0], a[1]), h1 = sat_h2(a[2], a[3]);
-  const h2 h2_ = sat_h2(b[0], b[1]), h3 = sat_h2(b[2], b[3]);
-  hi = u4{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1), __builtin_bit_cast(unsigned, h2_), __builtin_bit_cast(unsigned, h3)};
-  auto lo2 = [](float x0, _Float16 hh0, float x1, _Float16 hh1) {
-    return __builtin_bit_cast(unsigned, sat_h2((x0 - (float)hh0) * kSplitUp, (x1 - (float)hh1) * kSplitUp));
-  };
-  lo = u4{lo2(a[0], h0[0], a[1], h0[1]), lo2(a[2], h1[0], a[3], h1[1]), lo2(b[0], h2_[0], b[1], h2_[1]), lo2(b[2], h3[0], b[3], h3[1])};
-}
-// split8 in 20 vector instructions instead of ~37 (round 5): hi by four v_cvt_pk_f16_f32 as above; the residual x - hi by v_fma_mix_f32 reading the
+// split8 in 20 vector instructions instead of ~37 (round 5): hi by four v_cvt_pk_f16_f32 (sat_h2); the residual x - hi by v_fma_mix_f32 reading the
 // fp16 half straight out of the packed register (fma(hi, -1, x): exact, no separate conversion), and lo = RN16(residual * 2^11) by
 // v_fma_mixlo_f16 / v_fma_mixhi_f16 (the product is exact, ONE rounding, written into its half of the packed register: no multiply, no pack).
 // Bit-identical to split8 for |x| inside the fp16 range (tests/test_proj_gpu.py compares the two paths bit for bit).  One asm statement per
@@ -305,21 +290,9 @@ __device__ __forceinline__ void split8_raw_scaled(const f4 a, const f4 b, const 
   lo = u4{l0, l1, l2, l3};
 }
 // the documented [hi | lo 2^11] pair (oeh_split_pairs' output format, the projection GEMM's `pairs` = 1 input)
-__device__ __forceinline__ void split8_scaled(const f4 a, const f4 b, u4& hi, u4& lo) {
-#ifdef OEH_SPLIT_REF   // (the round-4 form, for A/B builds: make alt NAME=ref DEFS=-DOEH_SPLIT_REF)
-  split8_ref(a, b, hi, lo);
-#else
-  split8_mix(a, b, 2048.0f, hi, lo);
-#endif
-}
+__device__ __forceinline__ void split8_scaled(const f4 a, const f4 b, u4& hi, u4& lo) { split8_mix(a, b, 2048.0f, hi, lo); }
 // the kernels' own operand pairs (never leave a kernel)
-__device__ __forceinline__ void split8(const f4 a, const f4 b, u4& hi, u4& lo) {
-#ifdef OEH_PAIR_RAW
-  split8_raw(a, b, hi, lo);
-#else
-  split8_scaled(a, b, hi, lo);
-#endif
-}
+__device__ __forceinline__ void split8(const f4 a, const f4 b, u4& hi, u4& lo) { split8_scaled(a, b, hi, lo); }
 // 8 consecutive fp32 storage elements -> the (hi, lo) operand pair
 __device__ __forceinline__ void load8_split(const void* base, long elem_off, u4& hi, u4& lo) {
   const f4* p = reinterpret_cast<const f4*>(reinterpret_cast<const float*>(base) + elem_off);

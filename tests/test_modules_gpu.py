@@ -225,8 +225,8 @@ def test_modules_at_twelve_heads_against_the_reference(oa):
 # eval on the reference's grids: 2.0e-3 of 41 440 sampled outputs one output-grid step off (never more) - every output sums 768 context indices
 # x weights, and the share of context indices that differ from the reference's by one step is 1.5e-5 (test_attn_gpu.py: cfg4 full size)
 def test_vit_small_size_against_the_reference(oa):
-    """ViT-S/16's attention at its own size (C = 384, 6 heads of 64, N = 197 tokens: three full key tiles + a ragged one of 5 keys - the tile the
-    one-pass kernel now specialises) against module outputs captured from the reference (vit_attn_s16.npz); fp32 and fp16 modules."""
+    """ViT-S/16's attention at its own size (C = 384, 6 heads of 64, N = 197 tokens: three full key tiles + a ragged one of 5 keys, which the
+    one-pass kernel runs through its full tile body) against module outputs captured from the reference (vit_attn_s16.npz); fp32 and fp16 modules."""
     from tests.golden import synth as sy
 
     g = load_golden("vit_attn_s16.npz")

@@ -24,12 +24,23 @@ __global__ void k_split_scaled(const float* x, unsigned* out, float k, int clamp
   }
 }
 
+// the [hi | lo 2^11] pair by its definition, in plain conversions (the round-4 form of split8)
+__device__ void split8_def(const f4 a, const f4 b, u4& hi, u4& lo) {
+  const h2 h0 = sat_h2(a[0], a[1]), h1 = sat_h2(a[2], a[3]);
+  const h2 h2_ = sat_h2(b[0], b[1]), h3 = sat_h2(b[2], b[3]);
+  hi = u4{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1), __builtin_bit_cast(unsigned, h2_), __builtin_bit_cast(unsigned, h3)};
+  auto lo2 = [](float x0, _Float16 hh0, float x1, _Float16 hh1) {
+    return __builtin_bit_cast(unsigned, sat_h2((x0 - (float)hh0) * 2048.0f, (x1 - (float)hh1) * 2048.0f));
+  };
+  lo = u4{lo2(a[0], h0[0], a[1], h0[1]), lo2(a[2], h1[0], a[3], h1[1]), lo2(b[0], h2_[0], b[1], h2_[1]), lo2(b[2], h3[0], b[3], h3[1])};
+}
+
 __global__ void k_split(const float* x, unsigned* out, float k2048, int clampmode) {
   if (clampmode) fp16_overflow_clamp();
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   f4 a = *reinterpret_cast<const f4*>(x + t * 8), b = *reinterpret_cast<const f4*>(x + t * 8 + 4);
   u4 hi, lo, hi2, lo2;
-  split8_ref(a, b, hi, lo);
+  split8_def(a, b, hi, lo);
   split8_mix(a, b, k2048, hi2, lo2);
   for (int i = 0; i < 4; ++i) {
     out[t * 16 + i] = hi[i]; out[t * 16 + 4 + i] = lo[i]; out[t * 16 + 8 + i] = hi2[i]; out[t * 16 + 12 + i] = lo2[i];

@@ -368,6 +368,26 @@ int oeh_attn_bwd_dropout(const oeh_attn_desc* desc, const oeh_dropout* drop, con
                          const int64_t dk_stride[3], void* dv, const int64_t dv_stride[3], void* work, void* stream);
 int oeh_attn_dropout_mask(const oeh_attn_desc* desc, const oeh_dropout* drop, uint8_t* keep, void* stream);
 
+/* Options of the forward beyond oeh_attn_desc (ABI 6 and the descriptor stay as they are).
+ * pv_pairs != 0: fp32 storage (dtype OEH_F32) computes the CONTEXT to fp32 accuracy as well as the scores.  The one-pass and full-row
+ *   kernels split each fp32 probability tile in registers into fp16 operands p = P_hi + P_lo 2^-11 and accumulate
+ *   V P = V_hi P_hi + 2^-11 (V_lo P_hi + V_hi P_lo) - without it P enters the second product as ONE fp16 operand (~1e-4 relative on the
+ *   context).  The one-pass kernel's row sums include P_lo, so the denominator is the sum of what the numerator multiplied.  The
+ *   small-shape kernel (fp32 matrix-core operands) and the any-shape kernel (fp32 FMA) are fp32-exact already and run unchanged; a problem
+ *   that would reach the general kernel (fp16 probability operand) runs on the any-shape kernel instead.  Not with fake-quant (`fq`
+ *   enabled: the probability operand is a grid value), the in-kernel gate predictor (gate_hidden; `gate` is fine) or 16-bit storage
+ *   (including o_dtype OEH_F32): OEH_ENOTSUP.
+ * reserved: must be 0 (else OEH_EINVAL, before any other check or device work).
+ * oeh_attn_fwd_ex / oeh_attn_variant_ex with opts == NULL or pv_pairs == 0: exactly oeh_attn_fwd / oeh_attn_variant.  The variant name
+ * of a form with probability pairs ends in "+pv2" ("flash16/MQ2/D64/f32+pv2"). */
+typedef struct oeh_attn_opts {
+  int32_t pv_pairs;
+  int32_t reserved[3];
+} oeh_attn_opts;
+int oeh_attn_fwd_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const void* q, const void* k, const void* v, void* o,
+                    const oeh_fq_desc* fq, void* stream);
+const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const oeh_fq_desc* fq);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

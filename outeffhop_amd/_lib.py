@@ -64,6 +64,11 @@ class oeh_dropout(C.Structure):
     _fields_ = [("p", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class oeh_attn_opts(C.Structure):
+    """include/oeh.h: options of oeh_attn_fwd_ex (pv_pairs: the probability operand as an fp16 pair on fp32 storage)."""
+    _fields_ = [("pv_pairs", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class oeh_proj_seg(C.Structure):
     """include/oeh.h: one column segment (a projection) of oeh_proj_quant_i8."""
     _fields_ = [("alpha", C.c_float), ("scale", C.c_float), ("zero_point", C.c_float), ("out", C.c_void_p), ("y", C.c_void_p),
@@ -76,6 +81,7 @@ EXPORTS = (
     "oeh_attn_fwd_train", "oeh_attn_bwd_work_bytes", "oeh_attn_bwd",
     "oeh_attn_fwd_train_dropout", "oeh_attn_bwd_dropout", "oeh_attn_dropout_mask",
     "oeh_abi_version", "oeh_build_info", "oeh_strerror", "oeh_attn_variant",
+    "oeh_attn_fwd_ex", "oeh_attn_variant_ex",
 )
 
 _lib = None
@@ -143,6 +149,10 @@ def load() -> C.CDLL:
     lib.oeh_strerror.restype = C.c_char_p
     lib.oeh_attn_variant.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_fq_desc)]
     lib.oeh_attn_variant.restype = C.c_char_p
+    lib.oeh_attn_fwd_ex.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_attn_opts), vp, vp, vp, vp, C.POINTER(oeh_fq_desc), vp]
+    lib.oeh_attn_fwd_ex.restype = C.c_int
+    lib.oeh_attn_variant_ex.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_attn_opts), C.POINTER(oeh_fq_desc)]
+    lib.oeh_attn_variant_ex.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -374,6 +374,25 @@ def pad_is_boolean(mask: torch.Tensor) -> bool:
     return res
 
 
+# ---- fp32-accurate context for fp32 models (opt-in): with COMPENSATED_PV on, every fused inference call on fp32 storage without fake-quant
+# passes pv_pairs=True (include/oeh.h: oeh_attn_opts) - the probabilities enter the product with V as fp16 pairs, so the context is as accurate
+# as the scores (the reference's validate runs measure outliers on fp32 models).  The in-kernel gate predictor is not available then (the gate
+# runs as oeh_gate_fwd + gate values).  Off by default: it changes the fp32 outputs (in the last bits) and costs time.  The observable
+# (torch-op) path and the training path do not change.
+COMPENSATED_PV = False
+
+
+def set_compensated_pv(on: bool = True) -> None:
+    """Compute the fused fp32 attention's context from probability pairs (True) or with the fp16 probability operand (False, the default)."""
+    global COMPENSATED_PV
+    COMPENSATED_PV = bool(on)
+
+
+def pv_pairs_for(q: torch.Tensor, fq=None) -> bool:
+    """What attention calls on q pass as ops.attn_fwd(..., pv_pairs=): COMPENSATED_PV on fp32 storage without fake-quant."""
+    return COMPENSATED_PV and q.dtype == torch.float32 and fq is None
+
+
 def attention_core(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax_fn, scale: float = 1.0, scale_div: float = 0.0,
     attention_mask: Optional[torch.Tensor] = None, clamp_min: bool = False, detect_causal: bool = False,
@@ -398,14 +417,15 @@ def attention_core(
     # the fused INT8 chain stays on the quantiser grid with padded keys when the mask is a mask (0 / finfo.min entries - what
     # classify_causal has verified for a decoder mask; else one look per mask tensor object): include/oeh.h key_pad_boolean
     pad_bool = pad is not None and fq is not None and (causal or pad_is_boolean(attention_mask))
+    pv = pv_pairs_for(q, fq)
     kw = dict(softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full, key_pad_boolean=pad_bool, causal=causal,
-              clamp_min=clamp_min, mask_min=mask_min, fq=fq)
+              clamp_min=clamp_min, mask_min=mask_min, fq=fq, pv_pairs=pv)
     out = None
     if gate_mlp is not None:
         units = 0 if gate_mlp.w1.dim() == 2 else gate_mlp.w1.shape[1]
         if full is None and ops.fused_gate_ok(B, H, Sq, Sk, D, q.dtype, clip=bool(spec.clip), fq=fq is not None, units=units,
                                               base=spec.base, gamma=spec.gamma, key_pad=pad is not None, causal=causal,
-                                              scale=scale, scale_div=scale_div, mask_min=mask_min):
+                                              scale=scale, scale_div=scale_div, mask_min=mask_min, pv_pairs=pv):
             try:
                 out = ops.attn_fwd(q, k, v, gate_mlp=gate_mlp, **kw)
             except _lib.OehError as e:  # an option combination the 16-bit MFMA kernels do not take after all (alignment ...)

@@ -273,7 +273,10 @@ int g_place = 0;                         // tools/microbench.py only: 1 = plain 
 
 // query blocks (16 rows) per wave of the one-pass kernel: 2 (128-row workgroups) once that still gives every CU two
 // workgroups, else 1
-int flash_mq(const oeh_attn_desc* d) {
+int flash_mq(const oeh_attn_desc* d, bool pv2 = false) {
+  // the probability pairs with key padding / a (B,1,Sq,Sk) mask at head dim 64: one block per wave (two spill - the fp32 forms with padding are
+  // at the register file's edge already; oeh_attn_flash.inl instantiates only this one)
+  if (pv2 && d->D == 64 && (d->key_pad_mask != nullptr || d->full_mask != nullptr)) return 1;
   if (g_flash_mq != 0 && !(d->D == 128 && d->dtype == OEH_F32)) return g_flash_mq;
   if (d->D == 128 && d->dtype == OEH_F32) return 1;  // two blocks of fp32 operand pairs at d = 128 do not fit the register file (130 spills)
   const long wg2 = (long)((d->Sq + 127) / 128) * d->B * d->H;
@@ -386,7 +389,7 @@ void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const voi
                std::isfinite(d->mask_min) && d->mask_min < -1e4f) ? 1 : 0;
 }
 
-const char* variant_name(Variant v, const oeh_attn_desc* d, bool fq) {
+const char* variant_name(Variant v, const oeh_attn_desc* d, bool fq, bool pv2 = false) {
   static thread_local char buf[64];
   if (v == V_GENERIC) return "generic";
   if (v == V_I8) {
@@ -402,21 +405,36 @@ const char* variant_name(Variant v, const oeh_attn_desc* d, bool fq) {
   const int nt = d->Sk <= 128 ? 8 : (d->Sk <= 256 ? 16 : 32);
   const char* dt = d->dtype == OEH_F16 ? "f16" : (d->dtype == OEH_BF16 ? "bf16" : "f32");
   if (v == V_FLASH && wide_eligible(d, nullptr) && !fq) std::snprintf(buf, sizeof(buf), "flash16w/D%d/%s", d->D, dt);
-  else if (v == V_FLASH) std::snprintf(buf, sizeof(buf), "flash16/MQ%d/D%d/%s%s", flash_mq(d), d->D, dt, fq ? "/fq2p" : (d->clip ? "/clip2p" : ""));
-  else if (v == V_FAST) std::snprintf(buf, sizeof(buf), "fast16/NT%d/D%d/%s%s%s", nt, d->D, dt, d->clip ? "/clip" : "", fq ? "/fq" : "");
+  else if (v == V_FLASH) std::snprintf(buf, sizeof(buf), "flash16/MQ%d/D%d/%s%s%s", flash_mq(d, pv2), d->D, dt, fq ? "/fq2p" : (d->clip ? "/clip2p" : ""), pv2 ? "+pv2" : "");
+  else if (v == V_FAST) std::snprintf(buf, sizeof(buf), "fast16/NT%d/D%d/%s%s%s%s", nt, d->D, dt, d->clip ? "/clip" : "", fq ? "/fq" : "", pv2 ? "+pv2" : "");
   else std::snprintf(buf, sizeof(buf), "mfma16/NT%d/D%d/%s%s", nt, d->D, dt, fq ? "/fq" : "");
   return buf;
 }
 
-}  // namespace
+// oeh_attn_opts (include/oeh.h): OEH_EINVAL for reserved words, OEH_ENOTSUP for what the probability pairs do not cover; pv2 = the pairs are on
+int attn_opts(const oeh_attn_desc* d, const oeh_attn_opts* opts, const oeh_fq_desc* fq, bool& pv2) {
+  pv2 = false;
+  if (opts == nullptr) return OEH_OK;
+  if (opts->reserved[0] != 0 || opts->reserved[1] != 0 || opts->reserved[2] != 0) return OEH_EINVAL;
+  if (opts->pv_pairs == 0) return OEH_OK;
+  if (d == nullptr) return OEH_EINVAL;
+  if (d->dtype != OEH_F32 || any_fq(fq) || (d->gate == nullptr && d->gate_hidden != nullptr)) return OEH_ENOTSUP;
+  pv2 = true;
+  return OEH_OK;
+}
 
-extern "C" {
+// With the probability pairs, a problem the general kernel would take (its fp32 form rounds P to one fp16 operand) goes to the any-shape
+// kernel (fp32 FMA); the one-pass and full-row kernels run their PV2 forms, the small-shape kernel is fp32-exact as it is.
+Variant pick_variant_pv(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq, bool pv2) {
+  const Variant var = pick_variant(d, q, k, v, o, fq);
+  if (!pv2 || var != V_MFMA) return var;
+  return (size_t)(d->D + d->Sk) * 4 <= 64 * 1024 ? V_GENERIC : V_NONE;
+}
 
-int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq,
-                 void* stream) {
+int attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq, void* stream, bool pv2) {
   int rc = validate(desc, q, k, v, o, fq);
   if (rc != OEH_OK) return rc;
-  const Variant var = pick_variant(desc, q, k, v, o, fq);
+  const Variant var = pick_variant_pv(desc, q, k, v, o, fq, pv2);
   if (var == V_NONE) return OEH_ENOTSUP;
   if (desc->gate == nullptr && desc->gate_hidden != nullptr) {  // fused gate predictor: 16-bit MFMA variants, 16-B aligned rows
     // up to four 16-unit MFMA tiles of hidden units; fp32 storage: the full-row kernel's operand-pair form only
@@ -427,7 +445,7 @@ int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const 
   }
   AttnParams P;
   fill_params(P, desc, q, k, v, o, fq);
-  P.src32 = (desc->dtype == OEH_F32 && (var == V_FLASH || var == V_FAST)) ? 1 : 0;  // fp32 storage read directly, fp32 output
+  P.src32 = (desc->dtype == OEH_F32 && (var == V_FLASH || var == V_FAST)) ? (pv2 ? 2 : 1) : 0;  // fp32 storage read directly, fp32 output
   if (want_out32(desc)) {
     // the accumulators themselves - sibling instantiations (O32) of what the 16-bit workloads of BASELINE.json run.  Head dim 64: the one-pass
     // kernel's plain form with masks none / causal / key padding / a (B,1,Sq,Sk) mask, or with the in-kernel gate predictor (not both);
@@ -468,7 +486,7 @@ int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const 
       return oeh::launch_attn_wide(P, desc->dtype, st);
     }
 #endif
-    const int mq = flash_mq(desc);
+    const int mq = flash_mq(desc, pv2);
     P.nQT = (desc->Sq + 64 * mq - 1) / (64 * mq);
     switch (desc->D) {
       case 32: return oeh::launch_attn_flash_d32(P, desc->dtype, mq, st);
@@ -494,10 +512,38 @@ int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const 
   return oeh::launch_attn_generic(P, desc->dtype, st);
 }
 
+}  // namespace
+
+extern "C" {
+
+int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq,
+                 void* stream) {
+  return attn_fwd(desc, q, k, v, o, fq, stream, false);
+}
+
+int oeh_attn_fwd_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const void* q, const void* k, const void* v, void* o,
+                    const oeh_fq_desc* fq, void* stream) {
+  bool pv2 = false;
+  if (opts != nullptr && (opts->reserved[0] != 0 || opts->reserved[1] != 0 || opts->reserved[2] != 0)) return OEH_EINVAL;  // (before any other check)
+  const int rc = validate(desc, q, k, v, o, fq);
+  if (rc != OEH_OK) return rc;
+  const int orc = attn_opts(desc, opts, fq, pv2);
+  if (orc != OEH_OK) return orc;
+  return attn_fwd(desc, q, k, v, o, fq, stream, pv2);
+}
+
 const char* oeh_attn_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq) {
   if (desc == nullptr || desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0 || desc->D <= 0 || (!dtype_ok(desc->dtype) && desc->dtype != OEH_I8))
     return nullptr;
   return variant_name(pick_variant(desc, nullptr, nullptr, nullptr, nullptr, fq), desc, any_fq(fq));
+}
+
+const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const oeh_fq_desc* fq) {
+  bool pv2 = false;
+  if (attn_opts(desc, opts, fq, pv2) != OEH_OK) return nullptr;
+  if (!pv2) return oeh_attn_variant(desc, fq);
+  if (desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0 || desc->D <= 0) return nullptr;
+  return variant_name(pick_variant_pv(desc, nullptr, nullptr, nullptr, nullptr, fq, true), desc, false, true);
 }
 
 int oeh_softmax_rows(const void* x, void* y, int64_t rows, int32_t cols, int32_t dtype, int32_t softmax_base, int32_t clip,

@@ -68,9 +68,13 @@ constexpr int fast_occupancy() {  // what the LDS rings allow (6 tiles of 64 x 2
 // precedes its next commit); Q goes global -> registers directly.
 // O32: 16-bit storage with the output taken from the fp32 accumulators (include/oeh.h: o_dtype = OEH_F32) - the same loops, only the
 // epilogue's store differs (a runtime switch in the epilogue measured +2 ... +8 % on the production launches, round 4).
-template <int NT, int D, int IN, bool CLIP, bool GATE, int FQ = 0, bool SRC32 = false, bool O32 = false>
+// PV2 (fp32 storage, plain and clipped forms; include/oeh.h: oeh_attn_opts.pv_pairs): the probability operand as the pair p = P_hi + P_lo 2^-11
+// (oeh_common.h: split4_mix; P_lo takes the two score registers the packed P_hi leaves free) and the context as o += V_hi P_hi,
+// ox += V_lo P_hi + V_hi P_lo - one more MFMA per V fragment.  The denominator is the fp32 sum of the exponentials either way.
+template <int NT, int D, int IN, bool CLIP, bool GATE, int FQ = 0, bool SRC32 = false, bool O32 = false, bool PV2 = false>
 __global__ __launch_bounds__(256, (fast_occupancy<NT, D, SRC32, GATE>())) void oeh_attn_fast_kernel(const AttnParams P) {
   static_assert(!SRC32 || IN == IN_F16, "fp32 storage: fp16 operand pairs, fp32 output");
+  static_assert(!PV2 || (SRC32 && FQ == 0 && !GATE), "probability pairs: fp32 storage, the plain and clipped forms");
   static_assert(!O32 || (!SRC32 && FQ == 0 && !(GATE && CLIP)), "fp32 output of 16-bit storage: the plain and clipped forms, the plain form + in-kernel gate");
   constexpr bool OUT32 = SRC32 || O32;
   static_assert(!FQ || !GATE, "the fake-quant variant has no in-kernel gate predictor");
@@ -718,7 +722,11 @@ __global__ __launch_bounds__(256, (fast_occupancy<NT, D, SRC32, GATE>())) void o
       for (int sub = 0; sub < 4; ++sub) {
         const int t = kt * 4 + sub;
         sum += (s[t][0] + s[t][1]) + (s[t][2] + s[t][3]);
-        if constexpr (!CLIP) {
+        if constexpr (!CLIP && PV2) {
+          unsigned h0, h1, l0, l1;
+          split4_mix(s[t], 2048.0f, h0, h1, l0, l1);
+          s[t] = f4{bits_f32(h0), bits_f32(h1), bits_f32(l0), bits_f32(l1)};
+        } else if constexpr (!CLIP) {
           const unsigned lo = (IN == IN_BF16) ? pack2_bf16(s[t][0], s[t][1]) : pack2_f16(s[t][0], s[t][1]);
           const unsigned hi = (IN == IN_BF16) ? pack2_bf16(s[t][2], s[t][3]) : pack2_f16(s[t][2], s[t][3]);
           s[t][0] = bits_f32(lo);
@@ -746,6 +754,12 @@ __global__ __launch_bounds__(256, (fast_occupancy<NT, D, SRC32, GATE>())) void o
           float pv[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) pv[r] = __builtin_amdgcn_fmed3f(__builtin_fmaf(s[t][r], clip_iw, clip_g), 0.0f, 1.0f);
+          if constexpr (PV2) {
+            unsigned h0, h1, l0, l1;
+            split4_mix(f4{pv[0], pv[1], pv[2], pv[3]}, 2048.0f, h0, h1, l0, l1);
+            s[t] = f4{bits_f32(h0), bits_f32(h1), bits_f32(l0), bits_f32(l1)};
+            continue;
+          }
           const unsigned lo = (IN == IN_BF16) ? pack2_bf16(pv[0], pv[1]) : pack2_f16(pv[0], pv[1]);
           const unsigned hi = (IN == IN_BF16) ? pack2_bf16(pv[2], pv[3]) : pack2_f16(pv[2], pv[3]);
           s[t][0] = bits_f32(lo);
@@ -800,6 +814,10 @@ __global__ __launch_bounds__(256, (fast_occupancy<NT, D, SRC32, GATE>())) void o
             const s4 hil = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0 + TILEB + 16 * ROWB));
             const u2 l3 = __builtin_bit_cast(u2, lol), h3 = __builtin_bit_cast(u2, hil);
             ox[dt] = mfma16<IN>(u4{l3.x, l3.y, h3.x, h3.y}, pb, ox[dt]);
+          }
+          if constexpr (PV2) {  // + V_hi P_lo
+            const u4 pl = u4{f32_bits(s[t0][2]), f32_bits(s[t0][3]), f32_bits(s[t0 + 1][2]), f32_bits(s[t0 + 1][3])};
+            ox[dt] = mfma16<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pl, ox[dt]);
           }
         }
       }
@@ -892,6 +910,11 @@ static void launch_fast_nt_d_in(const AttnParams& P, unsigned grid, hipStream_t 
   const bool grid_pad = grid_chain && P.pad != nullptr;
   if (P.src32) {  // fp32 storage read directly, fp32 output
     if constexpr (IN == IN_F16) {
+      if (P.src32 == 2) {  // PV2: the probability pairs (oeh_api.hip refuses fake-quant and the in-kernel gate predictor with them)
+        if (P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 0, true, false, true>), dim3(grid), dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 0, true, false, true>), dim3(grid), dim3(256), 0, st, P);
+        return;
+      }
       if (grid_pad && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 3, true>), dim3(grid), dim3(256), 0, st, P);
       else if (grid_pad) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 3, true>), dim3(grid), dim3(256), 0, st, P);
       else if (grid_chain && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 1, true>), dim3(grid), dim3(256), 0, st, P);

@@ -62,9 +62,16 @@ constexpr int flash_occupancy() { return D >= 128 ? 1 : (SRC32 ? 2 : 3); }  // f
 // integer-valued probability to the second product; context quantiser and gate in the epilogue.  Rows of any length.
 // O32: 16-bit storage with the output taken from the fp32 accumulators (include/oeh.h: o_dtype = OEH_F32) - the same loop, only the
 // epilogue's store differs (as a runtime switch in the epilogue it cost the production launches +0.7 ... +3 %, round 4).
-template <int D, int IN, int MQ, bool PAD, bool GATE, bool SRC32 = false, int TP = 0, bool O32 = false>
+// PV2 (fp32 storage, plain and clipped forms; include/oeh.h: oeh_attn_opts.pv_pairs): the context to fp32 accuracy as well.  Each fp32
+// probability tile is split in registers like the operands, p = P_hi + P_lo 2^-11 (oeh_common.h: split8), and the second product becomes
+// o += V_hi P_hi, ox += V_lo P_hi + V_hi P_lo (ox is scaled by 2^-11 in the epilogue; V_lo P_lo, 2^-22 relative, is dropped): one more MFMA
+// per V fragment.  The one-pass form's row sums stay the sums of exactly what the numerator multiplies: a second ones-MFMA, on P_lo with
+// a ones operand of 2^-11, adds the lo part into the same accumulator.  The clipped form's denominator is the fp32 sum of the
+// exponentials (statistics pass) and does not change.
+template <int D, int IN, int MQ, bool PAD, bool GATE, bool SRC32 = false, int TP = 0, bool O32 = false, bool PV2 = false>
 __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_attn_flash_kernel(const AttnParams P) {
   static_assert(IN == IN_F16 || IN == IN_BF16, "16-bit matrix-core operands");
+  static_assert(!PV2 || (SRC32 && TP <= 1), "probability pairs: fp32 storage, the plain and clipped forms");
   static_assert(!O32 || (!SRC32 && TP == 0 && !(GATE && PAD)), "fp32 output of 16-bit storage: the plain one-pass form [+ key padding | + in-kernel gate]");
   constexpr bool CLIP = (TP == 1), FQ2 = (TP == 2);
   static_assert(TP == 0 || !GATE, "two-pass forms: no in-kernel gate predictor");
@@ -411,6 +418,7 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
   const float c1 = has_pad ? kLog2e : sc * kLog2e;   // pad mode keeps scaled+masked scores, otherwise raw dot products
   const u4 ones = (IN == IN_BF16) ? u4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u}
                                   : u4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u};
+  const u4 ones_lo = u4{0x10001000u, 0x10001000u, 0x10001000u, 0x10001000u};  // PV2: fp16 2^-11, the row sums' share of P_lo
   // Per-row state: mcneg = -(reference score) * c1 in exponent (log2) units, so that t = fma(s, c1, mcneg) is the
   // exponent argument; O and l are sums of exp2(t).  The reference is the first tile's row maximum and afterwards
   // moves only when a tile maximum exceeds it by 2^8.  softmax_1's "+1" is exp2(mcneg) (= exp(-reference)).
@@ -494,6 +502,7 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
     }
     prio_lo();
     u4 pb[MQ][2];
+    u4 pl[PV2 ? MQ : 1][2];                      // PV2: P_lo = RN16((p - P_hi) 2^11), P_hi = pb
     // exponent arguments t = (s - reference) * log2e  [key padding: BERT order scale*s + pad first]
     f4 padflag[(has_pad && MODE >= 3) ? 4 : 1];  // the grid chain with key padding (key_pad_boolean): +big for a visible key, the sentinel for a padded one
     if constexpr (has_pad) {
@@ -635,7 +644,8 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const f4 a = s[j][2 * u], bb = s[j][2 * u + 1];
-          if constexpr (IN == IN_BF16) pb[j][u] = u4{pack2_bf16(a[0], a[1]), pack2_bf16(a[2], a[3]), pack2_bf16(bb[0], bb[1]), pack2_bf16(bb[2], bb[3])};
+          if constexpr (PV2) split8(a, bb, pb[j][u], pl[j][u]);  // (P_hi bit for bit the pack below)
+          else if constexpr (IN == IN_BF16) pb[j][u] = u4{pack2_bf16(a[0], a[1]), pack2_bf16(a[2], a[3]), pack2_bf16(bb[0], bb[1]), pack2_bf16(bb[2], bb[3])};
           else pb[j][u] = u4{pack2_f16(a[0], a[1]), pack2_f16(a[2], a[3]), pack2_f16(bb[0], bb[1]), pack2_f16(bb[2], bb[3])};
         }
         continue;
@@ -705,7 +715,8 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const f4 a = s[j][2 * u], bb = s[j][2 * u + 1];
-        if constexpr (IN == IN_BF16) pb[j][u] = u4{pack2_bf16(a[0], a[1]), pack2_bf16(a[2], a[3]), pack2_bf16(bb[0], bb[1]), pack2_bf16(bb[2], bb[3])};
+        if constexpr (PV2) split8(a, bb, pb[j][u], pl[j][u]);
+        else if constexpr (IN == IN_BF16) pb[j][u] = u4{pack2_bf16(a[0], a[1]), pack2_bf16(a[2], a[3]), pack2_bf16(bb[0], bb[1]), pack2_bf16(bb[2], bb[3])};
         else pb[j][u] = u4{pack2_f16(a[0], a[1]), pack2_f16(a[2], a[3]), pack2_f16(bb[0], bb[1]), pack2_f16(bb[2], bb[3])};
       }
     }
@@ -823,6 +834,10 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
       if constexpr (MODE == 0) {
 #pragma unroll
         for (int j = J0; j < MQ; ++j) lacc[j] = mfma16<IN>(ones, pb[j][u], lacc[j]);
+        if constexpr (PV2) {
+#pragma unroll
+          for (int j = J0; j < MQ; ++j) lacc[j] = mfma16<IN>(ones_lo, pl[j][u], lacc[j]);
+        }
       }
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
@@ -840,6 +855,10 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
           const u4 vl = u4{l3.x, l3.y, h3.x, h3.y};
 #pragma unroll
           for (int j = J0; j < MQ; ++j) ox[j][dt] = mfma16<IN>(vl, pb[j][u], ox[j][dt]);
+          if constexpr (PV2) {  // + V_hi P_lo
+#pragma unroll
+            for (int j = J0; j < MQ; ++j) ox[j][dt] = mfma16<IN>(va, pl[j][u], ox[j][dt]);
+          }
         }
       }
     }
@@ -1109,6 +1128,15 @@ static void launch_flash_d_mq_in(const AttnParams& P, unsigned grid, hipStream_t
   const bool pad = P.pad != nullptr || P.full != nullptr, gate = P.gh != nullptr;  // (the PAD variants also serve a (B,1,Sq,Sk) mask)
   if (P.src32) {  // fp32 storage read directly, fp32 output; no in-kernel gate predictor on this path
     if constexpr (IN == IN_F16 && !(D == 128 && MQ == 2)) {  // (d = 128 with two blocks per wave: never selected, oeh_api.hip: flash_mq)
+      if (P.src32 == 2) {  // PV2: the probability pairs (oeh_api.hip refuses the fake-quant chain with them)
+        if constexpr (!(D == 64 && MQ == 2)) {  // (d = 64 with padding: one block per wave, oeh_api.hip: flash_mq)
+          if (P.clip && pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 1, false, true>), dim3(grid), dim3(256), 0, st, P);
+          else if (pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
+        }
+        if (P.clip && !pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 1, false, true>), dim3(grid), dim3(256), 0, st, P);
+        else if (!pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
+        return;
+      }
       if (P.fq_s.en && pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 2>), dim3(grid), dim3(256), 0, st, P);
       else if (P.fq_s.en) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 2>), dim3(grid), dim3(256), 0, st, P);
       else if (P.clip && pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 1>), dim3(grid), dim3(256), 0, st, P);

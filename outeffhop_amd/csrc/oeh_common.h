@@ -238,6 +238,26 @@ __device__ __forceinline__ void split8_mix(const f4 a, const f4 b, const float k
       : "v"(hi[0]), "v"(hi[1]), "v"(hi[2]), "v"(hi[3]), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "s"(k2048));
   lo = u4{l0, l1, l2, l3};
 }
+// split8_mix for 4 values (one score sub-tile row share of the full-row kernel): hi as pack2_f16 forms it, lo = RN16((x - hi) 2^11)
+__device__ __forceinline__ void split4_mix(const f4 a, const float k2048, unsigned& hi0, unsigned& hi1, unsigned& lo0, unsigned& lo1) {
+  const h2 h0 = sat_h2(a[0], a[1]), h1 = sat_h2(a[2], a[3]);
+  hi0 = __builtin_bit_cast(unsigned, h0);
+  hi1 = __builtin_bit_cast(unsigned, h1);
+  float d0, d1, d2, d3;
+  unsigned l0, l1;
+  asm("v_fma_mix_f32 %0, %6, -1.0, %8 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mix_f32 %1, %6, -1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mix_f32 %2, %7, -1.0, %10 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mix_f32 %3, %7, -1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %4, %0, %12, 0 op_sel_hi:[0,0,0]\n\t"
+      "v_fma_mixhi_f16 %4, %1, %12, 0 op_sel_hi:[0,0,0]\n\t"
+      "v_fma_mixlo_f16 %5, %2, %12, 0 op_sel_hi:[0,0,0]\n\t"
+      "v_fma_mixhi_f16 %5, %3, %12, 0 op_sel_hi:[0,0,0]"
+      : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(l0), "=&v"(l1)
+      : "v"(hi0), "v"(hi1), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "s"(k2048));
+  lo0 = l0;
+  lo1 = l1;
+}
 // The UNSCALED operand pair (round 5): x = hi + lo' with lo' = RN16(x - hi), no 2^11.  tools/probe/mix_probe.hip: v_mfma_f32_16x16x32_f16 takes
 // fp16 SUBNORMAL operands exactly (2^-24 * 1 and 2^-24 * 2^-24 come out exact), so the scaling that kept lo out of the subnormals is not needed by
 // the matrix core; what it bought is precision of lo itself: unscaled, a residual below 2^-14 (|x| < ~0.25) lands on the subnormal grid of 2^-24,

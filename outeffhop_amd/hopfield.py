@@ -15,6 +15,7 @@ from math import sqrt
 import torch
 from torch import nn
 
+from . import attention
 from .attention import unfused_core
 from .ops import SoftmaxSpec, attn_fwd, grad_recording
 from .softmax import SoftmaxFn
@@ -53,7 +54,7 @@ class Association(nn.Module):
         if (self.training and self.dropout.p > 0.0) or grad_recording(q, k, v):  # dropout / autograd: the observable torch-op path
             ctx, _, _ = unfused_core(q, k, v, softmax_fn=self.softmax, scale=scale, dropout=self.dropout)
             return ctx.permute(0, 2, 1, 3).contiguous()
-        out = attn_fwd(q, k, v, softmax=self.softmax.spec, scale=scale)  # stored (B,L,H,D)-contiguous
+        out = attn_fwd(q, k, v, softmax=self.softmax.spec, scale=scale, pv_pairs=attention.pv_pairs_for(q))  # stored (B,L,H,D)-contiguous
         return out.permute(0, 2, 1, 3)
 
 

@@ -5,6 +5,7 @@ liboeh_hip.so; tensors that are not on a GPU are an error (there is no CPU path 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import threading
 from dataclasses import dataclass
 from typing import Optional
@@ -12,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import OEH_BF16, OEH_F16, OEH_F32, oeh_attn_desc, oeh_dropout, oeh_fq, oeh_fq_desc
+from ._lib import OEH_BF16, OEH_F16, OEH_F32, oeh_attn_desc, oeh_attn_opts, oeh_dropout, oeh_fq, oeh_fq_desc
 
 _DT = {torch.float16: OEH_F16, torch.bfloat16: OEH_BF16, torch.float32: OEH_F32}
 
@@ -143,6 +144,7 @@ def attn_fwd(
     out: Optional[torch.Tensor] = None,
     gate_mlp: Optional["GatePredictor"] = None,
     out_dtype: Optional[torch.dtype] = None,
+    pv_pairs: bool = False,
     _prepared: Optional[list] = None,
 ) -> torch.Tensor:
     """Fused attention core.  q,k,v are logical (B,H,S,D) views (any batch/head/seq strides, unit head-dim
@@ -154,7 +156,9 @@ def attn_fwd(
     full_mask: additive (B,1,Sq,Sk); gate: fp32, broadcastable to (B,H,Sq,1), already times the scaling factor.
     out_dtype=torch.float32 with fp16 / bf16 inputs: the output straight from the kernel's fp32 accumulators (include/oeh.h: o_dtype) -
     the kernel's arithmetic before the output rounding, which is how tests / smoke / bench check the "within 1e-3" contract on the
-    kernel that ships; the one-pass and full-row kernels only (OehError -95 otherwise)."""
+    kernel that ships; the one-pass and full-row kernels only (OehError -95 otherwise).
+    pv_pairs=True (fp32 storage): the context to fp32 accuracy too - the probability operand of the second product as an fp16 pair
+    (include/oeh.h: oeh_attn_opts); OehError -95 with 16-bit storage, fake-quant or `gate_mlp`."""
     # ---- the repeated call (round 5): same geometry and options as an earlier call -> that call's prebuilt descriptor, pointers patched.
     # The Python below this block is ~13 us per call (checks, a 40-field ctypes descriptor, mask / gate views) against ~3 us for the launch of a
     # prebuilt one, and the fp16 BERT-base layer is host-bound in eager mode.  Only the plain forms (no fused quantisers, no in-kernel gate predictor,
@@ -164,6 +168,8 @@ def attn_fwd(
             and q.is_cuda and q.dim() == 4 and q.device.index == torch.cuda.current_device()
             and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (gate is not None and gate.requires_grad)))):
         fkey = _fast_key(q, k, v, softmax, scale, scale_div, key_pad_mask, key_pad_boolean, causal, clamp_min, mask_min, gate)
+        if fkey is not None and pv_pairs:
+            fkey = ("pv_pairs", fkey)
         hit = _fast_tls.table.get(fkey) if fkey is not None else None
         if hit is not None:
             fn, d, oshape, odt = hit
@@ -199,7 +205,7 @@ def attn_fwd(
         pad = lambda t: torch.nn.functional.pad(t, (0, Dp - D))  # noqa: E731
         res = attn_fwd(pad(q), pad(k), pad(v), softmax=softmax, scale=scale, scale_div=scale_div, key_pad_mask=key_pad_mask, full_mask=full_mask,
                        key_pad_boolean=key_pad_boolean, causal=causal, clamp_min=clamp_min, mask_min=float(torch.finfo(q.dtype).min if mask_min is None else mask_min), gate=gate,
-                       fq=fq)[..., :D]
+                       fq=fq, pv_pairs=pv_pairs)[..., :D]
         if out is None:
             return res
         out.copy_(res)
@@ -275,22 +281,31 @@ def attn_fwd(
         fqd.ctx_quant_before_gate = int(bool(fq.ctx_before_gate))
         fqd.ctx_emit_index = int(bool(fq.ctx_emit_index))
     lib = _lib.load()
+    fn, what = lib.oeh_attn_fwd, "oeh_attn_fwd"
+    if pv_pairs:  # oeh_attn_fwd_ex with the options bound: the same call signature as oeh_attn_fwd from here on
+        opts = oeh_attn_opts(pv_pairs=1)
+        keep.append(opts)
+        fn, what = functools.partial(_attn_fwd_ex, lib, C.byref(opts)), "oeh_attn_fwd_ex"
     if _prepared is not None:  # hand back the prebuilt C call instead of launching (bench / hipGraph loops)
         _warn_if_any_shape_kernel(lib, d, fqd, softmax)
         args = (C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out), None if fqd is None else C.byref(fqd))
-        _prepared.extend([lib.oeh_attn_fwd, args, (d, fqd, keep, q, k, v, out)])
+        _prepared.extend([fn, args, (d, fqd, keep, q, k, v, out)])
         return out
     with _on_device(dev):
-        rc = lib.oeh_attn_fwd(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out), None if fqd is None else C.byref(fqd), _stream())
-    _lib.check(rc, "oeh_attn_fwd")
+        rc = fn(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out), None if fqd is None else C.byref(fqd), _stream())
+    _lib.check(rc, what)
     _warn_if_any_shape_kernel(lib, d, fqd, softmax)  # (after the launch: a call the library refuses raises above and has run nothing)
     if fkey is not None and fqd is None and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1 and out.shape == (B, H, Sq, D):
         # remember the descriptor for the next call of this geometry (its mask / gate pointers are patched per call; the views `keep` holds
         # were only needed for THIS call's pointers)
         if len(_fast_tls.table) >= 256:
             _fast_tls.table.clear()
-        _fast_tls.table[fkey] = (lib.oeh_attn_fwd, d, (B, Sq, H, D), odt)
+        _fast_tls.table[fkey] = (fn, d, (B, Sq, H, D), odt)
     return out
+
+
+def _attn_fwd_ex(lib, opts, d, q, k, v, o, fqd, stream):
+    return lib.oeh_attn_fwd_ex(d, opts, q, k, v, o, fqd, stream)
 
 
 FAST_CALLS = True
@@ -615,7 +630,7 @@ def fused_gate_ok(B, H, Sq, Sk, D, dtype, clip: bool = False, fq: bool = False, 
     """True when `attn_fwd(..., gate_mlp=...)` is supported for this problem (else: `gate_fwd` + `gate=`).  `problem`: the
     remaining descriptor fields that decide the kernel variant (`attn_variant`'s keywords: base, gamma, key_pad, causal,
     scale, scale_div, mask_min) - the probe must describe the real call, not a default one."""
-    if dtype not in _DT or fq or int(units) > 64:
+    if dtype not in _DT or fq or int(units) > 64 or problem.get("pv_pairs"):  # (the probability pairs: no in-kernel predictor, include/oeh.h)
         return False
     v = attn_variant(B, H, Sq, Sk, D, dtype, clip=clip, gate_hidden=True, **problem)
     if v is None:
@@ -650,9 +665,10 @@ class PreparedAttn:
 
 def attn_variant(B, H, Sq, Sk, D, dtype=torch.float16, fq: bool = False, clip: bool = False, *, base: int = 1, gamma: float = -0.025,
                  key_pad: bool = False, full_mask: bool = False, causal: bool = False, scale: float = 1.0, scale_div: float = 0.0,
-                 mask_min: Optional[float] = None, key_pad_boolean: bool = False, gate_hidden: bool = False) -> Optional[str]:
+                 mask_min: Optional[float] = None, key_pad_boolean: bool = False, gate_hidden: bool = False, pv_pairs: bool = False) -> Optional[str]:
     """Name of the kernel variant the library would pick for this problem (host only; no GPU needed).  `gate_hidden`: with the
-    per-token gate predictor evaluated in the kernel (it narrows the choice)."""
+    per-token gate predictor evaluated in the kernel (it narrows the choice).  `pv_pairs`: with attn_fwd(..., pv_pairs=True) (None where
+    that is refused; the forms with probability pairs end in "+pv2")."""
     d = oeh_attn_desc()
     d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[dtype]
     d.scale, d.scale_div = float(scale), float(scale_div)
@@ -670,7 +686,10 @@ def attn_variant(B, H, Sq, Sk, D, dtype=torch.float16, fq: bool = False, clip: b
         fqd = oeh_fq_desc()
         fqd.scores.enable, fqd.scores.scale, fqd.scores.qmax = 1, 1.0, 255.0
         fqd.probs.enable, fqd.probs.scale, fqd.probs.qmax = 1, 1.0, 255.0
-    r = _lib.load().oeh_attn_variant(C.byref(d), None if fqd is None else C.byref(fqd))
+    if pv_pairs:
+        r = _lib.load().oeh_attn_variant_ex(C.byref(d), C.byref(oeh_attn_opts(pv_pairs=1)), None if fqd is None else C.byref(fqd))
+    else:
+        r = _lib.load().oeh_attn_variant(C.byref(d), None if fqd is None else C.byref(fqd))
     return None if r is None else r.decode()
 
 

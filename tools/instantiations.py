@@ -44,11 +44,14 @@ for line in out.splitlines():
     fam = m.group(1) if m else name
     a = targs(name)
     key = (fam,)
-    if fam == "oeh_attn_flash_kernel":       # <D, IN, MQ, PAD, GATE, SRC32, TP, O32>
-        a = a + [0] * (8 - len(a))
-        key = (fam, "PAD=%d GATE=%d SRC32=%d TP=%d O32=%d" % tuple(a[3:8]), REASON["flash"].get(tuple(a[3:8]), ""))
-    elif fam == "oeh_attn_fast_kernel":      # <NT, D, IN, CLIP, GATE, FQ, SRC32, O32>
-        a = a + [0] * (8 - len(a))
+    if fam == "oeh_attn_flash_kernel":       # <D, IN, MQ, PAD, GATE, SRC32, TP, O32, PV2>
+        a = a + [0] * (9 - len(a))
+        why = REASON["flash"].get(tuple(a[3:8]), "")
+        if a[8]:
+            why = "... with the probability pairs (pv_pairs, DESIGN 4.5): the context to fp32 accuracy; opt-in"
+        key = (fam, "PAD=%d GATE=%d SRC32=%d TP=%d O32=%d PV2=%d" % tuple(a[3:9]), why)
+    elif fam == "oeh_attn_fast_kernel":      # <NT, D, IN, CLIP, GATE, FQ, SRC32, O32, PV2>
+        a = a + [0] * (9 - len(a))
         why = {0: "plain / clipped softmax with the whole score row in registers (Sk <= 512): clipped softmax (cfg3), rows <= 128 keys (BERT-base, cfg2 / cfg5), vanilla + key padding",
                1: "the fused INT8 chain on the quantiser grid (cfg4: OPT + --quantize)", 2: "the INT8 chain in the reference's literal op order (key padding with arbitrary additive values)",
                3: "the INT8 grid chain with a 0 / finfo.min key-padding vector (quantised BERT, padded OPT batches)"}[a[5]]
@@ -56,7 +59,9 @@ for line in out.splitlines():
             why = "... with the per-token gate predictor in the kernel (gated BERT, cfg5)"
         if a[7]:
             why = "O32 sibling (round 4): output from the fp32 accumulators, for the 1e-3 contract checks (d = 64)"
-        key = (fam, "CLIP=%d GATE=%d FQ=%d SRC32=%d O32=%d" % (a[3], a[4], a[5], a[6], a[7]), why + ("; fp32 storage (operand pairs)" if a[6] else ""))
+        if a[8]:
+            why += "; the probability pairs (pv_pairs, DESIGN 4.5)"
+        key = (fam, "CLIP=%d GATE=%d FQ=%d SRC32=%d O32=%d PV2=%d" % (a[3], a[4], a[5], a[6], a[7], a[8]), why + ("; fp32 storage (operand pairs)" if a[6] else ""))
     elif fam == "oeh_attn_mfma_kernel":      # <NT, D, IN, FQ>
         key = (fam, "FQ=%d" % (a[3] if len(a) > 3 else 0), "general kernel: (B,1,Sq,Sk) masks, true score division, gamma > 0, any subset of the quantisers, the test-only index dumps; Sk <= 512")
     elif fam == "oeh_attn_i8_kernel":        # <NT, OUT, DUMP, CQ2, PAD>

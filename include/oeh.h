@@ -338,7 +338,8 @@ int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* 
  *   lse = m' + log(sum_k e^(x_k - m') + [softmax_1] e^(-m')),  m' = max(m, 0) for softmax_1, m for softmax
  * so that p = e^(x - lse) for either base (a fully masked softmax_1 row: p = 0; a fully masked vanilla row: uniform).
  * oeh_attn_bwd: do_, dq, dk, dv in desc->dtype with their own (batch, head, seq) element strides; o and lse from
- *   oeh_attn_fwd_train; work: caller-provided fp32 scratch of oeh_attn_bwd_work_bytes(desc) bytes (the row term delta).  Two kernels
+ *   oeh_attn_fwd_train; work: caller-provided fp32 scratch of oeh_attn_bwd_work_bytes(desc) bytes (two terms per query row: delta, and
+ *   log(den) of a row whose fp32 lse cannot hold it - a vanilla row at finfo.min of bf16 / fp32).  Two kernels
  *   (dq, then dk / dv), no allocation, no atomics: the gradients are bitwise reproducible; graph-capture safe.
  * oeh_attn_bwd_work_bytes: bytes of `work`, or the negative OEH_E* code of an unsupported / invalid descriptor. */
 int oeh_attn_fwd_train(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, float* lse, void* stream);

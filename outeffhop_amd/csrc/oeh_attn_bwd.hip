@@ -41,6 +41,7 @@ struct Params {
   void *dq, *dk, *dv, *out;
   float* lse;
   float* delta;
+  float* rowc;                // log of the number of keys at the row maximum where lse could not hold it (saturated rows), else 0
   int B, H, Sq, Sk;
   long qs_b, qs_h, qs_s, ks_b, ks_h, ks_s, vs_b, vs_h, vs_s, os_b, os_h, os_s, ds_b, ds_h, ds_s;
   long dqs_b, dqs_h, dqs_s, dks_b, dks_h, dks_s, dvs_b, dvs_h, dvs_s;
@@ -128,14 +129,15 @@ __device__ __forceinline__ float score(const Params& P, float dot, int b, int qi
   if (P.clamp_min) x = __builtin_fmaxf(x, P.mask_min);
   return x;
 }
-// the clamp's gradient gate: torch.max(x, floor) passes nothing where x was below the floor
+// the clamp's gradient gate: torch.max(x, floor) passes nothing where x was below the floor, and half where x equals it (autograd
+// splits the gradient of a tie between the two arguments; with bf16 storage x + finfo.min is the floor itself in fp32 and in float64)
 __device__ __forceinline__ float clamp_pass(const Params& P, float dot, int b, int qi, int ki, float padv) {
   if (!P.clamp_min) return 1.0f;
   float x = dot * P.scale;
   if (P.pad) x = x + padv;
   if (P.full) x = x + load_mask(P.full, P.full_f16, (long)b * P.full_sb + (long)min(qi, P.Sq - 1) * P.full_sq + ki);
   if (P.causal && ki > qi + (P.Sk - P.Sq)) x = x + P.mask_min;
-  return x < P.mask_min ? 0.0f : 1.0f;
+  return x < P.mask_min ? 0.0f : (x == P.mask_min ? 0.5f : 1.0f);
 }
 
 __device__ __forceinline__ float pad_of(const Params& P, int b, int ki) {
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
   f4 acc[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) acc[dt] = f4{0.f, 0.f, 0.f, 0.f};
-  float lse_row = 0.0f;
+  float lse_row = 0.0f, c_row = 0.0f;  // c_row: log(den) of a saturated row (lse_row + 64 == lse_row: the sum is lost in it), else 0
   // pass 0: statistics only (clip: p must be final before the clip), pass 1: P V with the final p; no clip: one online pass
   const int npass = P.clip ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
         for (int i = 0; i < 4; ++i) {
           float e;
           if (P.clip && pass == 1) {
-            const float pp = expf(x[t][i] - lse_row);
+            const float pp = expf((x[t][i] - lse_row) - c_row);
             const float u = pp * P.clip_w + P.clip_g;
             e = __builtin_fminf(__builtin_fmaxf(u, 0.0f), 1.0f);
           } else {
@@ -306,6 +308,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
       const float mm = m == -INFINITY ? 0.0f : m;
       const float den = P.base == 1 ? lt + expf(-mm) : lt;
       lse_row = den > 0.0f ? mm + logf(den) : INFINITY;  // (INFINITY: a vanilla row with no finite score - p = 0)
+      if (lse_row < 0.0f && lse_row + 64.0f == lse_row) c_row = logf(den);  // (the dq kernel counts the same den: see there)
       if (!P.clip) {
         const float r = den > 0.0f ? 1.0f / den : 0.0f;
 #pragma unroll
@@ -350,6 +353,35 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
   }
   const float L = qok ? P.lse[(long)bh * P.Sq + qi] : INFINITY;
   const int nkt = key_tiles_for(P, qt);
+  // A saturated row: its maximum m is so large in magnitude (a vanilla row masked by finfo.min of bf16 / fp32) that fp32 lse = m +
+  // log(den) IS m - e^(x - lse) would be 1 on every key at the maximum instead of 1 / den.  There every x is either m itself or far
+  // enough below it to give p = 0, so den is the number of keys with x == lse: counted here, and p = e^((x - lse) - c) with c = log(den)
+  // (c = 0 on every other row: the same bits as e^(x - lse)).
+  const bool sat = qok && L < 0.0f && L + 64.0f == L;
+  float c = 0.0f;
+  if (__syncthreads_or(sat)) {
+    float cnt = 0.0f;
+    for (int kt = 0; kt < nkt; ++kt) {
+      __syncthreads();
+      tile_to_lds<true, false>(k, P.ks_s, kt * T, P.Sk, Ks, nullptr);
+      if (threadIdx.x < T) padS[threadIdx.x] = pad_of(P, b, kt * T + threadIdx.x);
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        f4 s = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kc = 0; kc < 2; ++kc) s = mma<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int kl = 16 * t + 4 * g + i;
+          cnt += score(P, s[i], b, qi, kt * T + kl, padS[kl]) == L ? 1.0f : 0.0f;
+        }
+      }
+    }
+    cnt = row4_sum(cnt);
+    if (sat && cnt > 1.0f) c = logf(cnt);
+  }
+  if (qok && g == 0) P.rowc[(long)bh * P.Sq + qi] = c;
   float delta = 0.0f;
   if (!P.clip) {  // rowsum(dO o O): the lane's 16 of the row's 64 products, then the 4 lanes of the row
     float part = 0.0f;
@@ -393,7 +425,7 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
         for (int i = 0; i < 4; ++i) {
           const int kl = 16 * t + 4 * g + i, ki = kt * T + kl;
           const float x = score(P, s[i], b, qi, ki, padS[kl]);
-          const float p = (qok && ki < P.Sk) ? expf(x - L) : 0.0f;
+          const float p = (qok && ki < P.Sk) ? expf((x - L) - c) : 0.0f;
           if (sweep) {
             float y;
             dpart += dx_of(P, p, dy[i], 0.0f, y);
@@ -433,7 +465,7 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
   __shared__ __attribute__((aligned(16))) unsigned short Qt[D * LD];
   __shared__ __attribute__((aligned(16))) unsigned short Ds[T * LD];
   __shared__ __attribute__((aligned(16))) unsigned short Dt[D * LD];
-  __shared__ float lseS[T], deltaS[T];
+  __shared__ float lseS[T], deltaS[T], cS[T];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4;
   const int nBH = P.B * P.H;
   const int bid = blockIdx.x;
@@ -463,6 +495,7 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
       const int qq = qt * T + threadIdx.x;
       lseS[threadIdx.x] = qq < P.Sq ? P.lse[(long)bh * P.Sq + qq] : INFINITY;
       deltaS[threadIdx.x] = qq < P.Sq ? P.delta[(long)bh * P.Sq + qq] : 0.0f;
+      cS[threadIdx.x] = qq < P.Sq ? P.rowc[(long)bh * P.Sq + qq] : 0.0f;
     }
     __syncthreads();
     u2 kb = u2{0u, 0u};
@@ -481,7 +514,7 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
         const int ql = 16 * t + 4 * g + i, qi = qt * T + ql;
         const bool ok = kok && qi < P.Sq;
         const float x = score(P, s[i], b, qi, ki, padv);
-        const float p = ok ? expf(x - lseS[ql]) : 0.0f;
+        const float p = ok ? expf((x - lseS[ql]) - cS[ql]) : 0.0f;
         float yy;
         if constexpr (DROP) {  // dV takes z = keep y / (1 - p), dX takes dY = keep / (1 - p) dZ
           const float f = ((kb[t >> 1] >> (16 * (t & 1) + 4 * i)) & 1u) ? P.drop_scale : 0.0f;
@@ -643,6 +676,7 @@ int bwd_run(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, c
   Params P;
   fill(P, desc);
   P.q = q; P.k = k; P.v = v; P.o = o; P.dout = do_; P.lse = const_cast<float*>(lse); P.delta = reinterpret_cast<float*>(work);
+  P.rowc = P.delta + (long)desc->B * desc->H * desc->Sq;
   P.dq = dq; P.dk = dk; P.dv = dv;
   P.ds_b = do_stride[0]; P.ds_h = do_stride[1]; P.ds_s = do_stride[2];
   P.dqs_b = dq_stride[0]; P.dqs_h = dq_stride[1]; P.dqs_s = dq_stride[2];
@@ -695,7 +729,7 @@ int oeh_attn_fwd_train_dropout(const oeh_attn_desc* desc, const oeh_dropout* dro
 int64_t oeh_attn_bwd_work_bytes(const oeh_attn_desc* desc) {
   const int rc = check_desc(desc);
   if (rc != OEH_OK) return rc;
-  return (int64_t)desc->B * desc->H * desc->Sq * (int64_t)sizeof(float);
+  return 2 * (int64_t)desc->B * desc->H * desc->Sq * (int64_t)sizeof(float);  // delta and rowc per query row
 }
 
 int oeh_attn_bwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, const void* o, const void* do_,

@@ -43,7 +43,9 @@ def _bwd(lib, d, ptr):
     return lib.oeh_attn_bwd(C.byref(d), ptr, ptr, ptr, ptr, ptr, st, ptr, ptr, st, ptr, st, ptr, st, ptr, None)
 
 
-def test_validation_codes_without_gpu():
+def test_validation_codes_and_work_size_without_gpu():
+    """The entry points' error codes, and the size of `work`: two fp32 terms per query row - delta, and log(den) of a saturated row
+    (include/oeh.h: oeh_attn_bwd)."""
     from outeffhop_amd import _lib
 
     lib = _lib.load()
@@ -51,7 +53,7 @@ def test_validation_codes_without_gpu():
     assert lib.oeh_attn_fwd_train(None, one, one, one, one, one, None) == -22
     assert lib.oeh_attn_bwd_work_bytes(None) == -22
     d = _desc()
-    assert lib.oeh_attn_bwd_work_bytes(C.byref(d)) == 2 * 12 * 512 * 4
+    assert lib.oeh_attn_bwd_work_bytes(C.byref(d)) == 2 * (2 * 12 * 512) * 4  # B * H * Sq rows, 2 fp32 terms each
     assert lib.oeh_attn_fwd_train(C.byref(d), None, one, one, one, one, None) == -22  # null q
     assert _bwd(lib, d, None) == -22                                                  # null pointers
     for bad, code in ((dict(dtype=2), -95), (dict(dtype=3), -95), (dict(D=128), -95), (dict(D=32), -95), (dict(dtype=7), -22)):

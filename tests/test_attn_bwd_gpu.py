@@ -152,10 +152,21 @@ def test_gradient_parity_bert_scaling_and_batches():
 @pytest.mark.parametrize("sm", ["vanilla", "softmax1"])
 def test_fully_masked_rows(sm):
     """Rows with every key at the mask floor: softmax_1 gives p = 0 and zero gradients, vanilla a uniform row; finite, no NaN."""
+    _fully_masked_rows(sm, torch.float16)
+
+
+@pytest.mark.parametrize("sm", ["vanilla", "softmax1"])
+def test_fully_masked_rows_bf16(sm):
+    """test_fully_masked_rows in bf16: x + finfo.min IS the floor (in fp32 and in float64), so the clamp ties and passes half the
+    gradient, as autograd's max does; and the vanilla row's fp32 lse = m + log(den) rounds to m (the saturated rows of the kernels)."""
+    _fully_masked_rows(sm, torch.bfloat16)
+
+
+def _fully_masked_rows(sm, dt):
     from outeffhop_amd import fused_attention
 
     spec = _spec(sm)
-    B, H, S, dt = 1, 2, 96, torch.float16
+    B, H, S = 1, 2, 96
     q, k, v, do, _, _, _, _, _, mask_min = _problem(B, H, S, dt, "none", 11)
     full = torch.zeros(B, 1, S, S)
     full[:, :, 5] = mask_min

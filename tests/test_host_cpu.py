@@ -382,24 +382,31 @@ class Cfg0(Cfg):
     attention_probs_dropout_prob = 0.0
 
 
-def build_train_toy(g, case, device):
-    """The toy of tests/golden/make_golden.py:gen_train_grads out of this package's modules, with the reference's weights."""
+def build_train_toy(g, case, device, dtype=torch.float32):
+    """The toy of tests/golden/make_golden.py:gen_train_grads out of this package's modules, with the reference's weights (stored in
+    `dtype`)."""
     la = oa.OPTAttentionWithExtras(128, 2, is_decoder=True, softmax_fn=oa.SOFTMAX_MAPPING[case["softmax_a"]], **gate_kwargs(case["gate_a"]))
     lb = oa.BertSelfAttentionWithExtras(Cfg0(), softmax_fn=oa.SOFTMAX_MAPPING[case["softmax_b"]], **gate_kwargs(case["gate_b"]))
     for tag, mod in (("a", la), ("b", lb)):
         pre = f"{case['name']}.{tag}.w."
         mod.load_state_dict({k[len(pre):]: torch.from_numpy(g[k]) for k in g.files if k.startswith(pre)}, strict=True)
-        mod.to(device).train()
+        mod.to(device=device, dtype=dtype).train()
     return la, lb
 
 
-def run_train_toy(g, case, device):
-    la, lb = build_train_toy(g, case, device)
-    x = torch.from_numpy(g["x"]).to(device).requires_grad_(True)
-    y = x + la(x, attention_mask=torch.from_numpy(g["opt_mask"]).to(device))[0]
-    z = lb(y, attention_mask=torch.from_numpy(g["bert_mask"]).to(device))[0]
+def run_train_toy(g, case, device, dtype=torch.float32):
+    """The toy's forward and backward; a 16-bit `dtype` stores weights, input and masks in it (the masks clamped at its finfo.min, as
+    HF builds them for a model of that dtype)."""
+    la, lb = build_train_toy(g, case, device, dtype)
+    def mask(n):
+        m = torch.from_numpy(g[n])
+        return (m if dtype == torch.float32 else m.clamp(min=torch.finfo(dtype).min)).to(device=device, dtype=dtype)
+
+    x = torch.from_numpy(g["x"]).to(device=device, dtype=dtype).requires_grad_(True)
+    y = x + la(x, attention_mask=mask("opt_mask"))[0]
+    z = lb(y, attention_mask=mask("bert_mask"))[0]
     assert z.grad_fn is not None
-    (z * torch.from_numpy(g["w"]).to(device)).sum().backward()
+    (z * torch.from_numpy(g["w"]).to(device=device, dtype=dtype)).sum().backward()
     return la, lb, x, z
 
 

@@ -23,7 +23,6 @@ int launch_attn_flash_d128(const AttnParams& P, int in, int mq, hipStream_t st);
 int launch_attn_generic(const AttnParams& P, int in, hipStream_t st);
 int launch_attn_small(const AttnParams& P, int in, hipStream_t st);
 int launch_attn_i8(const AttnParams& P, int out, hipStream_t st);
-int launch_attn_wide(const AttnParams& P, int in, hipStream_t st);
 int launch_softmax_rows(const void* x, void* y, long rows, int cols, int in, int base, int clip, float w, float g, hipStream_t st);
 int launch_fake_quant(const void* x, void* y, unsigned char* idx, long n, int in, FqP f, hipStream_t st);
 int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_b, long hs_t, const float* w1, const float* b1,
@@ -71,6 +70,24 @@ FqP make_fq(const oeh_fq* f) {
 
 enum Variant { V_NONE = 0, V_FLASH, V_FAST, V_MFMA, V_GENERIC, V_SMALL, V_I8 };
 
+// Diagnostic hooks (include/oeh_debug.h; oeh_debug_set_variant / oeh_debug_set_stamps below): the bits of off_mask by name.  Bit
+// (1 << Variant) switches a variant off; bits 6 / 7 are no Variant values.
+enum Hook {
+  HOOK_NO_FLASH_F32 = 1 << 6,   // the fp32-storage form of the one-pass kernel off
+  HOOK_NO_FAST_F32 = 1 << 7,    // the fp32-storage form of the full-row kernel off
+  HOOK_FORCE_FLASH = 1 << 8,    // tools/microbench.py only: the one-pass kernel also where the full-row kernel measured faster
+  HOOK_PLAIN_ORDER = 1 << 9,    // tools/microbench.py only: plain block order in the one-pass kernel (no snake placement)
+  HOOK_FORCE_SMALL = 1 << 10,   // tests: the small-shape kernel wherever it can run (no size heuristic)
+  HOOK_NO_D128_RULE = 1 << 11,  // tests: the full-row kernel also for head dim 128 with clip / INT8 (the comparison against the general kernel)
+  HOOK_ALL = 0xfff              // (bit 12 and up: reserved, ignored)
+};
+struct Hooks {
+  int off;                      // off_mask & HOOK_ALL
+  int flash_mq;                 // tools/microbench.py only: force query blocks per wave
+  int head_group;               // tools/microbench.py only (OEH_HEAD_GROUP): block order of the fp32-storage kernels in groups of heads
+  unsigned long long* stamps;   // tools/timeline.py only
+} g_hooks = {};
+
 // rows must be 16-byte aligned for the MFMA path's 16-B loads / 8..16-B stores
 bool aligned16(const void* p, const int64_t* st, int eb) {
   if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
@@ -79,10 +96,15 @@ bool aligned16(const void* p, const int64_t* st, int eb) {
   return true;
 }
 
+// The descriptor sanity every entry point starts with: positive sizes (the head dim where the caller does not judge it itself) and a
+// storage type (INT8 where the caller takes it)
+bool desc_sane(const oeh_attn_desc* d, bool with_D, bool with_i8) {
+  if (d == nullptr || d->B <= 0 || d->H <= 0 || d->Sq <= 0 || d->Sk <= 0 || (with_D && d->D <= 0)) return false;
+  return dtype_ok(d->dtype) || (with_i8 && d->dtype == OEH_I8);
+}
+
 int validate(const oeh_attn_desc* d, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq) {
-  if (d == nullptr || q == nullptr || k == nullptr || v == nullptr || o == nullptr) return OEH_EINVAL;
-  if (d->B <= 0 || d->H <= 0 || d->Sq <= 0 || d->Sk <= 0 || d->D <= 0) return OEH_EINVAL;
-  if (!dtype_ok(d->dtype) && d->dtype != OEH_I8) return OEH_EINVAL;
+  if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || !desc_sane(d, true, true)) return OEH_EINVAL;
   if (d->dtype == OEH_I8) {
     if (!dtype_ok(d->o_dtype) && d->o_dtype != OEH_I8) return OEH_EINVAL;
     // (an int8 output is the context quantiser's centred indices: only with ctx_emit_index on a full 8-bit grid with a whole zero point)
@@ -122,24 +144,28 @@ int validate(const oeh_attn_desc* d, const void* q, const void* k, const void* v
   return OEH_OK;
 }
 
-// 16-bit q / k / v with the output taken from the fp32 accumulators (include/oeh.h: o_dtype)
-bool want_out32(const oeh_attn_desc* d) { return (d->dtype == OEH_F16 || d->dtype == OEH_BF16) && d->o_dtype == OEH_F32; }
-
 bool any_fq(const oeh_fq_desc* fq) { return fq != nullptr && (fq->scores.enable || fq->probs.enable || fq->ctx.enable); }
+
+// the per-token gate predictor evaluated in the kernel (gate values given: they win)
+bool gate_in_kernel(const oeh_attn_desc* d) { return d->gate == nullptr && d->gate_hidden != nullptr; }
 
 bool is_pow2(float x) {
   int e = 0;
   return x > 0.0f && std::isfinite(x) && std::frexp(x, &e) == 0.5f;
 }
 
+// ---- What each kernel family CAN run.  Where another family's kernel reuses these conditions it says so in the arguments: as16 - fp32
+// storage counts as 16-bit (the SRC32 forms read it directly: tiles staged through registers, fp16 operands, fp32 output); no_full - the
+// caller's kernel reads the (B,1,Sq,Sk) mask itself.
+
 // The fast kernel (oeh_attn_fast.inl) covers 16-bit storage, masks in {none, key padding, causal} and a positive
 // multiplicative scale (a power-of-two divisor is the same multiply, exactly); fake-quant is its FQ variant.
-bool fast_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
-  if (d->dtype == OEH_F32 || d->full_mask != nullptr) return false;
+bool fast_can(const oeh_attn_desc* d, const oeh_fq_desc* fq, bool as16 = false, bool no_full = false) {
+  if ((d->dtype == OEH_F32 && !as16) || (d->full_mask != nullptr && !no_full)) return false;
   // the LDS-DMA streams address a tile as scalar base + 32-bit lane byte offsets (up to 64 rows of the sequence stride)
   if (d->q_stride[2] >= (1 << 24) || d->k_stride[2] >= (1 << 24) || d->v_stride[2] >= (1 << 24) || d->q_stride[2] < 0 || d->k_stride[2] < 0 || d->v_stride[2] < 0) return false;
   if (any_fq(fq)) {  // the FQ variant: scores and probabilities both quantised (the reference's configuration), no in-kernel predictor
-    if (!(fq->scores.enable && fq->probs.enable) || (d->gate == nullptr && d->gate_hidden != nullptr)) return false;
+    if (!(fq->scores.enable && fq->probs.enable) || gate_in_kernel(d)) return false;
     if (fq->scores.dump_idx != nullptr || fq->probs.dump_idx != nullptr || fq->ctx.dump_idx != nullptr) return false;  // test-only dumps: general kernel
   }
   // a divisor (BERT order, bert_attention.py:265): a power of two is the same multiply exactly; any other positive divisor
@@ -153,107 +179,43 @@ bool fast_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
   return true;
 }
 
-int g_force_flash = 0;                   // tools/microbench.py only
-int g_no_d128_rule = 0;                 // tests: the full-row kernel also for head dim 128 with clip / INT8 (the comparison against the general kernel)
-int g_force_small = 0;                   // tests: the small-shape kernel wherever it can run (no size heuristic)
-int g_wide = 0;                          // tools / tests: the 32x32x16 form of the one-pass kernel (oeh_attn_wide.hip) wherever it applies
-
 // The one-pass kernel (oeh_attn_flash.inl) additionally needs the plain softmax_n (no clip).  No Sk limit.
-bool flash_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq, bool short_rows_too = false) {
-  if (d->full_mask != nullptr) {  // a (B,1,Sq,Sk) mask: only where the general kernel does not reach (rows of more than 512 keys); PAD variant
-    oeh_attn_desc t = *d;
-    t.full_mask = nullptr;
-    return d->Sk > 512 && !d->clip && !any_fq(fq) && fast_eligible(&t, fq) && (d->mask_min < -1.0e4f);
-  }
-  if (!fast_eligible(d, fq) || d->clip || any_fq(fq)) return false;
+// fp32 storage (as16): the same conditions on the problem; the in-kernel gate predictor reads a 16-bit layer input and is not available
+bool flash_can(const oeh_attn_desc* d, const oeh_fq_desc* fq, bool as16) {
+  if (d->clip || any_fq(fq) || (as16 && gate_in_kernel(d))) return false;
+  // a (B,1,Sq,Sk) mask: only where the general kernel does not reach (rows of more than 512 keys); PAD variant
+  if (d->full_mask != nullptr) return d->Sk > 512 && fast_can(d, fq, as16, true) && (d->mask_min < -1.0e4f);
   // (key padding under the vanilla softmax: a row without a visible key is uniform over ALL keys in the reference - the PAD variant's
   // epilogue gives such rows the mean of V, oeh_attn_flash.inl)
-  if (short_rows_too) return true;
-  // short rows (<= 128 keys) fit the full-row kernel's registers in one pass, which measures faster there (BERT-base B=32 S=128:
-  // 7.7 vs 9.7 us per launch) - until the batch is large enough for the one-pass kernel's 128-row workgroups to fill the chip by
-  // themselves (>= 768 of them): then its halved K / V streaming wins (H=12 S=128, round 3: B=48 12.3 vs 13.0 us, B=64 15.5 vs 14.5,
-  // B=96 23.0 vs 20.3, B=128 31.5 vs 24.2)
-  // causal rows whose count leaves the last 128-row workgroup at most half full (S = 192, 320, 448): the full-row kernel's 64-row
-  // workgroups waste nothing there (16.9 vs 18.3, 15.7 vs 17.1, 18.7 vs 19.4 us); without the causal mask the one-pass kernel keeps its lead
-  // (round 4, profiles/r04_dispatch_ab.txt - both sides of every rule in one process: S = 192 4.8 %, S = 320 3.1 % for the full-row kernel,
-  // S = 448 a tie (18.3 vs 18.2 us): the rule ends at 384 keys, like its fp32 twin below)
-  if (d->causal && d->Sk <= 384 && ((d->Sq - 1) % 128) < 64 && d->Sq > 128 && !g_force_flash && !short_rows_too) return false;
-  if (d->Sk <= 128 && !g_force_flash) {
-    const long wgs = (long)d->B * d->H * ((d->Sq + 127) / 128);
-    // (one threshold for every head dim since round 4: at d = 32 and 768 workgroups the one-pass kernel measured 10.0 vs 11.0 us, at
-    // 1536 16.7 vs 21.8 - the separate d <= 32 threshold of 1536 was the wrong way round on the re-measurement)
-    if (!(d->Sk > 64 && d->Sq >= 112 && wgs >= 768)) return false;
-  }
-  return true;
+  return fast_can(d, fq, as16);
 }
 
-// Clipped softmax on rows of MORE than 512 keys: the one-pass kernel's two-pass form (CLIP: statistics, then the product;
-// oeh_attn_flash.inl).  Up to 512 keys the full-row kernel computes the scores once and is the faster one.
-bool flash_clip_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
-  oeh_attn_desc t = *d;
-  if (t.dtype == OEH_F32) t.dtype = OEH_F16;  // fp32 storage: the SRC32 form (operand pairs), same conditions on the problem
+// The one-pass kernel's two-pass forms, in 16-bit and (SRC32, operand pairs) fp32 storage alike, no in-kernel gate predictor:
+//  - the fused INT8 chain (TP = 2).  What the full-row kernel's FQ == 1 takes: scores and probabilities both quantised, no clip, no key
+//    padding, no test dumps;
+//  - clipped softmax (CLIP: statistics, then the product; oeh_attn_flash.inl).
+bool flash_two_pass_can(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
+  if (gate_in_kernel(d)) return false;
+  if (any_fq(fq)) {
+    if (!fast_can(d, fq, true)) return false;  // (fast_can: both quantisers, no dumps, scale, masks, gamma <= 0 when clipped)
+    // key padding: on the grid only as a vector of 0 / <= -1e4 entries (key_pad_boolean), and with softmax_1 (trailing padded tiles are not streamed)
+    if (d->key_pad_mask != nullptr && !(d->key_pad_boolean && d->softmax_base == OEH_SOFTMAX_ONE)) return false;
+    return !(fq->probs.qmax > (d->dtype == OEH_BF16 ? 255.0f : 2047.0f));  // the integer-valued P operand must be exact
+  }
   // round 4: a (B,1,Sq,Sk) mask on rows of more than 512 keys too (the PAD variants read it per block, as the plain one-pass form does)
   const bool long_full = d->full_mask != nullptr && d->Sk > 512 && (d->mask_min < -1.0e4f);
-  if (long_full) t.full_mask = nullptr;
-  if (!d->clip || any_fq(fq) || !fast_eligible(&t, fq)) return false;  // (fast_eligible: gamma <= 0, masks, scale)
-  if (d->gate == nullptr && d->gate_hidden != nullptr) return false;
   // (key padding / a full mask under the VANILLA softmax since round 4: a row without a visible key - uniform over all Sk keys in the
   // reference - gets clip(w / Sk + gamma) times the sum of V in the epilogue, oeh_attn_flash.inl)
-  return d->Sk > 512 || (d->D == 128 && d->Sk >= 384 && d->full_mask == nullptr) || (g_force_flash && d->full_mask == nullptr);  // (d = 128, S = 512: 47.4 vs 58.2 us in the full-row kernel, causal 38.1 vs 41.2)
-}
-
-// The fused INT8 chain on rows of MORE than 512 keys: the one-pass kernel's two-pass form of the grid chain (TP = 2).  What
-// the full-row kernel's FQ == 1 takes: scores and probabilities both quantised, no clip, no key padding, no test dumps.
-bool flash_fq_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
-  oeh_attn_desc t = *d;
-  if (t.dtype == OEH_F32) t.dtype = OEH_F16;  // fp32 storage: the SRC32 form
-  if (!any_fq(fq) || !fast_eligible(&t, fq)) return false;  // (fast_eligible: both quantisers, no dumps, scale, masks, gamma <= 0 when clipped)
-  if (d->gate == nullptr && d->gate_hidden != nullptr) return false;
-  // key padding: on the grid only as a vector of 0 / <= -1e4 entries (key_pad_boolean), and with softmax_1 (trailing padded tiles are not streamed)
-  if (d->key_pad_mask != nullptr && !(d->key_pad_boolean && d->softmax_base == OEH_SOFTMAX_ONE)) return false;
-  if (fq->probs.qmax > (d->dtype == OEH_BF16 ? 255.0f : 2047.0f)) return false;  // the integer-valued P operand must be exact
-  return d->Sk > 512 || g_force_flash;
-}
-
-// fp32 storage on the one-pass kernel (SRC32 variants: tiles staged through registers, fp16 operands, fp32 output): the same
-// conditions on the problem; the in-kernel gate predictor reads a 16-bit layer input and is not available
-bool flash32_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
-  if (d->dtype != OEH_F32 || (d->gate == nullptr && d->gate_hidden != nullptr)) return false;
-  oeh_attn_desc t = *d;
-  t.dtype = OEH_F16;
-  if (!flash_eligible(&t, fq, true)) return false;
-  // rows of <= 128 keys: the full-row kernel's fp32 form where it applies, at every batch size measured (round 3, H=12 S=128: B=32 16.5
-  // vs 20.0 us, B=64 29.8 vs 30.6, B=128 54.6 vs 57.7); what it does not take stays here (16.7 us in the general kernel)
-  // (with >= 768 of its 128-row workgroups the one-pass form is ahead again: B=64 25.8 vs 30.5 us; with a padding vector 30.5 vs 31.5 -
-  // round 4: one rule for both, profiles/r04_dispatch_ab.txt)
-  const bool many_unpadded = d->Sq >= 112 && d->Sk > 64 && (long)d->B * d->H * ((d->Sq + 127) / 128) >= 768;
-  if (d->Sk <= 128 && !g_force_flash && d->full_mask == nullptr && !many_unpadded && fast_eligible(&t, fq)) return false;
-  // ... and causal rows that leave the last 128-row workgroup at most half full, up to 320 rows (S = 192: 33.1 vs 40.3 us, S = 320: 38.4 vs
-  // 39.0; S = 448: 42.9 vs 42.2 - the one-pass kernel again)
-  if (d->causal && d->Sk <= 384 && d->Sq > 128 && ((d->Sq - 1) % 128) < 64 && !g_force_flash && d->full_mask == nullptr && fast_eligible(&t, fq)) return false;
-  return true;
-}
-// ... and on the full-row kernel (clipped softmax, the INT8 chain, vanilla softmax with key padding)
-bool fast32_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
-  if (d->dtype != OEH_F32) return false;  // (the in-kernel gate predictor: on operand pairs here - fast_eligible refuses it together with fake-quant)
-  oeh_attn_desc t = *d;
-  t.dtype = OEH_F16;
-  return fast_eligible(&t, fq);
+  return d->clip && fast_can(d, fq, true, long_full);  // (fast_can: gamma <= 0, masks, scale)
 }
 
 // The small-shape kernel (oeh_attn_small.hip: one wave per (batch, head), K and V in registers, fp32 matrix-core products):
 // many tiny problems - STanHop's Association (L, S ~ 28, H = 4, E in {16, 32, 64}, batch * data_dim problems).  No masks,
 // no fake-quant, no in-kernel gate predictor; rows of 4 elements must be 4-element aligned (16 B in fp32, 8 B in 16-bit).
-bool small_eligible(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq) {
+bool small_can(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq) {
   if (any_fq(fq) || d->key_pad_mask != nullptr || d->full_mask != nullptr || d->causal) return false;
-  if (d->gate == nullptr && d->gate_hidden != nullptr) return false;
+  if (gate_in_kernel(d)) return false;
   if (!(d->D == 16 || d->D == 32 || d->D == 64) || d->Sk > 64 || d->Sq > 64) return false;
-  // A wave per problem only pays when there are enough problems to fill the chip, on fp32 data - where it also is the EXACT path (fp32
-  // matrix-core products: 3e-6 of the reference; the operand-pair kernels round the probability operand to fp16) - and on rows of at
-  // most 32 keys: measured, round 3 (d = 64, against the full-row kernel's fp32 form): B*H = 896 S = 28 9.4 vs 8.9 us (kept here: STanHop's
-  // shape, the exact path), B*H = 1536 S = 32 13.3 vs 13.7, but S = 48 29.8 vs 20.2 and S = 64 37.0 vs 22.7; 16-bit data: S = 28 8.3 vs 8.05
-  // in the full-row kernel, S = 48 18.6 vs 6.6, S = 64 19.9 vs 7.1 - or when no matrix-core kernel takes the shape (d = 16)
-  if (!g_force_small && d->D != 16 && (d->dtype != OEH_F32 || d->Sk > 32 || d->Sq > 32 || (long)d->B * d->H < 256)) return false;
   const int ab = 4 * elem_bytes(d->dtype);
   const int64_t* sts[4] = {d->q_stride, d->k_stride, d->v_stride, d->o_stride};
   const void* ps[4] = {q, k, v, o};
@@ -265,35 +227,6 @@ bool small_eligible(const oeh_attn_desc* d, const void* q, const void* k, const 
   return true;
 }
 
-unsigned long long* g_stamps = nullptr;  // tools/timeline.py only
-int g_variant_off = 0;                   // tools/microbench.py only: bit (1 << Variant) disables a variant
-int g_flash_mq = 0;                      // tools/microbench.py only: force query blocks per wave
-int g_head_group = 0;                    // tools/microbench.py only (OEH_HEAD_GROUP): block order of the fp32-storage kernels in groups of heads
-int g_place = 0;                         // tools/microbench.py only: 1 = plain block order in the one-pass kernel (no snake placement)
-
-// query blocks (16 rows) per wave of the one-pass kernel: 2 (128-row workgroups) once that still gives every CU two
-// workgroups, else 1
-int flash_mq(const oeh_attn_desc* d, bool pv2 = false) {
-  // the probability pairs with key padding / a (B,1,Sq,Sk) mask at head dim 64: one block per wave (two spill - the fp32 forms with padding are
-  // at the register file's edge already; oeh_attn_flash.inl instantiates only this one)
-  if (pv2 && d->D == 64 && (d->key_pad_mask != nullptr || d->full_mask != nullptr)) return 1;
-  if (g_flash_mq != 0 && !(d->D == 128 && d->dtype == OEH_F32)) return g_flash_mq;
-  if (d->D == 128 && d->dtype == OEH_F32) return 1;  // two blocks of fp32 operand pairs at d = 128 do not fit the register file (130 spills)
-  const long wg2 = (long)((d->Sq + 127) / 128) * d->B * d->H;
-  return (d->Sq > 64 && wg2 >= 416) ? 2 : 1;  // (H=12 S=512 causal: B=8 - 384 workgroups - 10.8 vs 12.4 us with one block per wave, B=9 - 432 - 13.3 vs 12.8, B=10 14.5 vs 12.7, B=12 16.2 vs 13.5)
-}
-
-// The 32x32x16 form of the one-pass kernel (oeh_attn_wide.hip): plain softmax / softmax_1, 16-bit storage, head dim 64, masks none |
-// causal, gate values only.  Behind the diagnostic hook (oeh_debug_set_variant bit 12) until it is measured ahead.
-bool wide_eligible(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
-#ifndef OEH_WITH_WIDE
-  return false;  // the candidate is not part of the production library (csrc/Makefile: `make experiment` builds it in)
-#endif
-  if (!g_wide || d->D != 64 || (d->dtype != OEH_F16 && d->dtype != OEH_BF16) || want_out32(d)) return false;
-  if (d->clip || any_fq(fq) || d->key_pad_mask != nullptr || d->full_mask != nullptr || (d->gate == nullptr && d->gate_hidden != nullptr)) return false;
-  return d->Sq > 64;
-}
-
 // INT8 storage (oeh_attn_i8.hip): see include/oeh.h, oeh_attn_desc.q_grid
 bool i8_eligible(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq) {
   if (d->dtype != OEH_I8 || d->D != 64 || d->Sk > 512 || (d->Sk & 15) != 0) return false;
@@ -303,7 +236,7 @@ bool i8_eligible(const oeh_attn_desc* d, const void* q, const void* k, const voi
   if (fq->probs.zero_point != std::nearbyint(fq->probs.zero_point) || fq->scores.zero_point != std::nearbyint(fq->scores.zero_point)) return false;
   const bool dumps = fq->scores.dump_idx != nullptr || fq->probs.dump_idx != nullptr || fq->ctx.dump_idx != nullptr;
   if (dumps && d->o_dtype != OEH_F32) return false;  // the index dumps (tests) exist in the fp32-output form
-  if ((d->clip && d->gamma > 0.0f) || d->full_mask != nullptr || (d->gate == nullptr && d->gate_hidden != nullptr)) return false;
+  if ((d->clip && d->gamma > 0.0f) || d->full_mask != nullptr || gate_in_kernel(d)) return false;
   if (d->key_pad_mask != nullptr && !(d->mask_min < -1.0e4f)) return false;  // (a key-padding vector of 0 / <= -1e4 entries: include/oeh.h)
   if (d->scale_div != 0.0f ? !(d->scale_div > 0.0f && std::isfinite(d->scale_div)) : !(d->scale > 0.0f && std::isfinite(d->scale))) return false;
   if (d->causal && (d->Sq > d->Sk || !(d->mask_min < -1.0e4f))) return false;
@@ -315,27 +248,94 @@ bool i8_eligible(const oeh_attn_desc* d, const void* q, const void* k, const voi
   return true;
 }
 
-Variant pick_variant(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq) {
+// ---- What MEASURED faster, among the kernels that can run a problem (16-bit and fp32 storage share every rule; HOOK_FORCE_FLASH
+// lifts the ones on the one-pass kernel)
+
+// The plain one-pass form against the full-row kernel on rows of <= 128 keys (never with a (B,1,Sq,Sk) mask: those rows have > 512 keys).
+bool prefer_full_row_short(const oeh_attn_desc* d) {
+  // short rows (<= 128 keys) fit the full-row kernel's registers in one pass, which measures faster there (BERT-base B=32 S=128:
+  // 7.7 vs 9.7 us per launch) - until the batch is large enough for the one-pass kernel's 128-row workgroups to fill the chip by
+  // themselves (>= 768 of them): then its halved K / V streaming wins (H=12 S=128, round 3: B=48 12.3 vs 13.0 us, B=64 15.5 vs 14.5,
+  // B=96 23.0 vs 20.3, B=128 31.5 vs 24.2)
+  // fp32 storage, rows of <= 128 keys: the full-row kernel's fp32 form where it applies, at every batch size measured (round 3, H=12 S=128: B=32 16.5
+  // vs 20.0 us, B=64 29.8 vs 30.6, B=128 54.6 vs 57.7); what it does not take stays here (16.7 us in the general kernel)
+  // (with >= 768 of its 128-row workgroups the one-pass form is ahead again: B=64 25.8 vs 30.5 us; with a padding vector 30.5 vs 31.5 -
+  // round 4: one rule for both, profiles/r04_dispatch_ab.txt)
+  if (d->full_mask != nullptr || d->Sk > 128 || (g_hooks.off & HOOK_FORCE_FLASH)) return false;
+  const long wgs = (long)d->B * d->H * ((d->Sq + 127) / 128);
+  // (one threshold for every head dim since round 4: at d = 32 and 768 workgroups the one-pass kernel measured 10.0 vs 11.0 us, at
+  // 1536 16.7 vs 21.8 - the separate d <= 32 threshold of 1536 was the wrong way round on the re-measurement)
+  return !(d->Sk > 64 && d->Sq >= 112 && wgs >= 768);
+}
+
+// ... and on causal rows whose count leaves the last 128-row workgroup at most half full, up to 384 keys
+bool prefer_full_row_causal_tail(const oeh_attn_desc* d) {
+  // causal rows whose count leaves the last 128-row workgroup at most half full (S = 192, 320, 448): the full-row kernel's 64-row
+  // workgroups waste nothing there (16.9 vs 18.3, 15.7 vs 17.1, 18.7 vs 19.4 us); without the causal mask the one-pass kernel keeps its lead
+  // (round 4, profiles/r04_dispatch_ab.txt - both sides of every rule in one process: S = 192 4.8 %, S = 320 3.1 % for the full-row kernel,
+  // S = 448 a tie (18.3 vs 18.2 us): the rule ends at 384 keys, like its fp32 twin below)
+  // fp32 storage: causal rows that leave the last 128-row workgroup at most half full, up to 320 rows (S = 192: 33.1 vs 40.3 us, S = 320: 38.4 vs
+  // 39.0; S = 448: 42.9 vs 42.2 - the one-pass kernel again)
+  if (d->full_mask != nullptr || (g_hooks.off & HOOK_FORCE_FLASH)) return false;
+  return d->causal && d->Sk <= 384 && d->Sq > 128 && ((d->Sq - 1) % 128) < 64;
+}
+
+// The two-pass forms of the one-pass kernel on rows of MORE than 512 keys.  Up to 512 keys the full-row kernel computes the scores once
+// and is the faster one - except the clipped softmax at head dim 128 from 384 keys.
+bool prefer_two_pass(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
+  const bool forced = (g_hooks.off & HOOK_FORCE_FLASH) != 0;
+  if (any_fq(fq)) return d->Sk > 512 || forced;
+  return d->Sk > 512 || (d->D == 128 && d->Sk >= 384 && d->full_mask == nullptr) || (forced && d->full_mask == nullptr);  // (d = 128, S = 512: 47.4 vs 58.2 us in the full-row kernel, causal 38.1 vs 41.2)
+}
+
+// head dim 128: the full-row kernel fits ONE workgroup per CU (16-KB tiles), and with the clip or the INT8 chain on top the general
+// kernel - smaller workgroups of its own - measures faster (round 3, B=16 H=8 S=512 causal: INT8 44.6 vs 39.8 us, clipped 41.2 vs 39.7;
+// S=256 clipped 30.3 vs 25.0); the plain softmax stays on the one-pass / full-row kernels
+bool prefer_general_d128(const oeh_attn_desc* d, const oeh_fq_desc* fq) {
+  return !(g_hooks.off & HOOK_NO_D128_RULE) && d->D == 128 && d->dtype != OEH_F32 && (any_fq(fq) || d->clip) && d->key_pad_mask == nullptr && !gate_in_kernel(d);
+}
+
+// A wave per problem only pays when there are enough problems to fill the chip, on fp32 data - where it also is the EXACT path (fp32
+// matrix-core products: 3e-6 of the reference; the operand-pair kernels round the probability operand to fp16) - and on rows of at
+// most 32 keys: measured, round 3 (d = 64, against the full-row kernel's fp32 form): B*H = 896 S = 28 9.4 vs 8.9 us (kept here: STanHop's
+// shape, the exact path), B*H = 1536 S = 32 13.3 vs 13.7, but S = 48 29.8 vs 20.2 and S = 64 37.0 vs 22.7; 16-bit data: S = 28 8.3 vs 8.05
+// in the full-row kernel, S = 48 18.6 vs 6.6, S = 64 19.9 vs 7.1 - or when no matrix-core kernel takes the shape (d = 16)
+bool prefer_small(const oeh_attn_desc* d) {
+  return (g_hooks.off & HOOK_FORCE_SMALL) || d->D == 16 || !(d->dtype != OEH_F32 || d->Sk > 32 || d->Sq > 32 || (long)d->B * d->H < 256);
+}
+
+// query blocks (16 rows) per wave of the one-pass kernel: 2 (128-row workgroups) once that still gives every CU two
+// workgroups, else 1
+int flash_mq(const oeh_attn_desc* d, bool pv2) {
+  // the probability pairs with key padding / a (B,1,Sq,Sk) mask at head dim 64: one block per wave (two spill - the fp32 forms with padding are
+  // at the register file's edge already; oeh_attn_flash.inl instantiates only this one)
+  if (pv2 && d->D == 64 && (d->key_pad_mask != nullptr || d->full_mask != nullptr)) return 1;
+  if (g_hooks.flash_mq != 0 && !(d->D == 128 && d->dtype == OEH_F32)) return g_hooks.flash_mq;
+  if (d->D == 128 && d->dtype == OEH_F32) return 1;  // two blocks of fp32 operand pairs at d = 128 do not fit the register file (130 spills)
+  const long wg2 = (long)((d->Sq + 127) / 128) * d->B * d->H;
+  return (d->Sq > 64 && wg2 >= 416) ? 2 : 1;  // (H=12 S=512 causal: B=8 - 384 workgroups - 10.8 vs 12.4 us with one block per wave, B=9 - 432 - 13.3 vs 12.8, B=10 14.5 vs 12.7, B=12 16.2 vs 13.5)
+}
+
+Variant pick_variant(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq, bool out32) {
   if (d->dtype == OEH_I8) return i8_eligible(d, q, k, v, o, fq) ? V_I8 : V_NONE;
   const int eb = elem_bytes(d->dtype);
-  const bool shape_ok = (d->D == 32 || d->D == 64 || d->D == 128) && d->Sk <= 512;
+  const bool f32 = d->dtype == OEH_F32;
+  const bool d_ok = d->D == 32 || d->D == 64 || d->D == 128;
+  const bool shape_ok = d_ok && d->Sk <= 512;
   // integer-valued (idx - zp) must be exact in the 16-bit P operand: |.| <= 2048 (f16) / 256 (bf16)
   bool p_exact = true;
   if (fq != nullptr && fq->probs.enable) p_exact = fq->probs.qmax <= (d->dtype == OEH_BF16 ? 255.0f : 2047.0f);
   const bool al = (q == nullptr) || (aligned16(q, d->q_stride, eb) && aligned16(k, d->k_stride, eb) &&
-                                     aligned16(v, d->v_stride, eb) && aligned16(o, d->o_stride, want_out32(d) ? 4 : eb));
-  const bool d_ok = d->D == 32 || d->D == 64 || d->D == 128;
-  if (small_eligible(d, q, k, v, o, fq) && !(g_variant_off & (1 << V_SMALL))) return V_SMALL;
-  if (d_ok && al && flash_eligible(d, fq) && !(g_variant_off & (1 << V_FLASH))) return V_FLASH;
-  if (d_ok && al && flash32_eligible(d, fq) && !(g_variant_off & ((1 << V_FLASH) | (1 << 6)))) return V_FLASH;
-  if (d_ok && al && flash_fq_eligible(d, fq) && !(g_variant_off & ((1 << V_FLASH) | (d->dtype == OEH_F32 ? (1 << 6) : 0)))) return V_FLASH;
-  if (d_ok && al && flash_clip_eligible(d, fq) && !(g_variant_off & ((1 << V_FLASH) | (d->dtype == OEH_F32 ? (1 << 6) : 0)))) return V_FLASH;
-  // head dim 128: the full-row kernel fits ONE workgroup per CU (16-KB tiles), and with the clip or the INT8 chain on top the general
-  // kernel - smaller workgroups of its own - measures faster (round 3, B=16 H=8 S=512 causal: INT8 44.6 vs 39.8 us, clipped 41.2 vs 39.7;
-  // S=256 clipped 30.3 vs 25.0); the plain softmax stays on the one-pass / full-row kernels
-  const bool d128_general = !g_no_d128_rule && d->D == 128 && d->dtype != OEH_F32 && (any_fq(fq) || d->clip) && d->key_pad_mask == nullptr && !(d->gate == nullptr && d->gate_hidden != nullptr);
-  if (shape_ok && p_exact && al && fast_eligible(d, fq) && !d128_general && !(g_variant_off & (1 << V_FAST))) return V_FAST;
-  if (shape_ok && p_exact && al && fast32_eligible(d, fq) && !(g_variant_off & ((1 << V_FAST) | (1 << 7)))) return V_FAST;
+                                     aligned16(v, d->v_stride, eb) && aligned16(o, d->o_stride, out32 ? 4 : eb));
+  const int off = g_hooks.off;
+  if (small_can(d, q, k, v, o, fq) && prefer_small(d) && !(off & (1 << V_SMALL))) return V_SMALL;
+  if (d_ok && al && !(off & ((1 << V_FLASH) | (f32 ? HOOK_NO_FLASH_F32 : 0)))) {
+    if (flash_can(d, fq, f32) && !prefer_full_row_short(d) && !prefer_full_row_causal_tail(d)) return V_FLASH;
+    if (flash_two_pass_can(d, fq) && prefer_two_pass(d, fq)) return V_FLASH;
+  }
+  // fp32 storage on the full-row kernel: clipped softmax, the INT8 chain, vanilla softmax with key padding (the in-kernel gate predictor: on
+  // operand pairs here - fast_can refuses it together with fake-quant)
+  if (shape_ok && p_exact && al && fast_can(d, fq, f32) && !prefer_general_d128(d, fq) && !(off & ((1 << V_FAST) | (f32 ? HOOK_NO_FAST_F32 : 0)))) return V_FAST;
   if (shape_ok && p_exact && al) return V_MFMA;
   if ((size_t)(d->D + d->Sk) * 4 <= 64 * 1024) return V_GENERIC;
   return V_NONE;
@@ -361,7 +361,7 @@ void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const voi
   P.full_sb = d->full_mask_stride[0]; P.full_sq = d->full_mask_stride[1];
   P.causal = d->causal ? 1 : 0; P.clamp_min = d->clamp_min ? 1 : 0; P.mask_min = d->mask_min;
   P.gate = d->gate; P.gs_b = d->gate_stride[0]; P.gs_h = d->gate_stride[1]; P.gs_s = d->gate_stride[2];
-  if (d->gate == nullptr && d->gate_hidden != nullptr) {
+  if (gate_in_kernel(d)) {
     P.gh = d->gate_hidden; P.ghs_b = d->gate_hidden_stride[0]; P.ghs_t = d->gate_hidden_stride[1];
     P.gw1 = d->gate_w1; P.gb1 = d->gate_b1; P.gw2 = d->gate_w2; P.gb2 = d->gate_b2;
     P.g_units = d->gate_units; P.g_scaling = d->gate_scaling; P.g_out = d->gate_out;
@@ -371,9 +371,9 @@ void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const voi
     P.ctx_before_gate = fq->ctx_quant_before_gate ? 1 : 0;
     if (fq->ctx_emit_index) P.fq_c.oscale = 1.0f;  // (validate(): the context quantiser is the last op)
   }
-  P.stamps = g_stamps;
-  P.snake = (g_place & 1) ? 0 : 1;
-  P.head_major = g_head_group;
+  P.stamps = g_hooks.stamps;
+  P.snake = (g_hooks.off & HOOK_PLAIN_ORDER) ? 0 : 1;
+  P.head_major = g_hooks.head_group;
   P.nQT = (d->Sq + 63) / 64;
   P.nBH = d->B * d->H;
   P.nBHpad = (P.nBH + 7) & ~7;
@@ -389,162 +389,133 @@ void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const voi
                std::isfinite(d->mask_min) && d->mask_min < -1e4f) ? 1 : 0;
 }
 
-const char* variant_name(Variant v, const oeh_attn_desc* d, bool fq, bool pv2 = false) {
-  static thread_local char buf[64];
-  if (v == V_GENERIC) return "generic";
-  if (v == V_I8) {
-    std::snprintf(buf, sizeof(buf), "i8mfma/NT%d/D64/%s", d->Sk <= 128 ? 8 : (d->Sk <= 256 ? 16 : 32),
-                  d->o_dtype == OEH_F16 ? "f16" : (d->o_dtype == OEH_BF16 ? "bf16" : (d->o_dtype == OEH_I8 ? "i8" : "f32")));
-    return buf;
+// Everything oeh_attn_fwd[_ex] decides before it launches, and what oeh_attn_variant[_ex] print
+struct AttnPlan {
+  int rc;       // OEH_OK, or the refusal (OEH_EINVAL / OEH_ENOTSUP / OEH_EALIGN)
+  Variant var;
+  int mq;       // one-pass kernel: query blocks per wave (AttnParams.nQT follows; the launch ladder's MQ)
+  int src32;    // AttnParams.src32: fp32 storage read directly, fp32 output (1), with the probability pairs (2)
+  int out32;    // AttnParams.out32: 16-bit storage with the output taken from the fp32 accumulators (include/oeh.h: o_dtype)
+  int pv2;      // the probability pairs are on (include/oeh.h: oeh_attn_opts.pv_pairs)
+  int nt;       // 16-key tiles of a full row, as the names print it
+};
+
+// The checks in the order the ABI promises (the first refusal wins).  name_only (oeh_attn_variant[_ex], host only: q .. o are null):
+// the sizes / dtype / option words instead of validate(), and the plan ends with the variant - a name exists also where steps 5 - 6 refuse.
+AttnPlan plan_attn(const oeh_attn_desc* d, const oeh_attn_opts* opts, const void* q, const void* k, const void* v, void* o,
+                   const oeh_fq_desc* fq, bool name_only) {
+  AttnPlan pl = {};
+  // 1 - 3. reserved option words (before any other check), the descriptor, what the probability pairs do not cover
+  if (opts != nullptr && (opts->reserved[0] != 0 || opts->reserved[1] != 0 || opts->reserved[2] != 0)) pl.rc = OEH_EINVAL;
+  else pl.rc = name_only ? (desc_sane(d, true, true) ? OEH_OK : OEH_EINVAL) : validate(d, q, k, v, o, fq);
+  if (pl.rc != OEH_OK) return pl;
+  if (opts != nullptr && opts->pv_pairs != 0) {
+    if (d->dtype != OEH_F32 || any_fq(fq) || gate_in_kernel(d)) { pl.rc = OEH_ENOTSUP; return pl; }
+    pl.pv2 = 1;
   }
-  if (v == V_SMALL) {
-    std::snprintf(buf, sizeof(buf), "small/ST%d/D%d/%s", d->Sk <= 32 ? 2 : 4, d->D, d->dtype == OEH_F16 ? "f16" : (d->dtype == OEH_BF16 ? "bf16" : "f32"));
-    return buf;
-  }
-  if (v == V_NONE) return nullptr;
-  const int nt = d->Sk <= 128 ? 8 : (d->Sk <= 256 ? 16 : 32);
-  const char* dt = d->dtype == OEH_F16 ? "f16" : (d->dtype == OEH_BF16 ? "bf16" : "f32");
-  if (v == V_FLASH && wide_eligible(d, nullptr) && !fq) std::snprintf(buf, sizeof(buf), "flash16w/D%d/%s", d->D, dt);
-  else if (v == V_FLASH) std::snprintf(buf, sizeof(buf), "flash16/MQ%d/D%d/%s%s%s", flash_mq(d, pv2), d->D, dt, fq ? "/fq2p" : (d->clip ? "/clip2p" : ""), pv2 ? "+pv2" : "");
-  else if (v == V_FAST) std::snprintf(buf, sizeof(buf), "fast16/NT%d/D%d/%s%s%s%s", nt, d->D, dt, d->clip ? "/clip" : "", fq ? "/fq" : "", pv2 ? "+pv2" : "");
-  else std::snprintf(buf, sizeof(buf), "mfma16/NT%d/D%d/%s%s", nt, d->D, dt, fq ? "/fq" : "");
-  return buf;
-}
-
-// oeh_attn_opts (include/oeh.h): OEH_EINVAL for reserved words, OEH_ENOTSUP for what the probability pairs do not cover; pv2 = the pairs are on
-int attn_opts(const oeh_attn_desc* d, const oeh_attn_opts* opts, const oeh_fq_desc* fq, bool& pv2) {
-  pv2 = false;
-  if (opts == nullptr) return OEH_OK;
-  if (opts->reserved[0] != 0 || opts->reserved[1] != 0 || opts->reserved[2] != 0) return OEH_EINVAL;
-  if (opts->pv_pairs == 0) return OEH_OK;
-  if (d == nullptr) return OEH_EINVAL;
-  if (d->dtype != OEH_F32 || any_fq(fq) || (d->gate == nullptr && d->gate_hidden != nullptr)) return OEH_ENOTSUP;
-  pv2 = true;
-  return OEH_OK;
-}
-
-// With the probability pairs, a problem the general kernel would take (its fp32 form rounds P to one fp16 operand) goes to the any-shape
-// kernel (fp32 FMA); the one-pass and full-row kernels run their PV2 forms, the small-shape kernel is fp32-exact as it is.
-Variant pick_variant_pv(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq, bool pv2) {
-  const Variant var = pick_variant(d, q, k, v, o, fq);
-  if (!pv2 || var != V_MFMA) return var;
-  return (size_t)(d->D + d->Sk) * 4 <= 64 * 1024 ? V_GENERIC : V_NONE;
-}
-
-int attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq, void* stream, bool pv2) {
-  int rc = validate(desc, q, k, v, o, fq);
-  if (rc != OEH_OK) return rc;
-  const Variant var = pick_variant_pv(desc, q, k, v, o, fq, pv2);
-  if (var == V_NONE) return OEH_ENOTSUP;
-  if (desc->gate == nullptr && desc->gate_hidden != nullptr) {  // fused gate predictor: 16-bit MFMA variants, 16-B aligned rows
+  // 4. the variant.  With the probability pairs, a problem the general kernel would take (its fp32 form rounds P to one fp16 operand) goes to
+  // the any-shape kernel (fp32 FMA); the one-pass and full-row kernels run their PV2 forms, the small-shape kernel is fp32-exact as it is.
+  pl.out32 = (d->dtype == OEH_F16 || d->dtype == OEH_BF16) && d->o_dtype == OEH_F32;
+  pl.var = pick_variant(d, q, k, v, o, fq, pl.out32);
+  if (pl.pv2 && pl.var == V_MFMA) pl.var = (size_t)(d->D + d->Sk) * 4 <= 64 * 1024 ? V_GENERIC : V_NONE;
+  if (pl.var == V_NONE) { pl.rc = OEH_ENOTSUP; return pl; }
+  const bool matrix16 = pl.var == V_FLASH || pl.var == V_FAST;
+  pl.src32 = (d->dtype == OEH_F32 && matrix16) ? (pl.pv2 ? 2 : 1) : 0;
+  pl.nt = d->Sk <= 128 ? 8 : (d->Sk <= 256 ? 16 : 32);
+  pl.mq = pl.var == V_FLASH ? flash_mq(d, pl.pv2) : 0;  // 7. (before 5 - 6: the names print it, and the fp32-output rule reads it)
+  if (name_only) return pl;
+  // 5. fused gate predictor: 16-bit MFMA variants, 16-B aligned rows
+  if (gate_in_kernel(d)) {
     // up to four 16-unit MFMA tiles of hidden units; fp32 storage: the full-row kernel's operand-pair form only
-    if ((var != V_FAST && var != V_FLASH) || desc->gate_units > 64 || (desc->dtype == OEH_F32 && var != V_FAST)) return OEH_ENOTSUP;
-    const int geb = desc->dtype == OEH_F32 ? 4 : 2;
-    if (((reinterpret_cast<uintptr_t>(desc->gate_hidden) | (uintptr_t)(desc->gate_hidden_stride[0] * geb) | (uintptr_t)(desc->gate_hidden_stride[1] * geb)) & 15) != 0) return OEH_EALIGN;
-    if (desc->gate_hidden_stride[1] <= 0 || desc->gate_hidden_stride[1] >= (1 << 24)) return OEH_ENOTSUP;  // (32-bit lane offsets of the input rows' LDS-DMA)
+    if (!matrix16 || d->gate_units > 64 || (d->dtype == OEH_F32 && pl.var != V_FAST)) { pl.rc = OEH_ENOTSUP; return pl; }
+    const int geb = d->dtype == OEH_F32 ? 4 : 2;
+    if (((reinterpret_cast<uintptr_t>(d->gate_hidden) | (uintptr_t)(d->gate_hidden_stride[0] * geb) | (uintptr_t)(d->gate_hidden_stride[1] * geb)) & 15) != 0) { pl.rc = OEH_EALIGN; return pl; }
+    if (d->gate_hidden_stride[1] <= 0 || d->gate_hidden_stride[1] >= (1 << 24)) { pl.rc = OEH_ENOTSUP; return pl; }  // (32-bit lane offsets of the input rows' LDS-DMA)
   }
-  AttnParams P;
-  fill_params(P, desc, q, k, v, o, fq);
-  P.src32 = (desc->dtype == OEH_F32 && (var == V_FLASH || var == V_FAST)) ? (pv2 ? 2 : 1) : 0;  // fp32 storage read directly, fp32 output
-  if (want_out32(desc)) {
+  // 6. fp32 output
+  if (pl.out32) {
     // the accumulators themselves - sibling instantiations (O32) of what the 16-bit workloads of BASELINE.json run.  Head dim 64: the one-pass
     // kernel's plain form with masks none / causal / key padding / a (B,1,Sq,Sk) mask, or with the in-kernel gate predictor (not both);
     // the full-row kernel's plain and clipped forms (+ key padding), the plain form with the in-kernel gate predictor.  Head dim 128
     // (round 5): the plain forms of both (one block per wave in the one-pass kernel), gate values only.
-    const bool gated_in_kernel = desc->gate == nullptr && desc->gate_hidden != nullptr;
-    const bool masked = desc->key_pad_mask != nullptr || desc->full_mask != nullptr;
-    bool ok = !any_fq(fq);
-    if (desc->D == 64) {
-      if (var == V_FLASH) ok = ok && !desc->clip && !(masked && gated_in_kernel);
-      else if (var == V_FAST) ok = ok && !(desc->clip && gated_in_kernel);
-      else ok = false;
-    } else if (desc->D == 128) {
-      ok = ok && !desc->clip && !gated_in_kernel && ((var == V_FLASH && !masked && flash_mq(desc) == 1) || var == V_FAST);
-    } else {
-      ok = false;
-    }
-    if (!ok) return OEH_ENOTSUP;
-    P.out32 = 1;
+    const bool masked = d->key_pad_mask != nullptr || d->full_mask != nullptr;
+    bool ok = !any_fq(fq) && matrix16;
+    if (d->D == 64) ok = ok && (pl.var == V_FLASH ? !d->clip && !(masked && gate_in_kernel(d)) : !(d->clip && gate_in_kernel(d)));
+    else if (d->D == 128) ok = ok && !d->clip && !gate_in_kernel(d) && (pl.var == V_FAST || (!masked && pl.mq == 1));
+    else ok = false;
+    if (!ok) pl.rc = OEH_ENOTSUP;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (var == V_SMALL) return oeh::launch_attn_small(P, desc->dtype, st);
-  if (var == V_I8) {
-    const double mult = desc->scale_div != 0.0f ? 1.0 / (double)desc->scale_div : (double)desc->scale;
-    P.i8_cq = 128 - (int)desc->q_grid.zero_point; P.i8_ck = 128 - (int)desc->k_grid.zero_point;
-    P.i8_cv = 128 - (int)desc->v_grid.zero_point; P.i8_cp = 128 - (int)fq->probs.zero_point;
-    P.i8_k1 = (float)((double)desc->q_grid.scale * (double)desc->k_grid.scale * mult / (double)fq->scores.scale);
-    P.i8_so = (float)((double)fq->probs.scale * (double)desc->v_grid.scale);
-    P.nBHpad = (P.nBH + 15) & ~15;  // head pairs on one XCD (oeh_attn_i8.hip)
-    P.magic_nbh = (unsigned)(0x100000000ULL / (unsigned long long)P.nBHpad);
-    return oeh::launch_attn_i8(P, desc->o_dtype, st);
-  }
-  if (var == V_FLASH) {
-    if (desc->scale_div != 0.0f) { P.scale = 1.0f / desc->scale_div; P.scale_div = 0.0f; }  // (fast_eligible: exact for a power of two)
-#ifdef OEH_WITH_WIDE
-    if (wide_eligible(desc, fq)) {
-      P.nQT = (desc->Sq + 127) / 128;
-      return oeh::launch_attn_wide(P, desc->dtype, st);
-    }
-#endif
-    const int mq = flash_mq(desc, pv2);
-    P.nQT = (desc->Sq + 64 * mq - 1) / (64 * mq);
-    switch (desc->D) {
-      case 32: return oeh::launch_attn_flash_d32(P, desc->dtype, mq, st);
-      case 64: return oeh::launch_attn_flash_d64(P, desc->dtype, mq, st);
-      default: return oeh::launch_attn_flash_d128(P, desc->dtype, mq, st);
-    }
-  }
-  if (var == V_FAST) {
-    if (desc->scale_div != 0.0f) { P.scale = 1.0f / desc->scale_div; P.scale_div = 0.0f; }  // (fast_eligible: exact for a power of two)
-    switch (desc->D) {
-      case 32: return oeh::launch_attn_fast_d32(P, desc->dtype, st);
-      case 64: return oeh::launch_attn_fast_d64(P, desc->dtype, st);
-      default: return oeh::launch_attn_fast_d128(P, desc->dtype, st);
-    }
-  }
-  if (var == V_MFMA) {
-    switch (desc->D) {
-      case 32: return oeh::launch_attn_mfma_d32(P, desc->dtype, any_fq(fq), st);
-      case 64: return oeh::launch_attn_mfma_d64(P, desc->dtype, any_fq(fq), st);
-      default: return oeh::launch_attn_mfma_d128(P, desc->dtype, any_fq(fq), st);
-    }
-  }
-  return oeh::launch_attn_generic(P, desc->dtype, st);
+  return pl;
 }
+
+const char* variant_name(const AttnPlan& pl, const oeh_attn_desc* d, bool fq) {
+  static thread_local char buf[64];
+  const char* dt = d->dtype == OEH_F16 ? "f16" : (d->dtype == OEH_BF16 ? "bf16" : "f32");
+  const char* pv2 = pl.pv2 ? "+pv2" : "";
+  switch (pl.var) {
+    case V_NONE: return nullptr;
+    case V_GENERIC: return "generic";
+    case V_I8:
+      std::snprintf(buf, sizeof(buf), "i8mfma/NT%d/D64/%s", pl.nt, d->o_dtype == OEH_F16 ? "f16" : (d->o_dtype == OEH_BF16 ? "bf16" : (d->o_dtype == OEH_I8 ? "i8" : "f32")));
+      break;
+    case V_SMALL: std::snprintf(buf, sizeof(buf), "small/ST%d/D%d/%s", d->Sk <= 32 ? 2 : 4, d->D, dt); break;
+    case V_FLASH: std::snprintf(buf, sizeof(buf), "flash16/MQ%d/D%d/%s%s%s", pl.mq, d->D, dt, fq ? "/fq2p" : (d->clip ? "/clip2p" : ""), pv2); break;
+    case V_FAST: std::snprintf(buf, sizeof(buf), "fast16/NT%d/D%d/%s%s%s%s", pl.nt, d->D, dt, d->clip ? "/clip" : "", fq ? "/fq" : "", pv2); break;
+    case V_MFMA: std::snprintf(buf, sizeof(buf), "mfma16/NT%d/D%d/%s%s", pl.nt, d->D, dt, fq ? "/fq" : ""); break;
+  }
+  return buf;
+}
+
+// the head-dim units of a kernel family (D is 32, 64 or 128 here: pick_variant's d_ok)
+#define OEH_LAUNCH_BY_D(family, ...) \
+  (desc->D == 32 ? oeh::launch_attn_##family##_d32(__VA_ARGS__) : desc->D == 64 ? oeh::launch_attn_##family##_d64(__VA_ARGS__) : oeh::launch_attn_##family##_d128(__VA_ARGS__))
 
 }  // namespace
 
 extern "C" {
 
-int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq,
-                 void* stream) {
-  return attn_fwd(desc, q, k, v, o, fq, stream, false);
-}
-
 int oeh_attn_fwd_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const void* q, const void* k, const void* v, void* o,
                     const oeh_fq_desc* fq, void* stream) {
-  bool pv2 = false;
-  if (opts != nullptr && (opts->reserved[0] != 0 || opts->reserved[1] != 0 || opts->reserved[2] != 0)) return OEH_EINVAL;  // (before any other check)
-  const int rc = validate(desc, q, k, v, o, fq);
-  if (rc != OEH_OK) return rc;
-  const int orc = attn_opts(desc, opts, fq, pv2);
-  if (orc != OEH_OK) return orc;
-  return attn_fwd(desc, q, k, v, o, fq, stream, pv2);
+  const AttnPlan pl = plan_attn(desc, opts, q, k, v, o, fq, false);
+  if (pl.rc != OEH_OK) return pl.rc;
+  AttnParams P;
+  fill_params(P, desc, q, k, v, o, fq);
+  P.src32 = pl.src32;
+  P.out32 = pl.out32;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if ((pl.var == V_FLASH || pl.var == V_FAST) && desc->scale_div != 0.0f) { P.scale = 1.0f / desc->scale_div; P.scale_div = 0.0f; }  // (fast_can: exact for a power of two)
+  switch (pl.var) {
+    case V_SMALL: return oeh::launch_attn_small(P, desc->dtype, st);
+    case V_I8: {
+      const double mult = desc->scale_div != 0.0f ? 1.0 / (double)desc->scale_div : (double)desc->scale;
+      P.i8_cq = 128 - (int)desc->q_grid.zero_point; P.i8_ck = 128 - (int)desc->k_grid.zero_point;
+      P.i8_cv = 128 - (int)desc->v_grid.zero_point; P.i8_cp = 128 - (int)fq->probs.zero_point;
+      P.i8_k1 = (float)((double)desc->q_grid.scale * (double)desc->k_grid.scale * mult / (double)fq->scores.scale);
+      P.i8_so = (float)((double)fq->probs.scale * (double)desc->v_grid.scale);
+      P.nBHpad = (P.nBH + 15) & ~15;  // head pairs on one XCD (oeh_attn_i8.hip)
+      P.magic_nbh = (unsigned)(0x100000000ULL / (unsigned long long)P.nBHpad);
+      return oeh::launch_attn_i8(P, desc->o_dtype, st);
+    }
+    case V_FLASH:
+      P.nQT = (desc->Sq + 64 * pl.mq - 1) / (64 * pl.mq);
+      return OEH_LAUNCH_BY_D(flash, P, desc->dtype, pl.mq, st);
+    case V_FAST: return OEH_LAUNCH_BY_D(fast, P, desc->dtype, st);
+    case V_MFMA: return OEH_LAUNCH_BY_D(mfma, P, desc->dtype, any_fq(fq), st);
+    default: return oeh::launch_attn_generic(P, desc->dtype, st);
+  }
 }
 
-const char* oeh_attn_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq) {
-  if (desc == nullptr || desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0 || desc->D <= 0 || (!dtype_ok(desc->dtype) && desc->dtype != OEH_I8))
-    return nullptr;
-  return variant_name(pick_variant(desc, nullptr, nullptr, nullptr, nullptr, fq), desc, any_fq(fq));
+int oeh_attn_fwd(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq,
+                 void* stream) {
+  return oeh_attn_fwd_ex(desc, nullptr, q, k, v, o, fq, stream);
 }
 
 const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const oeh_fq_desc* fq) {
-  bool pv2 = false;
-  if (attn_opts(desc, opts, fq, pv2) != OEH_OK) return nullptr;
-  if (!pv2) return oeh_attn_variant(desc, fq);
-  if (desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0 || desc->D <= 0) return nullptr;
-  return variant_name(pick_variant_pv(desc, nullptr, nullptr, nullptr, nullptr, fq, true), desc, false, true);
+  const AttnPlan pl = plan_attn(desc, opts, nullptr, nullptr, nullptr, nullptr, fq, true);
+  return pl.rc == OEH_OK ? variant_name(pl, desc, any_fq(fq)) : nullptr;
 }
+
+const char* oeh_attn_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq) { return oeh_attn_variant_ex(desc, nullptr, fq); }
 
 int oeh_softmax_rows(const void* x, void* y, int64_t rows, int32_t cols, int32_t dtype, int32_t softmax_base, int32_t clip,
                      float gamma, float eta, void* stream) {
@@ -561,12 +532,8 @@ int oeh_fake_quant(const void* x, void* y, uint8_t* idx, int64_t n, int32_t dtyp
   if (!(scale > 0.0f) || !(qmax >= 1.0f) || zero_point < 0.0f || zero_point > qmax) return OEH_EINVAL;
   if (idx != nullptr && qmax > 255.0f) return OEH_ENOTSUP;
   if (n == 0 || (y == nullptr && idx == nullptr)) return OEH_OK;
-  FqP f;
-  std::memset(&f, 0, sizeof(f));
-  f.en = 1; f.scale = scale; f.rscale = 1.0f / scale; f.zp = zero_point; f.qmax = qmax;
-  f.lo = -zero_point; f.hi = qmax - zero_point;
-  f.c2 = scale_log2e(scale);
-  return oeh::launch_fake_quant(x, y, idx, n, dtype, f, reinterpret_cast<hipStream_t>(stream));
+  const oeh_fq f = {1, scale, zero_point, qmax, nullptr};
+  return oeh::launch_fake_quant(x, y, idx, n, dtype, make_fq(&f), reinterpret_cast<hipStream_t>(stream));
 }
 
 int oeh_gate_fwd(const void* hidden, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t d, int64_t hidden_stride_b,
@@ -602,10 +569,9 @@ int oeh_fake_quant_range(const void* x, void* y, int64_t n, int32_t dtype, const
 int oeh_attn_calibrate(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, float* ctx_out, int32_t which,
                        const double* scores_range, const double* probs_range, int32_t n_bits, double eps, double q_lo, double q_hi,
                        double momentum, int32_t first, double* state, void* work, void* stream) {
-  if (desc == nullptr || q == nullptr || k == nullptr) return OEH_EINVAL;
+  if (q == nullptr || k == nullptr || !desc_sane(desc, false, false)) return OEH_EINVAL;
   if (which < OEH_CALIB_SCORES || which > OEH_CALIB_CONTEXT || n_bits < 1 || n_bits > 16 || !(eps > 0.0)) return OEH_EINVAL;
   if (which == OEH_CALIB_CONTEXT ? (v == nullptr || ctx_out == nullptr) : (state == nullptr || work == nullptr)) return OEH_EINVAL;
-  if (desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0 || !dtype_ok(desc->dtype)) return OEH_EINVAL;
   if (desc->softmax_base != OEH_SOFTMAX_VANILLA && desc->softmax_base != OEH_SOFTMAX_ONE) return OEH_EINVAL;
   if (desc->key_pad_mask != nullptr && desc->key_pad_dtype != OEH_F16 && desc->key_pad_dtype != OEH_F32) return OEH_EINVAL;
   if (desc->full_mask != nullptr && desc->full_mask_dtype != OEH_F16 && desc->full_mask_dtype != OEH_F32) return OEH_EINVAL;
@@ -638,11 +604,9 @@ int oeh_quantize_heads_i8(const void* x, int8_t* out, void* y, int64_t B, int32_
     if (((reinterpret_cast<uintptr_t>(x) | (uintptr_t)(x_stride[0] * eb) | (uintptr_t)(x_stride[1] * eb) | reinterpret_cast<uintptr_t>(bias)) & 15) != 0) return OEH_EALIGN;
   }
   if (y != nullptr && ((reinterpret_cast<uintptr_t>(y) | (uintptr_t)(y_stride[0] * elem_bytes(dtype)) | (uintptr_t)(y_stride[1] * elem_bytes(dtype))) & 15) != 0) return OEH_EALIGN;  // 16-byte value stores
-  FqP f;
-  std::memset(&f, 0, sizeof(f));
-  f.en = 1; f.scale = scale; f.rscale = 1.0f / scale; f.zp = zero_point; f.qmax = 255.0f; f.lo = -zero_point; f.hi = 255.0f - zero_point;
+  const oeh_fq f = {1, scale, zero_point, 255.0f, nullptr};
   return oeh::launch_quantize_heads_i8(x, reinterpret_cast<signed char*>(out), y, B, S, H, x_stride[0], x_stride[1], y != nullptr ? y_stride[0] : 0,
-                                       y != nullptr ? y_stride[1] : 0, dtype, f, transpose ? 1 : 0, alpha, bias, reinterpret_cast<hipStream_t>(stream));
+                                       y != nullptr ? y_stride[1] : 0, dtype, make_fq(&f), transpose ? 1 : 0, alpha, bias, reinterpret_cast<hipStream_t>(stream));
 }
 
 int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* bias, int64_t B, int32_t S, int32_t K, int32_t E, int32_t n_seg,
@@ -671,7 +635,8 @@ int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* 
     t.alpha = g.alpha; t.out = reinterpret_cast<signed char*>(g.out); t.y = g.y; t.y_ld = g.y_stride_row; t.transpose = g.transpose ? 1 : 0;
     t.acc_add = pairs == 3 ? g.acc_add : nullptr;
     if ((reinterpret_cast<uintptr_t>(g.acc_add) & 3) != 0) return OEH_EALIGN;
-    t.f.en = 1; t.f.scale = g.scale; t.f.rscale = 1.0f / g.scale; t.f.zp = g.zero_point; t.f.qmax = 255.0f; t.f.lo = -g.zero_point; t.f.hi = 255.0f - g.zero_point;
+    const oeh_fq f = {1, g.scale, g.zero_point, 255.0f, nullptr};
+    t.f = make_fq(&f);
   }
   return oeh::launch_gemm(P, reinterpret_cast<hipStream_t>(stream));
 }
@@ -697,14 +662,14 @@ static bool debug_hooks_on() {
 }
 int oeh_debug_set_variant(int off_mask, int flash_mq_force) {
   if (!debug_hooks_on()) return OEH_ENOTSUP;
-  g_wide = (off_mask >> 12) & 1;
-  g_variant_off = off_mask & 0xff; g_force_flash = (off_mask >> 8) & 1; g_flash_mq = flash_mq_force; g_place = (off_mask >> 9) & 1; g_force_small = (off_mask >> 10) & 1; g_no_d128_rule = (off_mask >> 11) & 1;
-  { const char* e = std::getenv("OEH_HEAD_GROUP"); g_head_group = e != nullptr ? (std::atoi(e) & ~7) : 0; }
+  g_hooks.off = off_mask & HOOK_ALL;
+  g_hooks.flash_mq = flash_mq_force;
+  { const char* e = std::getenv("OEH_HEAD_GROUP"); g_hooks.head_group = e != nullptr ? (std::atoi(e) & ~7) : 0; }
   return OEH_OK;
 }
 int oeh_debug_set_stamps(void* device_buffer) {
   if (!debug_hooks_on()) return OEH_ENOTSUP;
-  g_stamps = static_cast<unsigned long long*>(device_buffer);
+  g_hooks.stamps = static_cast<unsigned long long*>(device_buffer);
   return OEH_OK;
 }
 

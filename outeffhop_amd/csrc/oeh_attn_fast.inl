@@ -902,69 +902,48 @@ __global__ __launch_bounds__(256, (fast_occupancy<NT, D, SRC32, GATE>())) void o
 }
 #undef OEH_STAMP
 
+// One launch of the ladder below: true = launched.  A combination without a branch returns false (OEH_ENOTSUP in the wrapper): the plan
+// (oeh_api.hip: plan_attn) never selects one, and a future change that does shall not pass for a launch.
+#define OEH_GO(...) (oeh_attn_fast_kernel<NT, D, IN, __VA_ARGS__><<<dim3(grid), dim3(256), 0, st>>>(P), true)
 template <int NT, int D, int IN>
-static void launch_fast_nt_d_in(const AttnParams& P, unsigned grid, hipStream_t st) {
+static bool launch_fast_nt_d_in(const AttnParams& P, unsigned grid, hipStream_t st) {
   const bool gate = P.gh != nullptr;
   const bool fqon = P.fq_s.en && P.fq_p.en;
   const bool grid_chain = fqon && (P.pad == nullptr || P.pad_bool);  // FQ == 1, or 3 with a key-padding vector (include/oeh.h: key_pad_boolean)
   const bool grid_pad = grid_chain && P.pad != nullptr;
-  if (P.src32) {  // fp32 storage read directly, fp32 output
+  if (P.src32) {  // fp32 storage read directly, fp32 output (AttnPlan.src32: only with f32 storage, IN_F16)
     if constexpr (IN == IN_F16) {
-      if (P.src32 == 2) {  // PV2: the probability pairs (oeh_api.hip refuses fake-quant and the in-kernel gate predictor with them)
-        if (P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 0, true, false, true>), dim3(grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 0, true, false, true>), dim3(grid), dim3(256), 0, st, P);
-        return;
-      }
-      if (grid_pad && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 3, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (grid_pad) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 3, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (grid_chain && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 1, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (grid_chain) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 1, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (fqon && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 2, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (fqon) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 2, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (P.clip && gate) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, true, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (gate) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, true, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 0, true>), dim3(grid), dim3(256), 0, st, P);
+      // PV2: the probability pairs (AttnPlan.pv2 excludes fake-quant and the in-kernel gate predictor)
+      if (P.src32 == 2) return P.clip ? OEH_GO(true, false, 0, true, false, true) : OEH_GO(false, false, 0, true, false, true);
+      if (grid_pad) return P.clip ? OEH_GO(true, false, 3, true) : OEH_GO(false, false, 3, true);
+      if (grid_chain) return P.clip ? OEH_GO(true, false, 1, true) : OEH_GO(false, false, 1, true);
+      if (fqon) return P.clip ? OEH_GO(true, false, 2, true) : OEH_GO(false, false, 2, true);
+      if (P.clip) return gate ? OEH_GO(true, true, 0, true) : OEH_GO(true, false, 0, true);
+      return gate ? OEH_GO(false, true, 0, true) : OEH_GO(false, false, 0, true);
     }
-    return;
+    return false;
   }
-  if (fqon) {
-    if (grid_pad && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 3>), dim3(grid), dim3(256), 0, st, P);
-    else if (grid_pad) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 3>), dim3(grid), dim3(256), 0, st, P);
-    else if (grid_chain && P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 1>), dim3(grid), dim3(256), 0, st, P);
-    else if (grid_chain) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 1>), dim3(grid), dim3(256), 0, st, P);
-    else if (P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 2>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 2>), dim3(grid), dim3(256), 0, st, P);
-    return;
-  }
-  if constexpr (D == 64) {  // (oeh_api.hip: the out32 rule - head dim 64: plain, clipped, plain + the in-kernel gate predictor)
-    if (P.out32) {
-      if (P.clip) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (gate) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, true, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
-      else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
-      return;
+  if (grid_pad) return P.clip ? OEH_GO(true, false, 3) : OEH_GO(false, false, 3);
+  if (grid_chain) return P.clip ? OEH_GO(true, false, 1) : OEH_GO(false, false, 1);
+  if (fqon) return P.clip ? OEH_GO(true, false, 2) : OEH_GO(false, false, 2);
+  if (P.out32) {  // (AttnPlan.out32, plan_attn step 6)
+    if constexpr (D == 64) {  // head dim 64: plain, clipped, plain + the in-kernel gate predictor
+      if (P.clip) return OEH_GO(true, false, 0, false, true);
+      return gate ? OEH_GO(false, true, 0, false, true) : OEH_GO(false, false, 0, false, true);
     }
+    if constexpr (D == 128) return OEH_GO(false, false, 0, false, true);  // head dim 128: the plain form
+    return false;
   }
-  if constexpr (D == 128) {  // (head dim 128: the plain form)
-    if (P.out32) {
-      hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
-      return;
-    }
-  }
-  if (P.clip) {
-    if (gate) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, true>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, true, false>), dim3(grid), dim3(256), 0, st, P);
-  } else {
-    if (gate) hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, true>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_fast_kernel<NT, D, IN, false, false>), dim3(grid), dim3(256), 0, st, P);
-  }
+  if (P.clip) return gate ? OEH_GO(true, true) : OEH_GO(true, false);
+  return gate ? OEH_GO(false, true) : OEH_GO(false, false);
 }
+#undef OEH_GO
 
 template <int NT, int D>
 static int launch_fast_nt_d(const AttnParams& P, int in, hipStream_t st) {
   const unsigned grid = (unsigned)(P.nQT * P.nBHpad);
-  if (in == IN_BF16) launch_fast_nt_d_in<NT, D, IN_BF16>(P, grid, st);
-  else launch_fast_nt_d_in<NT, D, IN_F16>(P, grid, st);
+  const bool launched = in == IN_BF16 ? launch_fast_nt_d_in<NT, D, IN_BF16>(P, grid, st) : launch_fast_nt_d_in<NT, D, IN_F16>(P, grid, st);
+  if (!launched) return -95;  // OEH_ENOTSUP
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

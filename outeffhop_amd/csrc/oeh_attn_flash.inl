@@ -1123,71 +1123,52 @@ __global__ __launch_bounds__(256, (flash_occupancy<D, MQ, SRC32>())) void oeh_at
 }
 #undef OEH_STAMP
 
+// One launch of the ladder below: true = launched.  A combination without a branch returns false (OEH_ENOTSUP in the wrapper): the plan
+// (oeh_api.hip: plan_attn) never selects one, and a future change that does shall not pass for a launch.
+#define OEH_GO(...) (oeh_attn_flash_kernel<D, IN, MQ, __VA_ARGS__><<<dim3(grid), dim3(256), 0, st>>>(P), true)
 template <int D, int MQ, int IN>
-static void launch_flash_d_mq_in(const AttnParams& P, unsigned grid, hipStream_t st) {
+static bool launch_flash_d_mq_in(const AttnParams& P, unsigned grid, hipStream_t st) {
   const bool pad = P.pad != nullptr || P.full != nullptr, gate = P.gh != nullptr;  // (the PAD variants also serve a (B,1,Sq,Sk) mask)
-  if (P.src32) {  // fp32 storage read directly, fp32 output; no in-kernel gate predictor on this path
-    if constexpr (IN == IN_F16 && !(D == 128 && MQ == 2)) {  // (d = 128 with two blocks per wave: never selected, oeh_api.hip: flash_mq)
-      if (P.src32 == 2) {  // PV2: the probability pairs (oeh_api.hip refuses the fake-quant chain with them)
-        if constexpr (!(D == 64 && MQ == 2)) {  // (d = 64 with padding: one block per wave, oeh_api.hip: flash_mq)
-          if (P.clip && pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 1, false, true>), dim3(grid), dim3(256), 0, st, P);
-          else if (pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
+  if (P.src32) {  // fp32 storage read directly, fp32 output; no in-kernel gate predictor on this path (AttnPlan.src32: only with f32 storage, IN_F16)
+    if constexpr (IN == IN_F16 && !(D == 128 && MQ == 2)) {  // (d = 128 with two blocks per wave: AttnPlan.mq is 1 there, flash_mq)
+      if (P.src32 == 2) {  // PV2: the probability pairs (AttnPlan.pv2 excludes the fake-quant chain)
+        if constexpr (!(D == 64 && MQ == 2)) {  // (d = 64 with padding: AttnPlan.mq is 1, flash_mq)
+          if (pad) return P.clip ? OEH_GO(true, false, true, 1, false, true) : OEH_GO(true, false, true, 0, false, true);
         }
-        if (P.clip && !pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 1, false, true>), dim3(grid), dim3(256), 0, st, P);
-        else if (!pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 0, false, true>), dim3(grid), dim3(256), 0, st, P);
-        return;
+        if (!pad) return P.clip ? OEH_GO(false, false, true, 1, false, true) : OEH_GO(false, false, true, 0, false, true);
+        return false;
       }
-      if (P.fq_s.en && pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 2>), dim3(grid), dim3(256), 0, st, P);
-      else if (P.fq_s.en) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 2>), dim3(grid), dim3(256), 0, st, P);
-      else if (P.clip && pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true, 1>), dim3(grid), dim3(256), 0, st, P);
-      else if (P.clip) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true, 1>), dim3(grid), dim3(256), 0, st, P);
-      else if (pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, true>), dim3(grid), dim3(256), 0, st, P);
-      else hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, true>), dim3(grid), dim3(256), 0, st, P);
+      if (P.fq_s.en) return pad ? OEH_GO(true, false, true, 2) : OEH_GO(false, false, true, 2);
+      if (P.clip) return pad ? OEH_GO(true, false, true, 1) : OEH_GO(false, false, true, 1);
+      return pad ? OEH_GO(true, false, true) : OEH_GO(false, false, true);
     }
-    return;
+    return false;
   }
-  if (P.fq_s.en) {  // (oeh_api.hip: flash_fq_eligible - the grid chain: no clip, no in-kernel predictor; key padding as a 0 / <= -1e4 vector)
-    if (pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, false, 2>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, false, 2>), dim3(grid), dim3(256), 0, st, P);
-    return;
-  }
-  if (P.clip) {  // (oeh_api.hip: flash_clip_eligible - no in-kernel predictor)
-    if (pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, false, 1>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, false, 1>), dim3(grid), dim3(256), 0, st, P);
-    return;
-  }
-  if constexpr (D == 64) {  // (oeh_api.hip: the out32 rule - head dim 64: plain, + key padding / a (B,1,Sq,Sk) mask, + the in-kernel gate predictor)
-    if (P.out32) {
-      if (pad) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false, false, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      else if (gate) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, true, false, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      else hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, false, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      return;
+  // (flash_two_pass_can - the grid chain: no clip, no in-kernel predictor; key padding as a 0 / <= -1e4 vector)
+  if (P.fq_s.en) return pad ? OEH_GO(true, false, false, 2) : OEH_GO(false, false, false, 2);
+  if (P.clip) return pad ? OEH_GO(true, false, false, 1) : OEH_GO(false, false, false, 1);  // (flash_two_pass_can - no in-kernel predictor)
+  if (P.out32) {  // (AttnPlan.out32, plan_attn step 6)
+    if constexpr (D == 64) {  // head dim 64: plain, + key padding / a (B,1,Sq,Sk) mask, + the in-kernel gate predictor
+      if (pad) return OEH_GO(true, false, false, 0, true);
+      return gate ? OEH_GO(false, true, false, 0, true) : OEH_GO(false, false, false, 0, true);
     }
+    if constexpr (D == 128 && MQ == 1) return OEH_GO(false, false, false, 0, true);  // head dim 128: the plain form, AttnPlan.mq == 1
+    return false;
   }
-  if constexpr (D == 128 && MQ == 1) {  // (head dim 128: the plain form; flash_mq gives one block per wave there)
-    if (P.out32) {
-      hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false, false, 0, true>), dim3(grid), dim3(256), 0, st, P);
-      return;
-    }
-  }
-  if (pad) {
-    if (gate) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, true>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, true, false>), dim3(grid), dim3(256), 0, st, P);
-  } else {
-    if (gate) hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, true>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((oeh_attn_flash_kernel<D, IN, MQ, false, false>), dim3(grid), dim3(256), 0, st, P);
-  }
+  if (pad) return gate ? OEH_GO(true, true) : OEH_GO(true, false);
+  return gate ? OEH_GO(false, true) : OEH_GO(false, false);
 }
+#undef OEH_GO
 
 template <int D, int MQ>
 static int launch_flash_d_mq(const AttnParams& P, int in, hipStream_t st) {
   const unsigned grid = (unsigned)(P.nQT * P.nBHpad);
-  if (in == IN_BF16) launch_flash_d_mq_in<D, MQ, IN_BF16>(P, grid, st);
-  else launch_flash_d_mq_in<D, MQ, IN_F16>(P, grid, st);
+  const bool launched = in == IN_BF16 ? launch_flash_d_mq_in<D, MQ, IN_BF16>(P, grid, st) : launch_flash_d_mq_in<D, MQ, IN_F16>(P, grid, st);
+  if (!launched) return -95;  // OEH_ENOTSUP
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-// P.nQT = ceil(Sq / (64*MQ)) workgroups per head; MQ is chosen by the host (oeh_api.hip: flash_mq)
+// P.nQT = ceil(Sq / (64*MQ)) workgroups per head; MQ is AttnPlan.mq (oeh_api.hip: flash_mq)
 template <int D>
 static int launch_flash_d(const AttnParams& P, int in, int mq, hipStream_t st) {
   if (mq == 1) return launch_flash_d_mq<D, 1>(P, in, st);

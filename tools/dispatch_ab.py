@@ -80,12 +80,12 @@ def ab(rule, shape, side_a, side_b, iters=120):
 
 def main():
     only = sys.argv[1:]
-    want = lambda r: (not only and r != "wide") or any(o in r for o in only)  # noqa: E731  ("wide": an experiment, on request only)
+    want = lambda r: not only or any(o in r for o in only)  # noqa: E731
     # 1. one-pass kernel, query blocks per wave: two (128-row workgroups) from 416 workgroups on  (oeh_api.hip: flash_mq)
     if want("flash_mq"):
         for B in (7, 8, 9, 10, 12):  # H=12 S=512: 4 workgroups of 128 rows per head -> 336, 384, 432, 480, 576
             ab("flash_mq >= 416 wgs -> MQ2", (B, 12, 512, 64, "f16", 1, 0, 0, 0), (0, 0), (0, 1 if B * 48 >= 416 else 2))
-    # 2. rows of <= 128 keys: the one-pass kernel from 768 of its workgroups on, the full-row kernel below  (flash_eligible)
+    # 2. rows of <= 128 keys: the one-pass kernel from 768 of its workgroups on, the full-row kernel below  (prefer_full_row_short)
     if want("short_rows"):
         for B in (32, 48, 64, 96):  # H=12 S=128: B*12 workgroups of 128 rows
             wg = B * 12
@@ -93,7 +93,7 @@ def main():
         for B in (64, 128, 192):   # d = 32: the threshold is 1536
             wg = B * 12
             ab("Sk<=128 d=32: one-pass >= 1536", (B, 12, 128, 32, "f16", 0, 0, 0, 0), (0, 0), ((2, 0) if wg >= 1536 else (256, 0)))
-    # 3. causal rows that leave the last 128-row workgroup at most half full: full-row kernel  (flash_eligible)
+    # 3. causal rows that leave the last 128-row workgroup at most half full: full-row kernel  (prefer_full_row_causal_tail)
     if want("ragged_causal"):
         for S, B in ((192, 40), (256, 32), (320, 24), (448, 18), (512, 16)):
             half_full = ((S - 1) % 128) < 64
@@ -112,7 +112,7 @@ def main():
     if want("d128_general"):
         for S, B, clip, int8 in ((256, 32, 1, 0), (256, 32, 0, 1), (512, 16, 0, 1)):
             ab("d=128 clip/int8: general kernel", (B, 8, S, 128, "f16", 1, clip, int8, 0), (0, 0), (1 << 11, 0))
-    # 7. fp32 storage, rows of <= 128 keys: the full-row fp32 form, except unpadded with >= 768 workgroups  (flash32_eligible)
+    # 7. fp32 storage, rows of <= 128 keys: the full-row fp32 form, except unpadded with >= 768 workgroups  (prefer_full_row_short)
     if want("fp32_short_rows"):
         for B, pad in ((32, 1), (64, 1), (32, 0), (64, 0), (96, 0)):
             many = (not pad) and B * 12 >= 768
@@ -121,11 +121,6 @@ def main():
     if want("fp32_ragged_causal"):
         for S, B in ((192, 40), (320, 24), (448, 18)):
             ab("fp32 causal ragged <= 384: full-row", (B, 12, S, 64, "f32", 1, 0, 0, 0), (0, 0), ((256, 0) if S <= 384 else (64, 0)))
-    # the 32x32x16 form of the one-pass kernel (oeh_attn_wide.hip) against the production 16x16x32 form
-    if want("wide"):
-        for B, S, causal in ((16, 512, 1), (16, 512, 0), (8, 1024, 1), (4, 2048, 1), (32, 256, 1), (12, 512, 1)):
-            ab("wide (32x32x16) vs one-pass", (B, 12, S, 64, "f16", causal, 0, 0, 0), (0, 0), (4096, 0))
-        ab("wide (32x32x16) vs one-pass", (16, 12, 512, 64, "bf16", 1, 0, 0, 0), (0, 0), (4096, 0))
     # 9. the small-shape kernel: fp32 problems of at most 32 rows, >= 256 of them
     if want("small_shape"):
         for B, S in ((224, 28), (384, 32), (224, 48), (48, 28)):

@@ -389,6 +389,33 @@ int oeh_attn_fwd_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const 
                     const oeh_fq_desc* fq, void* stream);
 const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const oeh_fq_desc* fq);
 
+/* Split-key decode attention (oeh_attn_decode.hip): a generation step against a key / value cache - 1 <= Sq <= 16 query rows, any Sk >= 1 - with
+ * the KEYS of one (batch, head) split over up to OEH_DECODE_MAX_SPLITS workgroups and the partial results combined by a second small launch.
+ * oeh_attn_fwd gives such a problem one workgroup per (batch, head) that walks the whole cache serially; this entry point fills the chip.
+ * `desc` as for oeh_attn_fwd with: dtype OEH_F16 | OEH_BF16, D == 64, both softmax bases, clip with gamma <= 0, scale or a positive finite
+ * scale_div, key_pad_mask (f16 / f32), causal (the Sk - Sq offset; only Sq <= Sk), clamp_min + mask_min, gate values with their strides,
+ * o_dtype == OEH_F32 (fp32 output from the accumulators, written by the combine pass).  No fake-quant argument.
+ * Refusals, in this order: OEH_EINVAL - null pointers, non-positive sizes, splits < 0 or > OEH_DECODE_MAX_SPLITS; OEH_ENOTSUP - full_mask,
+ * gate_hidden, fp32 or INT8 storage, another head dim, Sq > 16, clip with gamma > 0, causal with Sq > Sk; OEH_EALIGN - q, k, v or o rows (or
+ * `work`) not 16-byte aligned.
+ * splits == 0: the library chooses (oeh_attn_decode.hip, default_splits, with the measurements it was chosen from).  Otherwise the chunk is
+ * C = roundup64(ceil(Sk / splits)) keys and the effective count n = ceil(Sk / C); the variant name prints n:
+ * "decode16/SP<n>/D64/<f16|bf16>[/clip]".
+ * work: caller-provided device scratch of oeh_attn_decode_work_bytes(desc, splits) bytes, 16-byte aligned; contents irrelevant before and
+ * after.  Per (batch, head, split, query row): the running maximum m and the sum l = sum e^(x - m) of the split's scores, and 64 fp32
+ * accumulators sum e^(x - m) v.  The combine pass forms M = max_s m_s (softmax_1: max(., 0)), den = sum_s l_s e^(m_s - M) (+ e^(-M)) and
+ * o = sum_s acc_s e^(m_s - M) / den - M and den as TWO numbers, never one lse = M + log(den): a vanilla row without a visible key sits at
+ * finfo.min, where that sum rounds back to M and every key would get probability 1 (the same trap as the backward's scratch above).
+ * The clipped forms run three launches (statistics; y = clip((eta - gamma) e^(x - M) / den + gamma, 0, 1) times V per split; the sum).
+ * No allocation, no host synchronisation, no atomics, a fixed split order: bitwise reproducible; graph-capture safe (a linear chain of
+ * launches).  The masks are added literally in fp32 and no chunk is skipped (a vanilla row without a visible key is uniform over ALL keys).
+ * oeh_attn_decode_work_bytes: bytes of `work`, or the negative OEH_E* code.  oeh_attn_decode_variant: host only; NULL if refused; the
+ * string lives in thread-local storage until the next call on this thread. */
+#define OEH_DECODE_MAX_SPLITS 64
+int64_t oeh_attn_decode_work_bytes(const oeh_attn_desc* desc, int32_t splits);
+int oeh_attn_decode(const oeh_attn_desc* desc, int32_t splits, const void* q, const void* k, const void* v, void* o, void* work, void* stream);
+const char* oeh_attn_decode_variant(const oeh_attn_desc* desc, int32_t splits);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -8,7 +8,7 @@ over the C-ABI library `lib/liboeh_hip.so` (include/oeh.h).  There is no CPU imp
 every op raises if the HIP library is missing or a tensor is not on a GPU.
 """
 from . import _lib, ops  # noqa: F401
-from .attention import AttentionGateType, logit, set_fused_backward, set_fused_dropout  # noqa: F401
+from .attention import AttentionGateType, logit, set_fused_backward, set_fused_dropout, set_split_decode  # noqa: F401
 from .autograd_attention import fused_attention  # noqa: F401
 from .bert_attention import BertSelfAttentionWithExtras  # noqa: F401
 from .hopfield import Association, Hopfield, HopfieldPooling  # noqa: F401

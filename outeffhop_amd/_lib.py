@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("OEH_LIB") or os.path.join(_HERE, "lib", "liboeh_hip.s
 
 ABI_VERSION = 6  # include/oeh.h: OEH_ABI_VERSION
 CALIB_WORK_BYTES = 36864  # include/oeh.h: OEH_CALIB_WORK_BYTES
+DECODE_MAX_SPLITS = 64  # include/oeh.h: OEH_DECODE_MAX_SPLITS
 OEH_F16, OEH_BF16, OEH_F32, OEH_I8 = 0, 1, 2, 3
 OEH_SOFTMAX_VANILLA, OEH_SOFTMAX_ONE = 0, 1
 
@@ -82,6 +83,7 @@ EXPORTS = (
     "oeh_attn_fwd_train_dropout", "oeh_attn_bwd_dropout", "oeh_attn_dropout_mask",
     "oeh_abi_version", "oeh_build_info", "oeh_strerror", "oeh_attn_variant",
     "oeh_attn_fwd_ex", "oeh_attn_variant_ex",
+    "oeh_attn_decode_work_bytes", "oeh_attn_decode", "oeh_attn_decode_variant",
 )
 
 _lib = None
@@ -153,6 +155,12 @@ def load() -> C.CDLL:
     lib.oeh_attn_fwd_ex.restype = C.c_int
     lib.oeh_attn_variant_ex.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_attn_opts), C.POINTER(oeh_fq_desc)]
     lib.oeh_attn_variant_ex.restype = C.c_char_p
+    lib.oeh_attn_decode_work_bytes.argtypes = [C.POINTER(oeh_attn_desc), i32]
+    lib.oeh_attn_decode_work_bytes.restype = C.c_int64
+    lib.oeh_attn_decode.argtypes = [C.POINTER(oeh_attn_desc), i32, vp, vp, vp, vp, vp, vp]
+    lib.oeh_attn_decode.restype = C.c_int
+    lib.oeh_attn_decode_variant.argtypes = [C.POINTER(oeh_attn_desc), i32]
+    lib.oeh_attn_decode_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

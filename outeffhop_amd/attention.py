@@ -393,15 +393,33 @@ def pv_pairs_for(q: torch.Tensor, fq=None) -> bool:
     return COMPENSATED_PV and q.dtype == torch.float32 and fq is None
 
 
+# ---- generation steps on the split-key decode kernels: with SPLIT_DECODE on, a fused call that says `decode=True` (OPT's self-attention with
+# a past_key_value) and has at most 16 query rows, 16-bit storage, head dim 64, no fake-quant and no (B,1,Sq,Sk) mask left after
+# split_mask / classify_causal runs ops.attn_decode - the keys of a head over many workgroups plus a combine pass - instead of ops.attn_fwd's
+# one serial workgroup per (batch, head).  Outputs agree within the contract, not bit for bit (another summation order).  What the entry point
+# refuses (OehError -95 / -14) falls back to ops.attn_fwd.
+# OFF by default: against ops.attn_fwd (tools/decode_bench.py, profiles/decode_bench.txt; OPT-125m heads, one query row, fp16) the decode path
+# measured 1.8-2.1x faster at B H = 12, Sk = 2048, but 0.55-0.9x at Sk = 512 and at B H = 192, and the crossover between those points is not
+# measured - this rule routes every problem in scope, so it stays opt-in until a measured "B H <= x and Sk >= y" replaces it.
+SPLIT_DECODE = False
+
+
+def set_split_decode(on: bool = True) -> None:
+    """Route the modules' generation steps to the split-key decode kernels (True) or keep them on ops.attn_fwd (False, the default)."""
+    global SPLIT_DECODE
+    SPLIT_DECODE = bool(on)
+
+
 def attention_core(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax_fn, scale: float = 1.0, scale_div: float = 0.0,
     attention_mask: Optional[torch.Tensor] = None, clamp_min: bool = False, detect_causal: bool = False,
     gate: Optional[torch.Tensor] = None, fq: Optional[AttnFakeQuant] = None, mask_min: Optional[float] = None,
-    gate_mlp=None,
+    gate_mlp=None, decode: bool = False,
 ) -> torch.Tensor:
     """Fused path: logical (B,H,S,d) views in, (B,Sq,H*d) context out (head merge is free).  `gate_mlp`
     (ops.GatePredictor): the per-token gate is evaluated inside the attention kernel where the library supports that
-    (full-row 16-bit kernel, <= 16 hidden units), else by `ops.gate_fwd` first."""
+    (full-row 16-bit kernel, <= 16 hidden units), else by `ops.gate_fwd` first.  `decode`: a generation step against a key / value
+    cache - the split-key decode kernels where they apply (SPLIT_DECODE above)."""
     B, H, Sq, D = q.shape
     Sk = k.shape[2]
     spec = spec_of(softmax_fn)
@@ -421,6 +439,14 @@ def attention_core(
     kw = dict(softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full, key_pad_boolean=pad_bool, causal=causal,
               clamp_min=clamp_min, mask_min=mask_min, fq=fq, pv_pairs=pv)
     out = None
+    if (decode and SPLIT_DECODE and gate_mlp is None and fq is None and full is None and Sq <= 16 and D == 64
+            and q.dtype in (torch.float16, torch.bfloat16)):
+        try:
+            out = ops.attn_decode(q, k, v, softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, causal=causal, clamp_min=clamp_min,
+                                  mask_min=mask_min, gate=gate)
+        except _lib.OehError as e:  # outside the decode entry point's scope after all (gamma > 0, alignment ...): the general forward
+            if e.code not in (-95, -14):
+                raise
     if gate_mlp is not None:
         units = 0 if gate_mlp.w1.dim() == 2 else gate_mlp.w1.shape[1]
         if full is None and ops.fused_gate_ok(B, H, Sq, Sk, D, q.dtype, clip=bool(spec.clip), fq=fq is not None, units=units,

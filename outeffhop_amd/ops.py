@@ -693,6 +693,100 @@ def attn_variant(B, H, Sq, Sk, D, dtype=torch.float16, fq: bool = False, clip: b
     return None if r is None else r.decode()
 
 
+DECODE_CALLS = 0  # launches of `attn_decode` (the modules' generation steps: attention.SPLIT_DECODE)
+_decode_work = {}  # (device index, stream handle) -> the split-key scratch of that stream
+
+
+def _decode_scratch(dev, nbytes: int):
+    """The current stream's scratch for `oeh_attn_decode` on `dev`, grown to the largest request so far (bounded like `_calib_scratch`).
+    Under graph capture the call gets a buffer of its own instead, allocated inside the capture: it then lives in the graph's private
+    pool for as long as the graph does - a cached buffer may be replaced (a larger request, the table starting over) and freed while a
+    graph that recorded its address is still replayed."""
+    with _on_device(dev):
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    work = _decode_work.get(key)
+    if work is None or work.numel() * 8 < nbytes:
+        if len(_decode_work) >= 32:
+            _decode_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
+        work = _decode_work[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    return work
+
+
+def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0,
+                key_pad_mask: Optional[torch.Tensor] = None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None,
+                gate: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, splits: int = 0) -> torch.Tensor:
+    """Split-key decode attention (`oeh_attn_decode`): a generation step - q (B,H,Sq,64) with 1 <= Sq <= 16 against k, v (B,H,Sk,64) views of
+    a cache (any batch / head / sequence strides, unit head-dim stride; fp16 / bf16) - with the keys of a head split over `splits`
+    workgroups (0: the library's rule) and a combine pass.  Masks, gate, `out_dtype` and the result's layout ((B,Sq,H,D)-contiguous) as
+    `attn_fwd`; what the entry point does not take (another head dim, more query rows, fp32 storage, gamma > 0) raises OehError -95.
+    Bitwise reproducible; graph-capture safe (a captured call owns its scratch: `_decode_scratch`)."""
+    global DECODE_CALLS
+    dev = _need_gpu(q, k, v, key_pad_mask, gate)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k, v must be 4-D (B,H,S,D) views")
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if k.shape != (B, H, Sk, D) or v.shape != (B, H, Sk, D):
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in _DT:
+        raise ValueError(f"q/k/v dtypes must match and be fp16/bf16/fp32, got {q.dtype}, {k.dtype}, {v.dtype}")
+    fix = lambda t: t if t.stride(3) == 1 else t.contiguous()  # noqa: E731
+    q, k, v = fix(q), fix(k), fix(v)
+    odt = q.dtype if out_dtype is None else out_dtype
+    if odt != q.dtype and odt != torch.float32:
+        raise ValueError(f"out_dtype must be the input dtype or float32 (got {odt} for {q.dtype})")
+    out = torch.empty((B, Sq, H, D), dtype=odt, device=q.device).permute(0, 2, 1, 3)
+    d = oeh_attn_desc()
+    d.B, d.H, d.Sq, d.Sk, d.D = B, H, Sq, Sk, D
+    d.dtype, d.o_dtype = _DT[q.dtype], _DT[odt]
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
+        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    d.scale, d.scale_div = float(scale), float(scale_div)
+    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    keep = []
+    if key_pad_mask is not None:
+        m = key_pad_mask.reshape(B, Sk)
+        if m.dtype not in (torch.float16, torch.float32):
+            m = m.float()
+        m = m.contiguous()
+        keep.append(m)
+        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
+    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
+    d.mask_min = float(torch.finfo(q.dtype).min if mask_min is None else mask_min)
+    if gate is not None:
+        g = gate.to(torch.float32)
+        while g.dim() < 4:
+            g = g.unsqueeze(0)
+        g = g.expand(B, H, Sq, 1)
+        keep.append(g)
+        d.gate = g.data_ptr()
+        d.gate_stride[:] = [g.stride(0), g.stride(1), g.stride(2)]
+    lib = _lib.load()
+    nbytes = lib.oeh_attn_decode_work_bytes(C.byref(d), int(splits))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "oeh_attn_decode")
+    work = _decode_scratch(dev, int(nbytes))
+    with _on_device(dev):
+        rc = lib.oeh_attn_decode(C.byref(d), int(splits), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(work), _stream())
+    _lib.check(rc, "oeh_attn_decode")
+    DECODE_CALLS += 1
+    return out
+
+
+def attn_decode_variant(B, H, Sq, Sk, D=64, dtype=torch.float16, *, clip: bool = False, gamma: float = -0.025, causal: bool = False, splits: int = 0) -> Optional[str]:
+    """Name of the form `attn_decode` would run ("decode16/SP<effective splits>/D64/f16[/clip]"), or None where it refuses (host only)."""
+    d = oeh_attn_desc()
+    d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[dtype]
+    d.scale, d.softmax_base, d.causal = 1.0, 1, int(bool(causal))
+    d.mask_min = float(torch.finfo(torch.float32).min)
+    if clip:
+        d.clip, d.gamma, d.eta = 1, float(gamma), 1.0
+    r = _lib.load().oeh_attn_decode_variant(C.byref(d), int(splits))
+    return None if r is None else r.decode()
+
+
 def softmax_rows(x: torch.Tensor, spec: SoftmaxSpec = SoftmaxSpec(), dim: int = -1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """SOFTMAX_MAPPING callable on the GPU: softmax / softmax_1 / clipped variants along `dim`."""
     dev = _need_gpu(x, out)

@@ -120,7 +120,8 @@ class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
         weights = None
         if fusable:
             merged = attention_core(q, k, v, softmax_fn=self.softmax_fn, scale=1.0, attention_mask=attention_mask,
-                                    clamp_min=attention_mask is not None, detect_causal=True, gate=gate, gate_mlp=gp)
+                                    clamp_min=attention_mask is not None, detect_causal=True, gate=gate, gate_mlp=gp,
+                                    decode=key_value_states is None and past_key_value is not None)
             if gp is not None:
                 GateState.finish_predictor(self, gp, self.num_heads)
         else:

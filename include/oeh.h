@@ -394,7 +394,8 @@ const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* 
  * oeh_attn_fwd gives such a problem one workgroup per (batch, head) that walks the whole cache serially; this entry point fills the chip.
  * `desc` as for oeh_attn_fwd with: dtype OEH_F16 | OEH_BF16, D == 64, both softmax bases, clip with gamma <= 0, scale or a positive finite
  * scale_div, key_pad_mask (f16 / f32), causal (the Sk - Sq offset; only Sq <= Sk), clamp_min + mask_min, gate values with their strides,
- * o_dtype == OEH_F32 (fp32 output from the accumulators, written by the combine pass).  No fake-quant argument.
+ * o_dtype == OEH_F32 (fp32 output from the accumulators, written by the combine pass).  oeh_attn_decode takes no fake-quant argument;
+ * oeh_attn_decode_fq below is the same entry point with one.
  * Refusals, in this order: OEH_EINVAL - null pointers, non-positive sizes, splits < 0 or > OEH_DECODE_MAX_SPLITS; OEH_ENOTSUP - full_mask,
  * gate_hidden, fp32 or INT8 storage, another head dim, Sq > 16, clip with gamma > 0, causal with Sq > Sk; OEH_EALIGN - q, k, v or o rows (or
  * `work`) not 16-byte aligned.
@@ -415,6 +416,26 @@ const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* 
 int64_t oeh_attn_decode_work_bytes(const oeh_attn_desc* desc, int32_t splits);
 int oeh_attn_decode(const oeh_attn_desc* desc, int32_t splits, const void* q, const void* k, const void* v, void* o, void* work, void* stream);
 const char* oeh_attn_decode_variant(const oeh_attn_desc* desc, int32_t splits);
+/* The same with the fused INT8 chain of oeh_attn_fwd - QK^T -> scale -> [fq scores] -> masks -> softmax / softmax_1 -> [clip] -> [fq probs] -> PV ->
+ * [fq ctx | gate, in the order of ctx_quant_before_gate] - for a quantised decoder's generation step; any subset of the three quantisers.
+ * `desc`, `splits` (the same rule), the scope and `work` - layout and size of oeh_attn_decode_work_bytes(desc, splits), the same (m, l) pairs
+ * and accumulators; there is no second size function - as for oeh_attn_decode.  With fq == NULL or no quantiser enabled the call IS
+ * oeh_attn_decode, bit for bit.
+ * The scores are quantised right after the scaling (scale_div: a true division) and before the masks, which are added literally
+ * (key_pad_boolean is accepted and not needed); a key beyond Sk stays invisible, a zero K row quantises to a grid point.  With the probability
+ * quantiser (as with the clip) the three-launch form runs: statistics; a product pass that forms p = e^(x - M) / den, clips, and feeds the
+ * integers idx - zero_point (exact in fp16 and bf16) to the second product; a sum that applies the probability scale in fp32.  Otherwise the
+ * two-launch form, the scores quantiser in the partial pass.  The context quantiser and the gate sit in the last launch; o_dtype == OEH_F32
+ * stays available.  Index dumps (oeh_fq.dump_idx, tests): scores and probabilities dense (B,H,Sq,Sk), each split writing its own keys; context
+ * (B,H,Sq,64).  Still plain launches in a fixed split order: bitwise reproducible, graph-capture safe.
+ * Refusals: those of oeh_attn_decode first, in its order (full_mask, gate_hidden, fp32 / INT8 storage, another head dim, Sq > 16 ... are
+ * OEH_ENOTSUP here too); then OEH_EINVAL - an enabled quantiser whose scale is not positive and finite, whose qmax is not finite and >= 1 or
+ * whose zero point lies outside [0, qmax]; then OEH_ENOTSUP - ctx_emit_index (oeh_attn_fwd has it), a uint8 dump of a grid with qmax > 255.
+ * oeh_attn_decode_fq_variant: the decode name with "/fq" appended when a quantiser is enabled ("decode16/SP8/D64/f16/fq", ".../clip/fq");
+ * NULL if refused; thread-local storage as above. */
+int oeh_attn_decode_fq(const oeh_attn_desc* desc, const oeh_fq_desc* fq, int32_t splits, const void* q, const void* k, const void* v, void* o,
+                       void* work, void* stream);
+const char* oeh_attn_decode_fq_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq, int32_t splits);
 
 /* library information (host side, no device work) */
 int oeh_abi_version(void);

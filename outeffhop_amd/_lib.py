@@ -83,7 +83,7 @@ EXPORTS = (
     "oeh_attn_fwd_train_dropout", "oeh_attn_bwd_dropout", "oeh_attn_dropout_mask",
     "oeh_abi_version", "oeh_build_info", "oeh_strerror", "oeh_attn_variant",
     "oeh_attn_fwd_ex", "oeh_attn_variant_ex",
-    "oeh_attn_decode_work_bytes", "oeh_attn_decode", "oeh_attn_decode_variant",
+    "oeh_attn_decode_work_bytes", "oeh_attn_decode", "oeh_attn_decode_variant", "oeh_attn_decode_fq", "oeh_attn_decode_fq_variant",
 )
 
 _lib = None
@@ -161,6 +161,10 @@ def load() -> C.CDLL:
     lib.oeh_attn_decode.restype = C.c_int
     lib.oeh_attn_decode_variant.argtypes = [C.POINTER(oeh_attn_desc), i32]
     lib.oeh_attn_decode_variant.restype = C.c_char_p
+    lib.oeh_attn_decode_fq.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_fq_desc), i32, vp, vp, vp, vp, vp, vp]
+    lib.oeh_attn_decode_fq.restype = C.c_int
+    lib.oeh_attn_decode_fq_variant.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_fq_desc), i32]
+    lib.oeh_attn_decode_fq_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

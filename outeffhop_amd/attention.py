@@ -394,13 +394,16 @@ def pv_pairs_for(q: torch.Tensor, fq=None) -> bool:
 
 
 # ---- generation steps on the split-key decode kernels: with SPLIT_DECODE on, a fused call that says `decode=True` (OPT's self-attention with
-# a past_key_value) and has at most 16 query rows, 16-bit storage, head dim 64, no fake-quant and no (B,1,Sq,Sk) mask left after
+# a past_key_value, and the quantised decoder QuantizedOPTAttentionWithExtras with its three fake-quantisers: oeh_attn_decode_fq) and has at
+# most 16 query rows, 16-bit storage, head dim 64, no gate predictor and no (B,1,Sq,Sk) mask left after
 # split_mask / classify_causal runs ops.attn_decode - the keys of a head over many workgroups plus a combine pass - instead of ops.attn_fwd's
 # one serial workgroup per (batch, head).  Outputs agree within the contract, not bit for bit (another summation order).  What the entry point
 # refuses (OehError -95 / -14) falls back to ops.attn_fwd.
 # OFF by default: against ops.attn_fwd (tools/decode_bench.py, profiles/decode_bench.txt; OPT-125m heads, one query row, fp16) the decode path
 # measured 1.8-2.1x faster at B H = 12, Sk = 2048, but 0.55-0.9x at Sk = 512 and at B H = 192, and the crossover between those points is not
 # measured - this rule routes every problem in scope, so it stays opt-in until a measured "B H <= x and Sk >= y" replaces it.
+# With the fused INT8 chain (a quantised decoder's step: oeh_attn_decode_fq against oeh_attn_fwd's fq forms; tools/decode_bench.py --fq,
+# profiles/decode_bench_fq.txt, the second table of DESIGN.md 10): 2.25-2.3x at B H = 12, Sk = 2048, 1.1x at B H = 192, Sk = 2048, 0.55-0.67x at Sk = 512.
 SPLIT_DECODE = False
 
 
@@ -439,12 +442,12 @@ def attention_core(
     kw = dict(softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full, key_pad_boolean=pad_bool, causal=causal,
               clamp_min=clamp_min, mask_min=mask_min, fq=fq, pv_pairs=pv)
     out = None
-    if (decode and SPLIT_DECODE and gate_mlp is None and fq is None and full is None and Sq <= 16 and D == 64
+    if (decode and SPLIT_DECODE and gate_mlp is None and full is None and Sq <= 16 and D == 64
             and q.dtype in (torch.float16, torch.bfloat16)):
         try:
             out = ops.attn_decode(q, k, v, softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, causal=causal, clamp_min=clamp_min,
-                                  mask_min=mask_min, gate=gate)
-        except _lib.OehError as e:  # outside the decode entry point's scope after all (gamma > 0, alignment ...): the general forward
+                                  mask_min=mask_min, gate=gate, fq=fq)
+        except _lib.OehError as e:  # outside the decode entry point's scope after all (gamma > 0, ctx_emit_index, alignment ...): the general forward
             if e.code not in (-95, -14):
                 raise
     if gate_mlp is not None:

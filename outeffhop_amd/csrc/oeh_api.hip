@@ -47,26 +47,7 @@ namespace {
 bool dtype_ok(int d) { return d == OEH_F16 || d == OEH_BF16 || d == OEH_F32; }
 int elem_bytes(int d) { return d == OEH_F32 ? 4 : d == OEH_I8 ? 1 : 2; }
 
-// RN(scale * log2(e)), the product formed in double
-float scale_log2e(float scale) { return (float)((double)scale * 1.4426950408889634074); }
-
-FqP make_fq(const oeh_fq* f) {
-  FqP r;
-  std::memset(&r, 0, sizeof(r));
-  if (f != nullptr && f->enable) {
-    r.en = 1;
-    r.scale = f->scale;
-    r.rscale = 1.0f / f->scale;
-    r.zp = f->zero_point;
-    r.qmax = f->qmax;
-    r.lo = -f->zero_point;
-    r.hi = f->qmax - f->zero_point;
-    r.dump = f->dump_idx;
-    r.c2 = scale_log2e(f->scale);
-    r.oscale = f->scale;
-  }
-  return r;
-}
+using oeh::make_fq;  // (oeh_attn_params.h)
 
 enum Variant { V_NONE = 0, V_FLASH, V_FAST, V_MFMA, V_GENERIC, V_SMALL, V_I8 };
 

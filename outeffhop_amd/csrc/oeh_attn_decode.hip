@@ -17,6 +17,12 @@
 //    its rows from the n statistic pairs and accumulates y = clip((eta - gamma) e^(x - M) / den + gamma, 0, 1) times V, and a plain sum.
 //  * the mask arithmetic is literal (fp32 add, then the clamp) and no chunk is skipped: under the vanilla softmax a row without a visible
 //    key is uniform over ALL keys, those of fully padded chunks included.
+//  * the fused INT8 chain (oeh_attn_decode_fq; FQ = true instantiations, the forms above compile as before): the scores quantiser sits right
+//    after the scaling, in front of the literal mask arithmetic, in EVERY pass that forms scores (the same operations: the same bits); the
+//    probability quantiser needs the row's denominator before the grid, so with it (as with the clip) the three-launch form runs - statistics,
+//    a product pass that forms p = e^(x - M) / den, [clip], rel = idx - zp and feeds the INTEGERS rel to the second product (exact in f16 and
+//    bf16), a plain sum that applies the probability scale in fp32; the context quantiser and the gate, in either order, sit in the last launch.
+//    Exponentials that feed a quantiser are the ~1 ulp exp_acc_nonpos, as in the other fake-quant kernels.
 #include "../../include/oeh.h"
 #include "oeh_attn_params.h"
 
@@ -52,21 +58,32 @@ __device__ __forceinline__ f4 dec_mfma(u4 a, u4 b, f4 c) {
 // e^(a - b) for a <= b or a = -inf; b finite
 __device__ __forceinline__ float exp_diff(float a, float b) { return __builtin_amdgcn_exp2f((a - b) * kLog2e); }
 
+// the same, ACC: to ~1 ulp (the fake-quant forms: the value feeds a quantiser)
+template <bool ACC>
+__device__ __forceinline__ float exp_d(float a, float b) {
+  if constexpr (ACC) return exp_acc_nonpos(a - b);
+  else return exp_diff(a, b);
+}
+
 // (M, den) of one query row from its n statistic pairs, in split order.  A row whose every score is -inf keeps M finite (0): all weights 0.
+template <bool ACC = false>
 __device__ __forceinline__ void row_stats(const float* ml, const int n, const long stride, const int base, float& M, float& den) {
   float mx = kNegInf;
   for (int s = 0; s < n; ++s) mx = __builtin_fmaxf(mx, ml[s * stride]);
   if (base != 0) mx = __builtin_fmaxf(mx, 0.0f);
   if (mx == kNegInf) mx = 0.0f;
   float d = 0.0f;
-  for (int s = 0; s < n; ++s) d = d + ml[s * stride + 1] * exp_diff(ml[s * stride], mx);
-  if (base != 0) d = d + __builtin_amdgcn_exp2f(-mx * kLog2e);
+  for (int s = 0; s < n; ++s) d = d + ml[s * stride + 1] * exp_d<ACC>(ml[s * stride], mx);
+  if (base != 0) d = d + exp_d<ACC>(-mx, 0.0f);
   M = mx;
   den = d;
 }
 
-template <int IN, int MODE>
-__global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParams DP) {
+// FQ: the forms with the scores / probability quantisers (each under a wave-uniform test of its enable flag; FQ = false: none of that code).
+// The fake-quant plain / product forms ask the register allocator for four waves per SIMD (the non-quantised product form's occupancy): left
+// alone they come out at 122 / 114 VGPRs + 16 AGPRs, three waves; with the request 112 / 113 VGPRs, no AGPRs, no scratch.  (1: no request.)
+template <int IN, int MODE, bool FQ = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FQ && MODE != DEC_STATS ? 4 : 1))) void oeh_attn_decode_partial(const DecodeParams DP) {
   const AttnParams& P = DP.A;
   constexpr int ROWB = 128;  // bytes of a 64-element 16-bit row
   // per wave: the 32-key V image of the loop, then (the same 4 KB, after the wave's last transposed read) its 16 x 64 fp32 accumulators
@@ -97,7 +114,7 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
   if constexpr (MODE == DEC_CLIP) {
     if (qvalid) {
       float den;
-      row_stats(DP.ml + ((long)bh * DP.n * P.Sq + c) * 2, DP.n, (long)P.Sq * 2, P.base, M, den);
+      row_stats<FQ>(DP.ml + ((long)bh * DP.n * P.Sq + c) * 2, DP.n, (long)P.Sq * 2, P.base, M, den);
       inv_den = 1.0f / den;
     }
   }
@@ -155,7 +172,21 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = key0 + 16 * t + 4 * g + r;
-        float x = s[t][r] * P.scale;
+        float x;
+        if constexpr (FQ) {
+          // the reference's order: scale (BERT: a true division), quantise, then the masks.  The statistics and the product pass run these
+          // very operations on the same MFMA chain: the same quantised scores, bit for bit.
+          x = P.scale_div != 0.0f ? s[t][r] / P.scale_div : s[t][r] * P.scale;
+          if (P.fq_s.en) {
+            const float rel = fq_rel(x, P.fq_s);
+            if constexpr (MODE != DEC_STATS) {
+              if (P.fq_s.dump != nullptr && qvalid && key < P.Sk) P.fq_s.dump[((long)bh * P.Sq + c) * P.Sk + key] = (unsigned char)(rel + P.fq_s.zp);
+            }
+            x = P.fq_s.scale * rel;
+          }
+        } else {
+          x = s[t][r] * P.scale;
+        }
         if (key < P.Sk) {
           if (P.pad != nullptr) x = x + load_mask(P.pad, P.pad_f16, (long)b * P.pad_sb + key);
           if (P.causal && key > c + off) x = x + P.mask_min;
@@ -172,23 +203,33 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float p = exp_diff(s[t][r], M) * inv_den;
-          p = p * P.clip_w;
-          p = p + P.clip_g;
-          s[t][r] = __builtin_fminf(__builtin_fmaxf(p, 0.0f), 1.0f);  // (a key beyond Sk: clip(gamma) = 0, gamma <= 0)
+          float p = exp_d<FQ>(s[t][r], M) * inv_den;
+          if (!FQ || P.clip) {
+            p = p * P.clip_w;
+            p = p + P.clip_g;
+            p = __builtin_fminf(__builtin_fmaxf(p, 0.0f), 1.0f);  // (a key beyond Sk: clip(gamma) = 0, gamma <= 0)
+          }
+          if constexpr (FQ) {
+            if (P.fq_p.en) {  // the integer idx - zp (|.| <= 255: exact in f16 and bf16) is the P operand; the scale follows the product in fp32
+              const int key = key0 + 16 * t + 4 * g + r;
+              p = fq_rel(p, P.fq_p);  // (a masked key or one beyond Sk: p = 0, rel = 0)
+              if (P.fq_p.dump != nullptr && qvalid && key < P.Sk) P.fq_p.dump[((long)bh * P.Sq + c) * P.Sk + key] = (unsigned char)(p + P.fq_p.zp);
+            }
+          }
+          s[t][r] = p;
         }
       }
     } else {
       mx = row4_max(mx);
       const float m_new = __builtin_fmaxf(m, mx);
       const float m_ref = m_new == kNegInf ? 0.0f : m_new;  // (every score so far -inf: all terms 0, no inf - inf)
-      const float alpha = exp_diff(m, m_ref);
+      const float alpha = exp_d<FQ>(m, m_ref);
       float sum = 0.0f;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          s[t][r] = exp_diff(s[t][r], m_ref);
+          s[t][r] = exp_d<FQ>(s[t][r], m_ref);
           sum = sum + s[t][r];
         }
       }
@@ -213,6 +254,25 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
       u4 pb;
       if constexpr (IN == IN_BF16) pb = u4{pack2_bf16(s[0][0], s[0][1]), pack2_bf16(s[0][2], s[0][3]), pack2_bf16(s[1][0], s[1][1]), pack2_bf16(s[1][2], s[1][3])};
       else pb = u4{pack2_f16(s[0][0], s[0][1]), pack2_f16(s[0][2], s[0][3]), pack2_f16(s[1][0], s[1][1]), pack2_f16(s[1][2], s[1][3])};
+      // The two-launch fake-quant form (no probability quantiser: the weights e^(x - m) are no integers): what the 16-bit rounding of a weight
+      // drops goes through the product as a second operand, so that the context - it may feed the context quantiser - carries the weights to
+      // ~2^-17 instead of bf16's 2^-9 / fp16's 2^-11 (a context grid has 255 steps: 2^-9 of a value is a sizeable share of one).
+      u4 pb2 = u4{0, 0, 0, 0};
+      if constexpr (FQ && MODE == DEC_PLAIN) {
+        float lo[2][4];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const unsigned w = pb[2 * t + (r >> 1)];
+            float hi;
+            if constexpr (IN == IN_BF16) hi = __builtin_bit_cast(float, (r & 1) ? (w & 0xffff0000u) : (w << 16));
+            else hi = (float)__builtin_bit_cast(_Float16, (unsigned short)((r & 1) ? (w >> 16) : (w & 0xffffu)));
+            lo[t][r] = s[t][r] - hi;
+          }
+        if constexpr (IN == IN_BF16) pb2 = u4{pack2_bf16(lo[0][0], lo[0][1]), pack2_bf16(lo[0][2], lo[0][3]), pack2_bf16(lo[1][0], lo[1][1]), pack2_bf16(lo[1][2], lo[1][3])};
+        else pb2 = u4{pack2_f16(lo[0][0], lo[0][1]), pack2_f16(lo[0][2], lo[0][3]), pack2_f16(lo[1][0], lo[1][1]), pack2_f16(lo[1][2], lo[1][3])};
+      }
       const int row = 4 * g + (c >> 2);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
@@ -220,6 +280,7 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
         const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0));
         const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0 + 16 * ROWB));
         const u2 l2 = __builtin_bit_cast(u2, lo), h2 = __builtin_bit_cast(u2, hi);
+        if constexpr (FQ && MODE == DEC_PLAIN) acc[dt] = dec_mfma<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pb2, acc[dt]);  // (the small part first)
         acc[dt] = dec_mfma<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pb, acc[dt]);
       }
     }
@@ -256,7 +317,7 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
     float lw = 0.0f;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-      const float e = exp_diff(lds_ml[w][row][0], m_ref);
+      const float e = exp_d<FQ>(lds_ml[w][row][0], m_ref);
       lw = lw + lds_ml[w][row][1] * e;
       if constexpr (MODE == DEC_PLAIN) a = a + *acc_slot(w, row, quad) * e;
     }
@@ -266,8 +327,9 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_partial(const DecodeParam
 }
 
 // One thread per (batch, head, query row, 4 output columns): the splits in their fixed order, the gate, the store.
-// SUM: the clipped form - the slabs are sums of y v already.
-template <bool SUM>
+// SUM: the three-launch forms - the slabs are sums of y v already (with the probability quantiser: of (idx - zp) v, its scale applied here).
+// FQ: the context quantiser before or after the gate (oeh_common.h: ctx_chain), its index dump.
+template <bool SUM, bool FQ = false>
 __global__ __launch_bounds__(256) void oeh_attn_decode_combine(const DecodeParams DP) {
   const AttnParams& P = DP.A;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -282,15 +344,27 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_combine(const DecodeParam
   f4 o = f4{0.f, 0.f, 0.f, 0.f};
   if constexpr (SUM) {
     for (int s = 0; s < DP.n; ++s) o = o + *reinterpret_cast<const f4*>(ap + s * stride);
+    if constexpr (FQ) {
+      if (P.fq_p.en) o = o * P.fq_p.scale;
+    }
   } else {
     const float* ml = DP.ml + ((long)bh * DP.n * P.Sq + row) * 2;
     float M, den;
-    row_stats(ml, DP.n, (long)P.Sq * 2, P.base, M, den);
-    for (int s = 0; s < DP.n; ++s) o = o + *reinterpret_cast<const f4*>(ap + s * stride) * exp_diff(ml[s * (long)P.Sq * 2], M);
+    row_stats<FQ>(ml, DP.n, (long)P.Sq * 2, P.base, M, den);
+    for (int s = 0; s < DP.n; ++s) o = o + *reinterpret_cast<const f4*>(ap + s * stride) * exp_d<FQ>(ml[s * (long)P.Sq * 2], M);
     const float inv = 1.0f / den;
     o = o * inv;
   }
-  if (P.gate != nullptr) o = o * P.gate[(long)b * P.gs_b + (long)h * P.gs_h + (long)row * P.gs_s];
+  if constexpr (FQ) {
+    const bool gated = P.gate != nullptr;
+    const float gatev = gated ? P.gate[(long)b * P.gs_b + (long)h * P.gs_h + (long)row * P.gs_s] : 1.0f;
+    float x[4] = {o[0], o[1], o[2], o[3]}, rel[4] = {0.f, 0.f, 0.f, 0.f};
+    ctx_chain<4, true>(x, P.fq_c, P.ctx_before_gate, gated, gatev, rel);
+    if (P.fq_c.en && P.fq_c.dump != nullptr) *reinterpret_cast<unsigned int*>(P.fq_c.dump + r * 64 + 4 * quad) = fq_dump_word(f4{rel[0], rel[1], rel[2], rel[3]}, P.fq_c);
+    o = f4{x[0], x[1], x[2], x[3]};
+  } else {
+    if (P.gate != nullptr) o = o * P.gate[(long)b * P.gs_b + (long)h * P.gs_h + (long)row * P.gs_s];
+  }
   const long ooff = bh_offset(b, P.os_b, h, P.os_h) + (long)row * P.os_s + 4 * quad;
   if (DP.out == IN_F32) *reinterpret_cast<f4*>(reinterpret_cast<float*>(P.o) + ooff) = o;
   else if (DP.out == IN_BF16) *reinterpret_cast<u2*>(reinterpret_cast<unsigned short*>(P.o) + ooff) = u2{pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3])};
@@ -298,10 +372,19 @@ __global__ __launch_bounds__(256) void oeh_attn_decode_combine(const DecodeParam
 }
 
 template <int IN>
-int launch_decode_in(const DecodeParams& DP, hipStream_t st) {
+int launch_decode_in(const DecodeParams& DP, hipStream_t st, const bool fq) {
   const dim3 grid((unsigned)((long)DP.A.nBH * DP.n)), block(256);
   const dim3 cgrid((unsigned)(((long)DP.A.nBH * DP.A.Sq * 16 + 255) / 256));
-  if (DP.A.clip) {
+  if (fq) {
+    if (DP.A.clip || DP.A.fq_p.en) {
+      hipLaunchKernelGGL((oeh_attn_decode_partial<IN, DEC_STATS, true>), grid, block, 0, st, DP);
+      hipLaunchKernelGGL((oeh_attn_decode_partial<IN, DEC_CLIP, true>), grid, block, 0, st, DP);
+      hipLaunchKernelGGL((oeh_attn_decode_combine<true, true>), cgrid, block, 0, st, DP);
+    } else {
+      hipLaunchKernelGGL((oeh_attn_decode_partial<IN, DEC_PLAIN, true>), grid, block, 0, st, DP);
+      hipLaunchKernelGGL((oeh_attn_decode_combine<false, true>), cgrid, block, 0, st, DP);
+    }
+  } else if (DP.A.clip) {
     hipLaunchKernelGGL((oeh_attn_decode_partial<IN, DEC_STATS>), grid, block, 0, st, DP);
     hipLaunchKernelGGL((oeh_attn_decode_partial<IN, DEC_CLIP>), grid, block, 0, st, DP);
     hipLaunchKernelGGL((oeh_attn_decode_combine<true>), cgrid, block, 0, st, DP);
@@ -383,6 +466,56 @@ DecodePlan plan_decode(const oeh_attn_desc* d, int splits, bool host_only, const
 
 int64_t ml_bytes(const oeh_attn_desc* d, int n) { return (((int64_t)d->B * d->H * n * d->Sq * 2 * 4) + 15) & ~(int64_t)15; }
 
+bool any_fq(const oeh_fq_desc* fq) { return fq != nullptr && (fq->scores.enable || fq->probs.enable || fq->ctx.enable); }
+
+// oeh_attn_decode_fq's own refusals, after those of the plan: OEH_EINVAL (a grid that is none), then OEH_ENOTSUP
+int check_fq(const oeh_fq_desc* fq) {
+  const oeh_fq* fs[3] = {&fq->scores, &fq->probs, &fq->ctx};
+  for (const oeh_fq* f : fs) {
+    if (!f->enable) continue;
+    if (!(f->scale > 0.0f) || !std::isfinite(f->scale) || !std::isfinite(f->qmax) || !(f->qmax >= 1.0f) || !(f->zero_point >= 0.0f && f->zero_point <= f->qmax))
+      return OEH_EINVAL;
+  }
+  if (fq->ctx_emit_index) return OEH_ENOTSUP;
+  for (const oeh_fq* f : fs)
+    if (f->enable && f->dump_idx != nullptr && f->qmax > 255.0f) return OEH_ENOTSUP;
+  return OEH_OK;
+}
+
+// fq: null or with at least one quantiser enabled and judged by check_fq
+int run_decode(const oeh_attn_desc* desc, const oeh_fq_desc* fq, const DecodePlan& pl, const void* q, const void* k, const void* v, void* o, void* work, void* stream) {
+  DecodeParams DP;
+  std::memset(&DP, 0, sizeof(DP));
+  AttnParams& P = DP.A;
+  P.q = q; P.k = k; P.v = v; P.o = o;
+  P.B = desc->B; P.H = desc->H; P.Sq = desc->Sq; P.Sk = desc->Sk; P.D = desc->D;
+  P.qs_b = desc->q_stride[0]; P.qs_h = desc->q_stride[1]; P.qs_s = desc->q_stride[2];
+  P.ks_b = desc->k_stride[0]; P.ks_h = desc->k_stride[1]; P.ks_s = desc->k_stride[2];
+  P.vs_b = desc->v_stride[0]; P.vs_h = desc->v_stride[1]; P.vs_s = desc->v_stride[2];
+  P.os_b = desc->o_stride[0]; P.os_h = desc->o_stride[1]; P.os_s = desc->o_stride[2];
+  P.scale = desc->scale_div != 0.0f ? 1.0f / desc->scale_div : desc->scale;  // (a divisor: one more rounding of 6e-8 relative, as in the other 16-bit kernels)
+  P.base = desc->softmax_base;
+  P.clip = desc->clip ? 1 : 0;
+  P.clip_w = (float)((double)desc->eta - (double)desc->gamma);
+  P.clip_g = desc->gamma;
+  P.pad = desc->key_pad_mask; P.pad_f16 = desc->key_pad_dtype == OEH_F16; P.pad_sb = desc->key_pad_stride;
+  P.causal = desc->causal ? 1 : 0; P.clamp_min = desc->clamp_min ? 1 : 0; P.mask_min = desc->mask_min;
+  P.gate = desc->gate; P.gs_b = desc->gate_stride[0]; P.gs_h = desc->gate_stride[1]; P.gs_s = desc->gate_stride[2];
+  P.nBH = desc->B * desc->H;
+  if (fq != nullptr) {
+    P.scale_div = desc->scale_div;  // (the fake-quant forms divide: the quotient feeds the scores quantiser)
+    P.fq_s = make_fq(&fq->scores); P.fq_p = make_fq(&fq->probs); P.fq_c = make_fq(&fq->ctx);
+    P.ctx_before_gate = fq->ctx_quant_before_gate ? 1 : 0;
+  }
+  DP.n = pl.n;
+  DP.chunk = pl.chunk;
+  DP.ml = static_cast<float*>(work);
+  DP.acc = reinterpret_cast<float*>(static_cast<unsigned char*>(work) + ml_bytes(desc, pl.n));
+  DP.out = desc->o_dtype == OEH_F32 ? IN_F32 : (desc->dtype == OEH_BF16 ? IN_BF16 : IN_F16);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return desc->dtype == OEH_BF16 ? launch_decode_in<IN_BF16>(DP, st, fq != nullptr) : launch_decode_in<IN_F16>(DP, st, fq != nullptr);
+}
+
 }  // namespace
 }  // namespace oeh
 
@@ -405,31 +538,26 @@ const char* oeh_attn_decode_variant(const oeh_attn_desc* desc, int32_t splits) {
 int oeh_attn_decode(const oeh_attn_desc* desc, int32_t splits, const void* q, const void* k, const void* v, void* o, void* work, void* stream) {
   const oeh::DecodePlan pl = oeh::plan_decode(desc, splits, false, q, k, v, o, work);
   if (pl.rc != OEH_OK) return pl.rc;
-  oeh::DecodeParams DP;
-  std::memset(&DP, 0, sizeof(DP));
-  oeh::AttnParams& P = DP.A;
-  P.q = q; P.k = k; P.v = v; P.o = o;
-  P.B = desc->B; P.H = desc->H; P.Sq = desc->Sq; P.Sk = desc->Sk; P.D = desc->D;
-  P.qs_b = desc->q_stride[0]; P.qs_h = desc->q_stride[1]; P.qs_s = desc->q_stride[2];
-  P.ks_b = desc->k_stride[0]; P.ks_h = desc->k_stride[1]; P.ks_s = desc->k_stride[2];
-  P.vs_b = desc->v_stride[0]; P.vs_h = desc->v_stride[1]; P.vs_s = desc->v_stride[2];
-  P.os_b = desc->o_stride[0]; P.os_h = desc->o_stride[1]; P.os_s = desc->o_stride[2];
-  P.scale = desc->scale_div != 0.0f ? 1.0f / desc->scale_div : desc->scale;  // (a divisor: one more rounding of 6e-8 relative, as in the other 16-bit kernels)
-  P.base = desc->softmax_base;
-  P.clip = desc->clip ? 1 : 0;
-  P.clip_w = (float)((double)desc->eta - (double)desc->gamma);
-  P.clip_g = desc->gamma;
-  P.pad = desc->key_pad_mask; P.pad_f16 = desc->key_pad_dtype == OEH_F16; P.pad_sb = desc->key_pad_stride;
-  P.causal = desc->causal ? 1 : 0; P.clamp_min = desc->clamp_min ? 1 : 0; P.mask_min = desc->mask_min;
-  P.gate = desc->gate; P.gs_b = desc->gate_stride[0]; P.gs_h = desc->gate_stride[1]; P.gs_s = desc->gate_stride[2];
-  P.nBH = desc->B * desc->H;
-  DP.n = pl.n;
-  DP.chunk = pl.chunk;
-  DP.ml = static_cast<float*>(work);
-  DP.acc = reinterpret_cast<float*>(static_cast<unsigned char*>(work) + oeh::ml_bytes(desc, pl.n));
-  DP.out = desc->o_dtype == OEH_F32 ? oeh::IN_F32 : (desc->dtype == OEH_BF16 ? oeh::IN_BF16 : oeh::IN_F16);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return desc->dtype == OEH_BF16 ? oeh::launch_decode_in<oeh::IN_BF16>(DP, st) : oeh::launch_decode_in<oeh::IN_F16>(DP, st);
+  return oeh::run_decode(desc, nullptr, pl, q, k, v, o, work, stream);
+}
+
+const char* oeh_attn_decode_fq_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq, int32_t splits) {
+  static thread_local char buf[64];
+  const char* name = oeh_attn_decode_variant(desc, splits);
+  if (name == nullptr || !oeh::any_fq(fq)) return name;
+  if (oeh::check_fq(fq) != OEH_OK) return nullptr;
+  std::snprintf(buf, sizeof(buf), "%s/fq", name);
+  return buf;
+}
+
+int oeh_attn_decode_fq(const oeh_attn_desc* desc, const oeh_fq_desc* fq, int32_t splits, const void* q, const void* k, const void* v, void* o, void* work,
+                       void* stream) {
+  const oeh::DecodePlan pl = oeh::plan_decode(desc, splits, false, q, k, v, o, work);
+  if (pl.rc != OEH_OK) return pl.rc;
+  if (!oeh::any_fq(fq)) return oeh::run_decode(desc, nullptr, pl, q, k, v, o, work, stream);
+  const int rc = oeh::check_fq(fq);
+  if (rc != OEH_OK) return rc;
+  return oeh::run_decode(desc, fq, pl, q, k, v, o, work, stream);
 }
 
 }  // extern "C"

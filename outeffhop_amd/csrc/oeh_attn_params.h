@@ -55,4 +55,24 @@ struct AttnParams {
   unsigned long long* stamps; // diagnostic builds only: per-wave s_memtime stamps (null in production)
 };
 
+// The kernels' view of one quantiser from the ABI's oeh_fq (include/oeh.h; a template only so that this header does not need it): host side,
+// shared by every entry point that takes an oeh_fq_desc.
+template <class OehFq>
+inline FqP make_fq(const OehFq* f) {
+  FqP r = {};
+  if (f != nullptr && f->enable) {
+    r.en = 1;
+    r.scale = f->scale;
+    r.rscale = 1.0f / f->scale;
+    r.zp = f->zero_point;
+    r.qmax = f->qmax;
+    r.lo = -f->zero_point;
+    r.hi = f->qmax - f->zero_point;
+    r.dump = f->dump_idx;
+    r.c2 = (float)((double)f->scale * 1.4426950408889634074);  // RN(scale * log2(e)), the product formed in double
+    r.oscale = f->scale;
+  }
+  return r;
+}
+
 }  // namespace oeh

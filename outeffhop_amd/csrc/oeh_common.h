@@ -26,7 +26,7 @@ constexpr float kLog2eLo = 0x1.4ae0bep-26f;  // log2 e - kLog2eHi
 // One fixed-range asymmetric fake-quantiser (uniform_quantizers.py:72-82,114-115,146).
 struct FqP {
   int en;
-  float scale, rscale, zp, qmax;  // rscale = RN(1/scale), formed by the host (oeh_api.hip: make_fq)
+  float scale, rscale, zp, qmax;  // rscale = RN(1/scale), formed by the host (oeh_attn_params.h: make_fq)
   float lo, hi;                   // -zp and qmax - zp: the grid relative to the zero point
   float c2;                       // RN(scale * log2(e)), formed in double by the host: exp(scale * d) = exp2(d * c2) for grid differences d
   float oscale;                   // what a quantised value is written out as: oscale * (idx - zp); = scale, or 1 for the context quantiser

@@ -716,11 +716,14 @@ def _decode_scratch(dev, nbytes: int):
 
 def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0,
                 key_pad_mask: Optional[torch.Tensor] = None, causal: bool = False, clamp_min: bool = False, mask_min: Optional[float] = None,
-                gate: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, splits: int = 0) -> torch.Tensor:
+                gate: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, splits: int = 0,
+                fq: Optional[AttnFakeQuant] = None) -> torch.Tensor:
     """Split-key decode attention (`oeh_attn_decode`): a generation step - q (B,H,Sq,64) with 1 <= Sq <= 16 against k, v (B,H,Sk,64) views of
     a cache (any batch / head / sequence strides, unit head-dim stride; fp16 / bf16) - with the keys of a head split over `splits`
     workgroups (0: the library's rule) and a combine pass.  Masks, gate, `out_dtype` and the result's layout ((B,Sq,H,D)-contiguous) as
     `attn_fwd`; what the entry point does not take (another head dim, more query rows, fp32 storage, gamma > 0) raises OehError -95.
+    `fq`: the fused INT8 chain as in `attn_fwd` (`oeh_attn_decode_fq`: any subset of the three quantisers, index dumps included;
+    `ctx_emit_index` is refused, -95); None or nothing enabled: `oeh_attn_decode` itself.
     Bitwise reproducible; graph-capture safe (a captured call owns its scratch: `_decode_scratch`)."""
     global DECODE_CALLS
     dev = _need_gpu(q, k, v, key_pad_mask, gate)
@@ -768,22 +771,41 @@ def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax: S
     if nbytes < 0:
         _lib.check(int(nbytes), "oeh_attn_decode")
     work = _decode_scratch(dev, int(nbytes))
-    with _on_device(dev):
-        rc = lib.oeh_attn_decode(C.byref(d), int(splits), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(work), _stream())
-    _lib.check(rc, "oeh_attn_decode")
+    if fq is not None and (fq.scores or fq.probs or fq.ctx):
+        fqd = oeh_fq_desc()
+        _fill_fq(fqd.scores, fq.scores)
+        _fill_fq(fqd.probs, fq.probs)
+        _fill_fq(fqd.ctx, fq.ctx)
+        fqd.ctx_quant_before_gate = int(bool(fq.ctx_before_gate))
+        fqd.ctx_emit_index = int(bool(fq.ctx_emit_index))
+        with _on_device(dev):
+            rc = lib.oeh_attn_decode_fq(C.byref(d), C.byref(fqd), int(splits), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(work), _stream())
+        _lib.check(rc, "oeh_attn_decode_fq")
+    else:
+        with _on_device(dev):
+            rc = lib.oeh_attn_decode(C.byref(d), int(splits), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(work), _stream())
+        _lib.check(rc, "oeh_attn_decode")
     DECODE_CALLS += 1
     return out
 
 
-def attn_decode_variant(B, H, Sq, Sk, D=64, dtype=torch.float16, *, clip: bool = False, gamma: float = -0.025, causal: bool = False, splits: int = 0) -> Optional[str]:
-    """Name of the form `attn_decode` would run ("decode16/SP<effective splits>/D64/f16[/clip]"), or None where it refuses (host only)."""
+def attn_decode_variant(B, H, Sq, Sk, D=64, dtype=torch.float16, *, clip: bool = False, gamma: float = -0.025, causal: bool = False, splits: int = 0,
+                        fq: bool = False) -> Optional[str]:
+    """Name of the form `attn_decode` would run ("decode16/SP<effective splits>/D64/f16[/clip][/fq]"; `fq`: with the fused INT8 chain), or None
+    where it refuses (host only)."""
     d = oeh_attn_desc()
     d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[dtype]
     d.scale, d.softmax_base, d.causal = 1.0, 1, int(bool(causal))
     d.mask_min = float(torch.finfo(torch.float32).min)
     if clip:
         d.clip, d.gamma, d.eta = 1, float(gamma), 1.0
-    r = _lib.load().oeh_attn_decode_variant(C.byref(d), int(splits))
+    if fq:
+        fqd = oeh_fq_desc()
+        fqd.scores.enable, fqd.scores.scale, fqd.scores.qmax = 1, 1.0, 255.0
+        fqd.probs.enable, fqd.probs.scale, fqd.probs.qmax = 1, 1.0, 255.0
+        r = _lib.load().oeh_attn_decode_fq_variant(C.byref(d), C.byref(fqd), int(splits))
+    else:
+        r = _lib.load().oeh_attn_decode_variant(C.byref(d), int(splits))
     return None if r is None else r.decode()
 
 

@@ -1289,7 +1289,7 @@ class QuantizedOPTAttentionWithExtras(_QuantAttnBase):
         weights = None
         if fusable:
             merged = attention_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=attention_mask is not None,
-                                    detect_causal=True, gate=gate, fq=fq)
+                                    detect_causal=True, gate=gate, fq=fq, decode=key_value_states is None and past_key_value is not None)
         else:
             ctx, used = None, None
             if fq is None and layer_head_mask is None and not output_attentions and not (self.training and self.dropout > 0.0):

@@ -2,14 +2,17 @@
 """Same-process A/B of the split-key decode kernels (oeh_attn_decode, default split rule) against oeh_attn_fwd on the same buffers - what a
 generation step of OPT-125m ran before the decode entry point existed.
 
-    python tools/decode_bench.py [--out FILE] [--sweep] [--iters N] [--reps R]
+    python tools/decode_bench.py [--out FILE] [--sweep] [--fq] [--iters N] [--reps R]
 
 Shapes: H = 12, D = 64, fp16, causal, Sq = 1, B in {1, 16} x Sk in {512, 2048}, softmax1 and clippedsoftmax1(-.025:1).
 Method: each side's launches are captured into one graph of `iters` calls that walk a ring of K / V buffer sets (so that a call does not find
 the previous call's cache lines), the two graphs are replayed alternately `reps` times, each replay timed by device events; the line reports
 the median per-call time of each side.  Times are event times of graph replays, not tracer kernel times.  --sweep adds the time of every
 explicit split count (how the default rule was chosen).  At B = 16, Sk = 2048 the line also gives the achieved share of 8 TB/s on the
-algorithmic bytes (K + V + q + o)."""
+algorithmic bytes (K + V + q + o).
+--fq: the same comparison with the fused INT8 chain - oeh_attn_decode_fq against oeh_attn_fwd with the same oeh_fq_desc (what a generation step of
+the quantised OPT decoder runs without the decode route); the three ranges are calibrated once per shape and form from the first buffer set
+(percentiles 0.001 / 99.999 of the float intermediates, as the tests do), the context quantised before the (absent) gate."""
 import argparse
 import ctypes as C
 import os
@@ -39,6 +42,20 @@ def make_desc(q, k, v, o, spec):
     return d
 
 
+def calibrated_fq(q, k, v, spec):
+    """an oeh_fq_desc with all three quantisers on, ranges from the float intermediates of this buffer set"""
+    from oracle import oeh_oracle as O
+
+    qn, kn, vn = (t.float().cpu().numpy() for t in (q, k, v))
+    kw = dict(base=spec.base, clip=bool(spec.clip), gamma=spec.gamma, eta=spec.eta, causal=True, clamp_min=True)
+    ctx, fp = O.attn_core(qn, kn, vn, want=("scores", "probs"), **kw)
+    fqd = _lib.oeh_fq_desc()
+    for dst, x in ((fqd.scores, fp["scores"]), (fqd.probs, fp["probs"]), (fqd.ctx, ctx)):
+        ops._fill_fq(dst, ops.FakeQuantSpec.from_delta(*O.quant_range_to_params(*np.percentile(x, (0.001, 99.999)))))
+    fqd.ctx_quant_before_gate = 1
+    return fqd
+
+
 def timed_graph(launch, sets, iters):
     """one graph of `iters` launches walking the buffer ring"""
     launch(sets[0])
@@ -63,6 +80,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--fq", action="store_true", help="with the fused INT8 chain: oeh_attn_decode_fq against oeh_attn_fwd with the same quantisers")
     ap.add_argument("--boundary", action="store_true", help="the shapes around the modules' routing rule instead of the standard four")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--reps", type=int, default=7)
@@ -71,7 +89,7 @@ def main():
         raise SystemExit("decode_bench needs a GPU: there is no CPU timing")
     lib = _lib.load()
     dev = torch.device("cuda", 0)
-    lines = [f"# decode_bench: {lib.oeh_build_info().decode()}",
+    lines = [f"# decode_bench{' --fq' if a.fq else ''}: {lib.oeh_build_info().decode()}",
              f"# event times of graph replays ({a.iters} calls per graph, median of {a.reps} alternating replays); no tracer"]
     H, D, Sq = 12, 64, 1
     gen = torch.Generator().manual_seed(0)
@@ -91,11 +109,16 @@ def main():
                 d = make_desc(*sets[0], spec)
                 work = torch.empty(max(int(lib.oeh_attn_decode_work_bytes(C.byref(d), s)) for s in (0, 64)) // 8 + 2, dtype=torch.int64, device=dev)
                 stream = lambda: ops._stream()  # noqa: E731
+                fqd = calibrated_fq(*sets[0][:3], spec) if a.fq else None
+                fqp = None if fqd is None else C.byref(fqd)
 
-                def fwd(s, d=d):
-                    _lib.check(lib.oeh_attn_fwd(C.byref(d), ops._ptr(s[0]), ops._ptr(s[1]), ops._ptr(s[2]), ops._ptr(s[3]), None, stream()), "oeh_attn_fwd")
+                def fwd(s, d=d, fqp=fqp):
+                    _lib.check(lib.oeh_attn_fwd(C.byref(d), ops._ptr(s[0]), ops._ptr(s[1]), ops._ptr(s[2]), ops._ptr(s[3]), fqp, stream()), "oeh_attn_fwd")
 
-                def dec(s, d=d, splits=0):
+                def dec(s, d=d, splits=0, fqp=fqp):
+                    if fqp is not None:
+                        _lib.check(lib.oeh_attn_decode_fq(C.byref(d), fqp, splits, ops._ptr(s[0]), ops._ptr(s[1]), ops._ptr(s[2]), ops._ptr(s[3]), ops._ptr(work), stream()), "oeh_attn_decode_fq")
+                        return
                     _lib.check(lib.oeh_attn_decode(C.byref(d), splits, ops._ptr(s[0]), ops._ptr(s[1]), ops._ptr(s[2]), ops._ptr(s[3]), ops._ptr(work), stream()), "oeh_attn_decode")
 
                 fwd(sets[0])
@@ -109,10 +132,13 @@ def main():
                     ta.append(replay_ms(ga) * 1e3 / a.iters)
                     tb.append(replay_ms(gb) * 1e3 / a.iters)
                 ua, ub = statistics.median(ta), statistics.median(tb)
-                fwd_name = lib.oeh_attn_variant(C.byref(d), None).decode()
-                dec_name = lib.oeh_attn_decode_variant(C.byref(d), 0).decode()
-                line = (f"B={B:2d} Sk={Sk:4d} {form:24s} {fwd_name:22s} {ua:7.2f} us [{min(ta):.2f}..{max(ta):.2f}]  {dec_name:24s} {ub:7.2f} us [{min(tb):.2f}..{max(tb):.2f}]  "
+                fwd_name = lib.oeh_attn_variant(C.byref(d), fqp).decode()
+                dec_name = lib.oeh_attn_decode_fq_variant(C.byref(d), fqp, 0).decode()
+                wa, wb = (25, 27) if a.fq else (22, 24)  # (the "/fq" names are longer; the plain mode keeps the columns of profiles/decode_bench.txt)
+                line = (f"B={B:2d} Sk={Sk:4d} {form:24s} {fwd_name:{wa}s} {ua:7.2f} us [{min(ta):.2f}..{max(ta):.2f}]  {dec_name:{wb}s} {ub:7.2f} us [{min(tb):.2f}..{max(tb):.2f}]  "
                         f"speed-up {ua / ub:5.2f}x  max |diff| {diff:.1e}  ({nsets} buffer sets)")
+                if fqd is not None:
+                    line += f"  context step {fqd.ctx.scale:.1e}"
                 if B == 16 and Sk == 2048:
                     line += f"  {algo_bytes / 1e6:.1f} MB algorithmic: {algo_bytes / (ub * 1e-6) / 1e12:.2f} TB/s = {100.0 * algo_bytes / (ub * 1e-6) / PEAK_BYTES_PER_S:.1f} % of 8 TB/s"
                 print(line, flush=True)
@@ -121,7 +147,7 @@ def main():
                     parts = []
                     seen = set()
                     for s in (1, 2, 4, 8, 16, 32, 64):
-                        name = lib.oeh_attn_decode_variant(C.byref(d), s).decode()
+                        name = lib.oeh_attn_decode_fq_variant(C.byref(d), fqp, s).decode()
                         if name in seen:
                             continue
                         seen.add(name)

@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256) void fake_quant_range_kernel(const void* __res
   const E* x = reinterpret_cast<const E*>(xin);
   E* y = reinterpret_cast<E*>(yout);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    y[i] = In<IN>::from_f32(f.scale * fq_rel(In<IN>::to_f32(x[i]), f));
+    y[i] = In<IN>::from_f32(f.scale * fq_rel_sat(In<IN>::to_f32(x[i]), f));
 }
 
 int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st) {
@@ -597,7 +597,7 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const void* __restri
     load16_affine<IN>(xp, xv16, alpha, bias != nullptr ? bias + c0 : nullptr);  // (the projection's scale and bias when a raw accumulator comes in)
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      const float rel = fq_rel(xv16[k], f);
+      const float rel = fq_rel_sat(xv16[k], f);
       const unsigned int idx = (unsigned int)(rel + f.zp);
       if ((k & 3) == 0) w[k >> 2] = 0u;
       w[k >> 2] |= (idx ^ 0x80u) << (8 * (k & 3));
@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) void quantize_heads_t_kernel(const void* __res
     load16_affine<IN>(xp, xv16, alpha, bias != nullptr ? bias + h * 64 + d0 : nullptr);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      const float rel = fq_rel(xv16[k], f);
+      const float rel = fq_rel_sat(xv16[k], f);
       tile[d0 + k][row] = (unsigned char)(((unsigned int)(rel + f.zp)) ^ 0x80u);
       yv[k] = f.scale * rel;
     }

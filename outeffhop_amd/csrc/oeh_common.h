@@ -51,6 +51,22 @@ __device__ __forceinline__ float fq_quot(float x, const FqP& f) {
 // clamp(rint(x/scale) + zp, 0, qmax) - zp (all operands are integers far below 2^24, or the clamp saturates either way)
 // for two instructions less per element; x_q = scale * rel, and rel itself is the integer the P operand carries.
 __device__ __forceinline__ float fq_rel(float x, const FqP& f) { return __builtin_amdgcn_fmed3f(__builtin_rintf(fq_quot(x, f)), f.lo, f.hi); }
+// The quantiser of the stand-alone kernels (fake-quant, range fake-quant, the int8 producers), whose
+// input is arbitrary: where |x| / scale overflows fp32 (x = +-inf, 3e38 against a step below 1, 1e30 against 1e-9) fq_quot's first
+// product is +-inf, its residual the opposite infinity and the corrected quotient NaN, which the median above turns into `lo` - index 0
+// for a POSITIVE saturating input where the reference's clamp(round(x / scale) + zp, 0, qmax) gives qmax.  With the first product
+// clamped to a finite magnitude the residual keeps the sign of x and the corrected quotient is x's infinity (or a finite value far
+// beyond any grid); nothing changes for products below 3e38.  The attention kernels' inner loops keep fq_rel: there the only
+// quotient that overflows is the negative mask value's, whose index is `lo` either way.  The projection GEMM's epilogue (oeh_gemm.hip)
+// keeps fq_rel / fq_quot too and is open to the same defect where alpha * acc + bias over the step overflows fp32.
+__device__ __forceinline__ float fq_quot_sat(float x, const FqP& f) {
+  const float q0 = __builtin_amdgcn_fmed3f(x * f.rscale, -3.0e38f, 3.0e38f);
+  const float r = __builtin_fmaf(-q0, f.scale, x);
+  return __builtin_fmaf(r, f.rscale, q0);
+}
+// (+ 0: a quotient in (-0.5, 0) rounds to -0 and lo = -zp is -0 at zp = 0, while the reference's (idx - zp) is never -0 - the written value
+// scale * rel would carry the sign)
+__device__ __forceinline__ float fq_rel_sat(float x, const FqP& f) { return __builtin_amdgcn_fmed3f(__builtin_rintf(fq_quot_sat(x, f)), f.lo, f.hi) + 0.0f; }
 // (A packed form of the quotient - v_pk_mul_f32 / v_pk_fma_f32 on element pairs - measured much slower in the full-row
 // kernel: 55 vs 39 us on the INT8 OPT shape, 25.5 vs 13.9 us on BERT-base.  Packed fp32 buys no throughput on this chip
 // anyway: tools/pk_bench.hip times 16 scalar VALU operations at 37.7 cycles per wave and the same arithmetic as 8 packed

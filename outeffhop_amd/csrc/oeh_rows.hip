@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void oeh_fake_quant_vec_kernel(const void* __r
     unsigned int packed[N / 4];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      const float rel = fq_rel(v[k], f);
+      const float rel = fq_rel_sat(v[k], f);
       if (k % 4 == 0) packed[k / 4] = 0;
       packed[k / 4] |= ((unsigned int)(rel + f.zp)) << (8 * (k % 4));
       v[k] = f.scale * rel;
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void oeh_fake_quant_vec_kernel(const void* __r
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     typedef typename In<IN>::elem E;
     for (long i = nvec * N; i < n; ++i) {
-      const float rel = fq_rel(In<IN>::to_f32(reinterpret_cast<const E*>(xin)[i]), f);
+      const float rel = fq_rel_sat(In<IN>::to_f32(reinterpret_cast<const E*>(xin)[i]), f);
       if (idx_out) idx_out[i] = (unsigned char)(rel + f.zp);
       if (yout) reinterpret_cast<E*>(yout)[i] = In<IN>::from_f32(f.scale * rel);
     }

@@ -58,7 +58,7 @@ __device__ __forceinline__ float fq_rel(float x, const FqP& f) { return __builti
 // clamped to a finite magnitude the residual keeps the sign of x and the corrected quotient is x's infinity (or a finite value far
 // beyond any grid); nothing changes for products below 3e38.  The attention kernels' inner loops keep fq_rel: there the only
 // quotient that overflows is the negative mask value's, whose index is `lo` either way.  The projection GEMM's epilogue (oeh_gemm.hip)
-// keeps fq_rel / fq_quot too and is open to the same defect where alpha * acc + bias over the step overflows fp32.
+// uses the saturating forms: alpha * acc + bias, or its quotient by the step, can overflow fp32 (tests/test_proj_branches_gpu.py).
 __device__ __forceinline__ float fq_quot_sat(float x, const FqP& f) {
   const float q0 = __builtin_amdgcn_fmed3f(x * f.rscale, -3.0e38f, 3.0e38f);
   const float r = __builtin_fmaf(-q0, f.scale, x);

@@ -23,8 +23,8 @@
 // first version swizzled by (r >> 2) & 3, right for groups of 16 consecutive lanes: SQ_LDS_BANK_CONFLICT was half of the LDS cycles);
 // the DMA writes whole kilobytes and applies the swizzle to its SOURCE address.  Workgroup -> tile: the eight XCDs take contiguous ranges of row tiles, all column tiles of a row tile on
 // one XCD (an activation tile is fetched once per XCD and hit in its L2 by the other column tiles).
-// Epilogue: 7 vector instructions per output (fma, the three-instruction exact quotient, rint, + zero point, v_cvt_pk_u8_f32 whose
-// saturation is the clamp; 9 with values), index bytes through LDS images (4 x 4 byte transposes inside lane quads for the row-major
+// Epilogue: 8 vector instructions per output (fma, the three-instruction exact quotient with its first product clamped to a finite value -
+// oeh_common.h: fq_quot_sat -, rint, + zero point, v_cvt_pk_u8_f32 whose saturation is the clamp; 11 with values), index bytes through LDS images (4 x 4 byte transposes inside lane quads for the row-major
 // one) so that they leave as whole 16-byte pieces of contiguous output; values straight from the accumulator layout, write-through.
 // Measured (one MI355X, M = 8192, K = 768): q/k/v (N = 2304) from operand pairs 74 us with the (k, v) values, 63 us without, against 107 /
 // 91 us for the library GEMM (hipBLASLt, 70 us) + three quantiser passes; from the fp32 activations 76 / 70 us against 116 / 100 with the
@@ -36,6 +36,7 @@
 
 #include <cstdio>
 #include <type_traits>
+#include <utility>
 #include <cstdlib>
 
 namespace oeh {
@@ -74,6 +75,12 @@ struct Geo {
 #else
 #define GEMM_DBG(P) 0
 #endif
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression in its body
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
 
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef int i4 __attribute__((ext_vector_type(4)));
@@ -384,8 +391,11 @@ __global__ __launch_bounds__(256, (LOOP == 1 ? 1 : MI * NJ > 16 ? 2 : 4)) void o
 #pragma unroll
     for (int j = 0; j < NJ; ++j) biav[j] = P.bias[min(n0 + 16 * NJ * wn + 16 * j + l15, P.N - 1)];
     const unsigned sel_t = (unsigned)c4 | ((unsigned)(4 + c4) << 8);   // v_perm_b32 selector: byte c4 of the second / of the first source
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
+    // The column tiles are expanded at COMPILE time (static_for), not by `#pragma unroll`: the optimizer drops a full unroll above a size threshold, which
+    // the 128 x 288 forms reach with two more instructions per output - acc[][j] then becomes a run-time-indexed array in scratch memory, and the
+    // pipelined loops' accumulators are stored there straight after their inline-asm MFMAs, in front of the hazard padding above (stale values).
+    static_for<NJ>([&](auto jc) __attribute__((always_inline)) {
+      constexpr int j = decltype(jc)::value;
       const int nl = 16 * NJ * wn + 16 * j;          // tile-local first column (wave-uniform)
       const int n = n0 + nl;
       if (n < P.N) {
@@ -418,7 +428,8 @@ __global__ __launch_bounds__(256, (LOOP == 1 ? 1 : MI * NJ > 16 ? 2 : 4)) void o
               const bool rows_in = m0 + 16 * MI * wm + 16 * i < P.M && !(GEMM_DBG(P) & 16);  // (M % 16 == 0: a 16-row tile is inside or outside as a whole)
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                const float rel = fq_rel(__builtin_fmaf(accv(i, r), alpha, bia), f);
+                // (fq_rel_sat: alpha * acc + bias, or its quotient by the step, may overflow fp32 - index 255 / 0 by the sign, as the reference's clamp; rel is never -0)
+                const float rel = fq_rel_sat(__builtin_fmaf(accv(i, r), alpha, bia), f);
                 word = __builtin_amdgcn_cvt_pk_u8_f32(rel + f.zp, r, word);
                 if (rows_in) store_wt4_s(ybase + (long)(16 * i + r) * y_ld * 4, y_voff, f.scale * rel);
               }
@@ -426,7 +437,7 @@ __global__ __launch_bounds__(256, (LOOP == 1 ? 1 : MI * NJ > 16 ? 2 : 4)) void o
               // (no values wanted: the conversion's saturation to [0, 255] is the clamp)
 #pragma unroll
               for (int r = 0; r < 4; ++r)
-                word = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(fq_quot(__builtin_fmaf(accv(i, r), alpha, bia), f)) + f.zp, r, word);
+                word = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(fq_quot_sat(__builtin_fmaf(accv(i, r), alpha, bia), f)) + f.zp, r, word);
             }
             word ^= 0x80808080u;
             if (IDXC) *reinterpret_cast<unsigned*>(img_c + (nl + l15) * G_PITCH_C + rl) = word;
@@ -451,7 +462,7 @@ __global__ __launch_bounds__(256, (LOOP == 1 ? 1 : MI * NJ > 16 ? 2 : 4)) void o
         } else if (idx_r) body(F_{}, T_{}, F_{});
         else if (idx_c) body(F_{}, F_{}, T_{});
       }
-    }
+    });
     barrier_mem();
     if (GEMM_DBG(P) & 32) return;
     // The three segments' output pointers and layouts in scalar registers, selected per piece (round 5: the loops below indexed P.seg[] with a per-lane

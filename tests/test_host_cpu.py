@@ -480,3 +480,43 @@ def test_autograd_routes_to_the_differentiable_torch_op_path(monkeypatch):
         la, lb, x, z = run_train_toy(g, case, "cpu")
         check_train_toy(g, case, la, lb, x, z, rtol=2e-4, atol=2e-6)
 
+
+
+def test_projection_gemm_refusals_before_any_launch():
+    """`oeh_proj_quant_i8` (csrc/oeh_api.hip) refuses on the host, before anything is launched - dummy pointers, no GPU: what
+    tests/test_abi.py does not already try (no segments, K % 32, S % 16, pairs with lda < 2K, a first segment with neither output)."""
+    import ctypes as C
+
+    from outeffhop_amd import _lib
+
+    lib = _lib.load()
+    EINVAL, ENOTSUP, EALIGN = -22, -95, -14
+    p16 = 4096   # a 16-byte aligned dummy address
+
+    def call(pairs=0, B=2, S=64, K=64, E=128, n=2, lda=None, ldw=None, **seg0):
+        segs = (_lib.oeh_proj_seg * 3)()
+        for g in segs:
+            g.alpha, g.scale, g.zero_point, g.out, g.y, g.y_stride_row, g.transpose, g.acc_add = 1.0, 0.5, 3.0, p16, None, E, 0, None
+        for k, v in seg0.items():
+            which, field = (1, k[:-1]) if k.endswith("1") else (0, k)
+            setattr(segs[which], field, v)
+        one = C.c_void_p(p16)
+        return lib.oeh_proj_quant_i8(one, pairs, one, one, B, S, K, E, n, segs, (2 if pairs == 1 else 1) * K if lda is None else lda, K if ldw is None else ldw, None)
+
+    assert call(pairs=3, K=96) == ENOTSUP                                # int8: a K step is 64 elements
+    assert call(pairs=4) == EINVAL and call(pairs=-1) == EINVAL
+    assert call(ldw=32) == EINVAL and call(lda=63) == EINVAL             # rows shorter than K
+    assert call(lda=68) == EALIGN and call(ldw=68) == EALIGN             # row pitch not a multiple of 16 bytes (fp16: 8 elements)
+    assert call(B=1 << 20, S=64, K=32) == ENOTSUP                        # 32-bit lane offsets of a: B S lda 2 = 2^32
+    assert call(B=1, S=16, K=32, E=1 << 26, n=3) == ENOTSUP              # ... of w: n E ldw 2 = 3 * 2^32
+    assert call(y=p16, y_stride_row=1 << 27) == ENOTSUP                  # ... of the value stores: (12 y_stride_row + 16) 4 >= 2^32
+    assert call(y=p16, y_stride_row=127) == EINVAL                       # y_stride_row < E
+    assert call(out=p16 + 8) == EALIGN                                   # out: 16-byte pieces
+    assert call(y=p16 + 2) == EALIGN                                     # y: fp32
+    assert call(pairs=3, acc_add=p16 + 2) == EALIGN                      # acc_add: int32
+    for zp in (0.5, -1.0, 256.0, float("nan")):
+        assert call(zero_point=zp) == EINVAL, zp                         # an integer in [0, 255]
+    for sc in (0.0, -1.0, float("nan")):
+        assert call(scale=sc) == EINVAL, sc
+    assert call(out1=None) == EINVAL                                     # the second segment with neither out nor y
+    assert call(zero_point1=300.0) == EINVAL

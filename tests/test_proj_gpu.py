@@ -102,10 +102,10 @@ def test_projection_gemm_refuses_what_it_does_not_do():
 
 
 def test_projection_gemm_random_shapes_against_the_library_path():
-    """Random (B, S, H, K), one to three segments, both operand forms, values on / off per segment, both tile shapes (the library
-    picks by problem size; the diagnostic switch forces the other): every index within one step of the library GEMM + quantiser
-    pass on the same operands, all but a few in 10^5 equal; values consistent with the indices."""
-    import os
+    """Random (B, S, H, K), one to three segments, both operand forms, values on / off per segment, on the tile the library picks by
+    problem size (these shapes all take the 64 x 192 one; tests/test_proj_branches_gpu.py reaches every kernel by shape): every index
+    within one step of the library GEMM + quantiser pass on the same operands, all but a few in 10^5 equal; values consistent with
+    the indices."""
     from outeffhop_amd import ops
 
     rng = np.random.default_rng(7)

@@ -16,6 +16,7 @@
 #ifndef OEH_H_
 #define OEH_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -436,6 +437,42 @@ const char* oeh_attn_decode_variant(const oeh_attn_desc* desc, int32_t splits);
 int oeh_attn_decode_fq(const oeh_attn_desc* desc, const oeh_fq_desc* fq, int32_t splits, const void* q, const void* k, const void* v, void* o,
                        void* work, void* stream);
 const char* oeh_attn_decode_fq_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq, int32_t splits);
+
+/* Outlier statistics (oeh_stats.hip): the two numbers the reference reports its results in - the maximum infinity norm and the average
+ * kurtosis of layer outputs (validate_clm.py:565-621, validate_mlm.py:497-533, validate_vit1.py:620-693, run_clm_ddp.py:735-760, with
+ * `kurtosis` of transformers_language/utils.py:9-20) - for every row of a (rows, cols) array in ONE pass over HBM, replacing the eager
+ * chain x.norm(p=inf), mean, std, (x - mu) ** 4, mean and its one .item() per sample and statistic.
+ * x: fp16 / bf16 / fp32, element (r, c) at x[r * row_stride + c], row_stride >= cols; rows may start at any element (no 16-byte rule).
+ * stats: (rows, 4) fp32, 16-byte aligned:
+ *   [0] inf_norm = max |x|                                  (bit for bit)
+ *   [1] kurtosis = mean((x - mu)^4) / (std^4 + eps)         (utils.py:9-20)
+ *   [2] mean
+ *   [3] std, unbiased: sqrt(sum (x - mu)^2 / (cols - 1))    (torch.std)
+ * evaluated from central moments about per-chunk means in fp32 (never raw power sums), corrected and merged in float64 (Chan / Pebay
+ * pairwise updates) in a fixed order: bitwise reproducible.  The values are the float64 results rounded to fp32 for 16-bit inputs too;
+ * the reference would evaluate (x - mu)^4 in the storage type there and overflow fp16.
+ * Special values: a NaN in a row -> inf_norm = NaN, kurtosis = NaN; a +-inf (and no NaN) -> inf_norm = +inf, kurtosis = NaN (mean and std
+ * are NaN in both cases); a constant row -> std = 0 and kurtosis = 0 exactly (eps > 0); cols == 1 -> inf_norm = |x|, mean = x, std and
+ * kurtosis NaN.  fp32 data with |x - mean| >= 2^31 overflows the fourth power as it does in the reference: no accuracy is promised, the
+ * call returns normally.
+ * meter (or NULL): device double[4] = {sum_inf, n_inf, sum_kurt, n_kurt}, 8-byte aligned - the running sums that the reference's
+ * AverageMeter.update(v.item()) forms on the host.  The last launch of the call adds this call's rows, in ascending order, in float64,
+ * as selected by `accumulate`: bit 0 (1) the inf-norms, bit 1 (2) the kurtoses; 0 leaves meter untouched.
+ * Rows of at most OEH_STATS_WAVE_COLS elements: one wave per row, one launch, no work buffer.  Longer rows: one workgroup per
+ * (row, chunk of OEH_STATS_CHUNK elements, cut at the row's own 16-byte boundaries) writes a record of OEH_STATS_RECORD_BYTES to `work`
+ * and a second launch merges them.  work: device scratch of oeh_outlier_stats_work_bytes(rows, cols) bytes (0 for the short-row form; 0
+ * for rows or cols < 1), 8-byte aligned, contents irrelevant before and after.  Plain launches in a linear chain: no atomics, no
+ * allocation, no host synchronisation, graph-capture safe.
+ * Refusals, before any launch: OEH_EINVAL - x or stats NULL, rows < 1 or cols < 1, row_stride < cols, a dtype other than OEH_F16 /
+ * OEH_BF16 / OEH_F32, eps < 0 or NaN, accumulate outside 0..3 or non-zero with meter == NULL, work == NULL where work_bytes > 0;
+ * OEH_EALIGN - stats not 16-byte aligned, meter or work not 8-byte aligned, x not aligned to its element; OEH_ENOTSUP - 2^31 or more
+ * (row, chunk) pairs. */
+#define OEH_STATS_WAVE_COLS 2040
+#define OEH_STATS_CHUNK 8192
+#define OEH_STATS_RECORD_BYTES 48
+size_t oeh_outlier_stats_work_bytes(int64_t rows, int64_t cols);
+int oeh_outlier_stats(const void* x, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, double eps, float* stats, double* meter,
+                      int32_t accumulate, void* work, void* stream);
 
 /* library information (host side, no device work) */
 int oeh_abi_version(void);

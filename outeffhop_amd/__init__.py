@@ -3,7 +3,7 @@
 Python host surface mirroring the reference's plugin interface:
     SOFTMAX_MAPPING, AttentionGateType, BertSelfAttentionWithExtras, OPTAttentionWithExtras,
     ViTSelfAttentionWithExtras, Association / Hopfield / HopfieldPooling, QuantizedActivation,
-    Quantized{Bert,OPT}...AttentionWithExtras
+    Quantized{Bert,OPT}...AttentionWithExtras, kurtosis / inf_norm / OutlierMeter (the reference's result metrics)
 over the C-ABI library `lib/liboeh_hip.so` (include/oeh.h).  There is no CPU implementation in this package:
 every op raises if the HIP library is missing or a tensor is not on a GPU.
 """
@@ -13,7 +13,8 @@ from .autograd_attention import fused_attention  # noqa: F401
 from .bert_attention import BertSelfAttentionWithExtras  # noqa: F401
 from .hopfield import Association, Hopfield, HopfieldPooling  # noqa: F401
 from .opt_attention import OPTAttentionWithExtras  # noqa: F401
-from .ops import AttnFakeQuant, FakeQuantSpec, SoftmaxSpec, attn_fwd, fake_quant, softmax_rows  # noqa: F401
+from .ops import AttnFakeQuant, FakeQuantSpec, SoftmaxSpec, attn_fwd, fake_quant, inf_norm, kurtosis, outlier_stats, softmax_rows  # noqa: F401
+from .outliers import OutlierMeter  # noqa: F401
 from .quantization import (  # noqa: F401
     AsymmetricUniformQuantizer,
     QMethods,

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("OEH_LIB") or os.path.join(_HERE, "lib", "liboeh_hip.s
 ABI_VERSION = 6  # include/oeh.h: OEH_ABI_VERSION
 CALIB_WORK_BYTES = 36864  # include/oeh.h: OEH_CALIB_WORK_BYTES
 DECODE_MAX_SPLITS = 64  # include/oeh.h: OEH_DECODE_MAX_SPLITS
+STATS_WAVE_COLS, STATS_CHUNK, STATS_RECORD_BYTES = 2040, 8192, 48  # include/oeh.h: OEH_STATS_WAVE_COLS, OEH_STATS_CHUNK, OEH_STATS_RECORD_BYTES
 OEH_F16, OEH_BF16, OEH_F32, OEH_I8 = 0, 1, 2, 3
 OEH_SOFTMAX_VANILLA, OEH_SOFTMAX_ONE = 0, 1
 
@@ -84,6 +85,7 @@ EXPORTS = (
     "oeh_abi_version", "oeh_build_info", "oeh_strerror", "oeh_attn_variant",
     "oeh_attn_fwd_ex", "oeh_attn_variant_ex",
     "oeh_attn_decode_work_bytes", "oeh_attn_decode", "oeh_attn_decode_variant", "oeh_attn_decode_fq", "oeh_attn_decode_fq_variant",
+    "oeh_outlier_stats_work_bytes", "oeh_outlier_stats",
 )
 
 _lib = None
@@ -165,6 +167,10 @@ def load() -> C.CDLL:
     lib.oeh_attn_decode_fq.restype = C.c_int
     lib.oeh_attn_decode_fq_variant.argtypes = [C.POINTER(oeh_attn_desc), C.POINTER(oeh_fq_desc), i32]
     lib.oeh_attn_decode_fq_variant.restype = C.c_char_p
+    lib.oeh_outlier_stats_work_bytes.argtypes = [i64, i64]
+    lib.oeh_outlier_stats_work_bytes.restype = C.c_size_t
+    lib.oeh_outlier_stats.argtypes = [vp, i64, i64, i64, i32, f64, vp, vp, i32, vp, vp]
+    lib.oeh_outlier_stats.restype = C.c_int
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

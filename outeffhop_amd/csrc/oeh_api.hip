@@ -30,6 +30,9 @@ int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_
 int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st);
 int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_hi, double momentum, int first, double* state, void* work,
                           hipStream_t st);
+long stats_chunks(long cols);
+int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,
+                         hipStream_t st);
 int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st);
 int launch_attn_calibrate(const AttnParams& P, int in, int which, const double* s_range, const double* p_range, float qmax, double eps, double q_lo,
                           double q_hi, double momentum, int first, double* state, void* work, hipStream_t st);
@@ -538,6 +541,23 @@ int oeh_percentile_ema(const void* x, int64_t n, int32_t dtype, double q_lo, dou
   if (!(q_lo >= 0.0 && q_lo <= 100.0 && q_hi >= 0.0 && q_hi <= 100.0) || !(momentum >= 0.0 && momentum <= 1.0)) return OEH_EINVAL;
   if ((reinterpret_cast<uintptr_t>(work) & 7) != 0 || (reinterpret_cast<uintptr_t>(state) & 7) != 0) return OEH_EALIGN;
   return oeh::launch_percentile_ema(x, n, dtype, q_lo, q_hi, momentum, first ? 1 : 0, state, work, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t oeh_outlier_stats_work_bytes(int64_t rows, int64_t cols) {
+  if (rows < 1 || cols < 1) return 0;
+  return (size_t)rows * (size_t)oeh::stats_chunks(cols) * OEH_STATS_RECORD_BYTES;
+}
+
+int oeh_outlier_stats(const void* x, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, double eps, float* stats, double* meter,
+                      int32_t accumulate, void* work, void* stream) {
+  if (x == nullptr || stats == nullptr || rows < 1 || cols < 1 || row_stride < cols || !dtype_ok(dtype) || !(eps >= 0.0)) return OEH_EINVAL;
+  if (accumulate < 0 || accumulate > 3 || (accumulate != 0 && meter == nullptr)) return OEH_EINVAL;
+  const bool need_work = oeh::stats_chunks(cols) > 0;
+  if (need_work && work == nullptr) return OEH_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(stats) & 15) != 0 || (reinterpret_cast<uintptr_t>(meter) & 7) != 0 || (need_work && (reinterpret_cast<uintptr_t>(work) & 7) != 0) ||
+      (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem_bytes(dtype) - 1)) != 0)
+    return OEH_EALIGN;
+  return oeh::launch_outlier_stats(x, rows, cols, row_stride, dtype, eps, stats, meter, accumulate, work, reinterpret_cast<hipStream_t>(stream));
 }
 
 int oeh_fake_quant_range(const void* x, void* y, int64_t n, int32_t dtype, const double* xmin_xmax, int32_t n_bits, double eps,

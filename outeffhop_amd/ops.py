@@ -985,6 +985,78 @@ def minmax(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- outlier statistics (include/oeh.h: oeh_outlier_stats): the reference's two result metrics, per sample, in one pass
+
+STATS_WAVE_COLS = _lib.STATS_WAVE_COLS  # W: rows up to this length take the one-wave, one-launch form (no work buffer)
+STATS_CHUNK = _lib.STATS_CHUNK          # C: elements per (row, chunk) workgroup of the long-row form
+STATS_INF_NORM, STATS_KURTOSIS, STATS_MEAN, STATS_STD = 0, 1, 2, 3  # columns of the result
+_stats_work = {}  # (device index, stream handle) -> the chunk records of that stream
+
+
+def _stats_scratch(dev, nbytes: int):
+    """The current stream's chunk-record buffer for `oeh_outlier_stats` on `dev`: kept, grown and bounded as `_decode_scratch` keeps the
+    split-key scratch, with a buffer of its own for a call under graph capture (it then lives in the graph's pool)."""
+    with _on_device(dev):
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    work = _stats_work.get(key)
+    if work is None or work.numel() * 8 < nbytes:
+        if len(_stats_work) >= 32:
+            _stats_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
+        work = _stats_work[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    return work
+
+
+def outlier_stats(x: torch.Tensor, eps: float = 1e-6, meter: Optional[torch.Tensor] = None, accumulate: int = 0, *,
+                  out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-sample (inf_norm, kurtosis, mean, std) of `x` viewed as (x.shape[0], -1): a (rows, 4) fp32 tensor from one pass over the
+    data, no host synchronisation (`include/oeh.h: oeh_outlier_stats`; validate_clm.py:565-586 with transformers_language/utils.py:9-20).
+    A view whose rows are dense and a row stride apart is read in place; anything else is made contiguous.  meter: float64[4] on x's
+    GPU, {sum_inf, n_inf, sum_kurt, n_kurt}; accumulate: 1 adds this call's inf-norms, 2 its kurtoses, 3 both.  out / work: caller's
+    buffers (tests); by default the result is new and the chunk records live in one buffer per stream."""
+    dev = _need_gpu(x, meter, out, work)
+    if x.dtype not in _DT:
+        raise ValueError(f"unsupported dtype {x.dtype}")
+    if x.dim() < 2:
+        raise ValueError("outlier_stats needs at least 2 dimensions: (samples, ...)")
+    x = x.detach()
+    rows = x.shape[0]
+    cols = x.numel() // rows if rows else 0
+    if not (rows >= 1 and cols >= 1 and (x[0].is_contiguous() or cols == 1) and (rows == 1 or x.stride(0) >= cols)):
+        x = x.contiguous()
+    row_stride = x.stride(0) if rows > 1 else cols
+    if meter is not None and (meter.dtype != torch.float64 or meter.numel() != 4 or not meter.is_contiguous()):
+        raise ValueError("meter must be a contiguous float64 tensor of 4 elements")
+    if out is None:
+        out = torch.empty((rows, 4), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, 4) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape (rows, 4)")
+    lib = _lib.load()
+    nbytes = lib.oeh_outlier_stats_work_bytes(rows, cols)
+    if work is None:
+        work = _stats_scratch(dev, nbytes) if nbytes else None
+    elif work.numel() * work.element_size() < nbytes:
+        raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, the call needs {nbytes}")
+    with _on_device(dev):
+        rc = lib.oeh_outlier_stats(_ptr(x), rows, cols, row_stride, _DT[x.dtype], float(eps), _ptr(out), _ptr(meter), int(accumulate), _ptr(work), _stream())
+    _lib.check(rc, "oeh_outlier_stats")
+    return out
+
+
+def kurtosis(x: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """x - (B, d).  The reference's `kurtosis` (transformers_language/utils.py:9-20): mean((x - mu)^4) / (std^4 + eps) per row, as a
+    (B,) fp32 tensor.  Deviation: the result is fp32, from fp32 / float64 arithmetic, for fp16 and bf16 inputs too - the reference
+    evaluates (x - mu) ** 4 in the input's type there, which overflows fp16 from |x - mu| = 16 on."""
+    return outlier_stats(x, eps)[:, STATS_KURTOSIS]
+
+
+def inf_norm(x: torch.Tensor) -> torch.Tensor:
+    """x.view(B, -1).norm(dim=1, p=inf) (validate_clm.py:575) as a (B,) fp32 tensor - fp32 for 16-bit inputs as well (the value is exact
+    in either type)."""
+    return outlier_stats(x)[:, STATS_INF_NORM]
+
+
 # ---- training: the forward with its row statistic and the fused backward (include/oeh.h: oeh_attn_fwd_train / oeh_attn_bwd)
 def _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min):
     """Descriptor + the mask views it points into, for the training entry points (fp16 / bf16, D = 64; the library refuses the rest)."""

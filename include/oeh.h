@@ -474,6 +474,46 @@ size_t oeh_outlier_stats_work_bytes(int64_t rows, int64_t cols);
 int oeh_outlier_stats(const void* x, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, double eps, float* stats, double* meter,
                       int32_t accumulate, void* work, void* stream);
 
+/* Quantisation-error search (oeh_qmse.hip): the squared error of K candidate quantiser grids on one array, every candidate from ONE
+ * read of the data - the loss_fx of the reference's MSE range estimator (quantization/range_estimators.py:134-142: fake-quantise,
+ * subtract, square, sum, .cpu(), once per candidate range; 100 times per tensor and batch in the 1-D grid search, 100 * 64 * 2 times in
+ * the 2-D search).
+ * x: n elements of fp16 / bf16 / fp32, dense, starting at any element (no 16-byte rule); nothing outside [x, x + n) is read.
+ * cand: K records of OEH_QMSE_CAND_BYTES = 16 bytes in device memory, 16-byte aligned, four floats each:
+ *   [0] scale > 0    the grid's step (the quantiser's clamp(delta, eps))
+ *   [1] lo           int_min - zero_point   (lowest index relative to the zero point)
+ *   [2] hi           int_max - zero_point
+ *   [3] reserved     (ignored; write 0)
+ * One record type covers every grid: symmetric signed (-128, 127), symmetric unsigned (0, 255), asymmetric (-zp, qmax - zp), any
+ * n_bits <= 16.  RN(1 / scale) is formed inside the kernel by a true division.  scale <= 0 is the caller's error and is not detected.
+ * loss: K float64 in device memory, 8-byte aligned: loss[k] = sum_i term_i(k), or loss[k] += that sum (ONE float64 add) when
+ * `accumulate` is not 0.  The term is defined in fp32, each operation rounded separately, exactly as the reference's eager ops round it
+ * (uniform_quantizers.py:114-115,146; 16-bit elements are widened to fp32 first - the reference would square and sum in the storage
+ * type there and overflow fp16):
+ *   q = RN(x_i / scale_k);  r = clamp(rint(q), lo_k, hi_k)  (ties to even);  y = fl32(scale_k * r);  d = fl32(x_i - y);  term = fl32(d * d)
+ * At most 32 terms are added in fp32, pairwise, before the sum continues in float64 in a fixed order:
+ *   |loss[k] - L64[k]| <= 6 * 2^-24 * L64[k],   L64 = the float64 sum of the fp32 terms;   bitwise reproducible.
+ * A call of K <= OEH_QMSE_F64_K candidates adds in float64 from the first term (loss[k] = L64[k] up to float64 rounding): such calls are
+ * the steps of a sequential search (golden section), whose result moves with the noise of its loss - the reference's fp32 sums move the
+ * range it finds by 1e-4 - and whose pass over the data is bound by the read, not by the arithmetic.
+ * A non-finite element makes the losses it affects inf / NaN; the call returns normally.
+ * A workgroup keeps a chunk of OEH_QMSE_CHUNK elements (cut at the array's own 16-byte boundaries) in registers and loops over the
+ * candidates; at most OEH_QMSE_MAX_BLOCKS workgroups (beyond that each takes several chunks) write one float64 per candidate to `work`
+ * and a merge launch adds them in a fixed order.  K is unbounded: it is cut into slices of OEH_QMSE_SLICE candidates, each a pass over the
+ * data and a merge.  work: device scratch of oeh_quant_mse_work_bytes(n, K) bytes (0 for n < 1 or K < 1), 8-byte aligned, contents
+ * irrelevant before and after.  Plain launches in a linear chain: no atomics, no allocation, no host synchronisation, graph-capture
+ * safe; the launch geometry depends on (n, K) only.
+ * Refusals, before any launch: OEH_EINVAL - x, cand, loss or work NULL, n < 1, K < 1, a dtype other than OEH_F16 / OEH_BF16 / OEH_F32;
+ * OEH_EALIGN - cand not 16-byte aligned, loss or work not 8-byte aligned, x not aligned to its element. */
+#define OEH_QMSE_CHUNK 8192
+#define OEH_QMSE_SLICE 256
+#define OEH_QMSE_MAX_BLOCKS 1024
+#define OEH_QMSE_CAND_BYTES 16
+#define OEH_QMSE_F64_K 4
+size_t oeh_quant_mse_work_bytes(int64_t n, int32_t K);
+int oeh_quant_mse(const void* x, int64_t n, int32_t dtype, const float* cand, int32_t K, double* loss, int32_t accumulate, void* work,
+                  void* stream);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

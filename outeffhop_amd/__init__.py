@@ -17,6 +17,8 @@ from .ops import AttnFakeQuant, FakeQuantSpec, SoftmaxSpec, attn_fwd, fake_quant
 from .outliers import OutlierMeter  # noqa: F401
 from .quantization import (  # noqa: F401
     AsymmetricUniformQuantizer,
+    MSE_Estimator,
+    OptMethod,
     QMethods,
     QuantizationManager,
     QuantizedActivation,

@@ -16,6 +16,7 @@ ABI_VERSION = 6  # include/oeh.h: OEH_ABI_VERSION
 CALIB_WORK_BYTES = 36864  # include/oeh.h: OEH_CALIB_WORK_BYTES
 DECODE_MAX_SPLITS = 64  # include/oeh.h: OEH_DECODE_MAX_SPLITS
 STATS_WAVE_COLS, STATS_CHUNK, STATS_RECORD_BYTES = 2040, 8192, 48  # include/oeh.h: OEH_STATS_WAVE_COLS, OEH_STATS_CHUNK, OEH_STATS_RECORD_BYTES
+QMSE_CHUNK, QMSE_SLICE, QMSE_MAX_BLOCKS, QMSE_CAND_BYTES, QMSE_F64_K = 8192, 256, 1024, 16, 4  # include/oeh.h: OEH_QMSE_CHUNK, OEH_QMSE_SLICE, OEH_QMSE_MAX_BLOCKS, OEH_QMSE_CAND_BYTES, OEH_QMSE_F64_K
 OEH_F16, OEH_BF16, OEH_F32, OEH_I8 = 0, 1, 2, 3
 OEH_SOFTMAX_VANILLA, OEH_SOFTMAX_ONE = 0, 1
 
@@ -86,6 +87,7 @@ EXPORTS = (
     "oeh_attn_fwd_ex", "oeh_attn_variant_ex",
     "oeh_attn_decode_work_bytes", "oeh_attn_decode", "oeh_attn_decode_variant", "oeh_attn_decode_fq", "oeh_attn_decode_fq_variant",
     "oeh_outlier_stats_work_bytes", "oeh_outlier_stats",
+    "oeh_quant_mse_work_bytes", "oeh_quant_mse",
 )
 
 _lib = None
@@ -171,6 +173,10 @@ def load() -> C.CDLL:
     lib.oeh_outlier_stats_work_bytes.restype = C.c_size_t
     lib.oeh_outlier_stats.argtypes = [vp, i64, i64, i64, i32, f64, vp, vp, i32, vp, vp]
     lib.oeh_outlier_stats.restype = C.c_int
+    lib.oeh_quant_mse_work_bytes.argtypes = [i64, i32]
+    lib.oeh_quant_mse_work_bytes.restype = C.c_size_t
+    lib.oeh_quant_mse.argtypes = [vp, i64, i32, vp, i32, vp, i32, vp, vp]
+    lib.oeh_quant_mse.restype = C.c_int
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -33,6 +33,8 @@ int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_h
 long stats_chunks(long cols);
 int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,
                          hipStream_t st);
+long qmse_blocks(long n, long* nch_out, long* cpb_out);
+int launch_quant_mse(const void* x, long n, int in, const float* cand, int K, double* loss, int accumulate, void* work, hipStream_t st);
 int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st);
 int launch_attn_calibrate(const AttnParams& P, int in, int which, const double* s_range, const double* p_range, float qmax, double eps, double q_lo,
                           double q_hi, double momentum, int first, double* state, void* work, hipStream_t st);
@@ -558,6 +560,20 @@ int oeh_outlier_stats(const void* x, int64_t rows, int64_t cols, int64_t row_str
       (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem_bytes(dtype) - 1)) != 0)
     return OEH_EALIGN;
   return oeh::launch_outlier_stats(x, rows, cols, row_stride, dtype, eps, stats, meter, accumulate, work, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t oeh_quant_mse_work_bytes(int64_t n, int32_t K) {
+  if (n < 1 || K < 1) return 0;
+  return (size_t)oeh::qmse_blocks(n, nullptr, nullptr) * (size_t)(K < OEH_QMSE_SLICE ? K : OEH_QMSE_SLICE) * sizeof(double);
+}
+
+int oeh_quant_mse(const void* x, int64_t n, int32_t dtype, const float* cand, int32_t K, double* loss, int32_t accumulate, void* work,
+                  void* stream) {
+  if (x == nullptr || cand == nullptr || loss == nullptr || work == nullptr || n < 1 || K < 1 || !dtype_ok(dtype)) return OEH_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(cand) & 15) != 0 || (reinterpret_cast<uintptr_t>(loss) & 7) != 0 || (reinterpret_cast<uintptr_t>(work) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem_bytes(dtype) - 1)) != 0)
+    return OEH_EALIGN;
+  return oeh::launch_quant_mse(x, n, dtype, cand, K, loss, accumulate != 0, work, reinterpret_cast<hipStream_t>(stream));
 }
 
 int oeh_fake_quant_range(const void* x, void* y, int64_t n, int32_t dtype, const double* xmin_xmax, int32_t n_bits, double eps,

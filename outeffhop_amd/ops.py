@@ -1057,6 +1057,72 @@ def inf_norm(x: torch.Tensor) -> torch.Tensor:
     return outlier_stats(x)[:, STATS_INF_NORM]
 
 
+# ---- quantisation-error search (include/oeh.h: oeh_quant_mse): the loss of every candidate grid of the MSE range estimator, one read
+
+QMSE_CHUNK = _lib.QMSE_CHUNK            # C: elements a workgroup keeps in registers
+QMSE_SLICE = _lib.QMSE_SLICE            # candidates per pass over the data
+QMSE_MAX_BLOCKS = _lib.QMSE_MAX_BLOCKS  # workgroups per pass: above C * this many elements a workgroup takes several chunks
+QMSE_F64_K = _lib.QMSE_F64_K            # calls of at most this many candidates add in float64 from the first term
+_qmse_work = {}  # (device index, stream handle) -> the per-workgroup sums of that stream
+
+
+def _qmse_scratch(dev, nbytes: int):
+    """The current stream's buffer of per-workgroup sums for `oeh_quant_mse` on `dev`, kept as `_stats_scratch` keeps the chunk records."""
+    with _on_device(dev):
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    work = _qmse_work.get(key)
+    if work is None or work.numel() * 8 < nbytes:
+        if len(_qmse_work) >= 32:
+            _qmse_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
+        work = _qmse_work[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    return work
+
+
+def quant_grid_candidates(scale, lo, hi) -> torch.Tensor:
+    """The (K, 4) fp32 candidate table of `quant_mse` from per-candidate scale, lo = int_min - zero_point and hi = int_max - zero_point
+    (tensors or sequences of equal length; include/oeh.h documents the record)."""
+    scale = torch.as_tensor(scale, dtype=torch.float32).reshape(-1)
+    lo = torch.as_tensor(lo, dtype=torch.float32, device=scale.device).reshape(-1)
+    hi = torch.as_tensor(hi, dtype=torch.float32, device=scale.device).reshape(-1)
+    return torch.stack([scale, lo, hi, torch.zeros_like(scale)], dim=1).contiguous()
+
+
+def quant_mse(x: torch.Tensor, cand: torch.Tensor, loss: Optional[torch.Tensor] = None, accumulate: bool = False, *,
+              work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The squared quantisation error of `x` on each of K candidate grids, as float64[K] on x's GPU, from one read of the data per
+    QMSE_SLICE candidates and without a host synchronisation (`include/oeh.h: oeh_quant_mse`; the loss_fx of range_estimators.py:134-142,
+    for all candidates at once).  cand: (K, 4) fp32 rows (scale, int_min - zero_point, int_max - zero_point, 0): `quant_grid_candidates`.
+    loss: float64[K] to store into, or with `accumulate` to add to (one float64 add per candidate); by default a new tensor (zeros
+    under `accumulate`).  The terms are fp32, rounded as the reference's eager ops round them; the sum is float64 from the 33rd term on.
+    Deviation: fp16 and bf16 elements are widened to fp32 first - the reference would square and sum in the storage type and overflow
+    fp16.  A dense view is read in place (any starting element); anything else is made contiguous.  work: caller's scratch (tests)."""
+    dev = _need_gpu(x, cand, loss, work)
+    if x.dtype not in _DT:
+        raise ValueError(f"unsupported dtype {x.dtype}")
+    if cand.dtype != torch.float32 or cand.dim() != 2 or cand.shape[1] != 4 or not cand.is_contiguous():
+        raise ValueError("cand must be a contiguous float32 tensor of shape (K, 4)")
+    K = cand.shape[0]
+    x = x.detach()
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if loss is None:
+        loss = (torch.zeros if accumulate else torch.empty)(K, dtype=torch.float64, device=x.device)
+    elif loss.dtype != torch.float64 or loss.numel() != K or not loss.is_contiguous():
+        raise ValueError("loss must be a contiguous float64 tensor of K elements")
+    lib = _lib.load()
+    nbytes = lib.oeh_quant_mse_work_bytes(x.numel(), K)
+    if work is None:
+        work = _qmse_scratch(dev, max(nbytes, 8))
+    elif work.numel() * work.element_size() < nbytes:
+        raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, the call needs {nbytes}")
+    with _on_device(dev):
+        rc = lib.oeh_quant_mse(_ptr(x), x.numel(), _DT[x.dtype], _ptr(cand), K, _ptr(loss), int(bool(accumulate)), _ptr(work), _stream())
+    _lib.check(rc, "oeh_quant_mse")
+    return loss
+
+
 # ---- training: the forward with its row statistic and the fused backward (include/oeh.h: oeh_attn_fwd_train / oeh_attn_bwd)
 def _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min):
     """Descriptor + the mask views it points into, for the training entry points (fp16 / bf16, D = 64; the library refuses the rest)."""

@@ -5,6 +5,7 @@ Host-side mirror of the part of the reference's `quantization/` package that the
 
   AsymmetricUniformQuantizer / SymmetricUniformQuantizer   quantization/quantizers/uniform_quantizers.py:12-310
   CurrentMinMaxEstimator / RunningMinMaxEstimator           quantization/range_estimators.py:54-106
+  OptMethod / MSE_Estimator                                 quantization/range_estimators.py:109-395
   QuantizationManager (estimate -> fix state machine)       quantization/quantization_manager.py:11-108
   QuantizedModule / QuantizedActivation                     quantization/base_quantized_classes.py:38-199
   QuantLinear (weight + output-activation quant)            quantization/hijacker.py:27-134, autoquant_utils.py:18-20
@@ -309,6 +310,247 @@ class RunningMinMaxEstimator(RangeEstimatorBase):
         return self.current_xmin, self.current_xmax
 
 
+class OptMethod(BaseEnumOptions):
+    grid = 1
+    golden_section = 2
+
+
+class NoDataPassedError(Exception):
+    def __init__(self):
+        super().__init__("no data has been passed through the range estimator yet")
+
+
+def quant_mse_eager(x: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """What `ops.quant_mse` computes, by plain torch ops on any device, one candidate after the other: the fp32 terms of
+    uniform_quantizers.py:114-115,146 (true division, round to even, clamp, scale, subtract, square) summed in float64, one host read
+    per candidate as in range_estimators.py:134-142.  The path of CPU tensors (weights quantised before .to(device)); on GPU tensors it
+    is the eager chain that tools/mse_bench.py times the kernel against.  16-bit data is widened to fp32, as the kernel widens it."""
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    c = cand.to(x.device)
+    out = []
+    for k in range(c.shape[0]):
+        scale, lo, hi = c[k, 0], c[k, 1], c[k, 2]
+        y = scale * torch.clamp(torch.round(x / scale), lo, hi)
+        out.append(float(((x - y) ** 2).sum(dtype=torch.float64)))
+    return torch.tensor(out, dtype=torch.float64, device=x.device)
+
+
+class MSE_Estimator(RangeEstimatorBase):
+    """The range that minimises the squared quantisation error (range_estimators.py:114-382; validate_clm.py --ranges_weights mse,
+    --ranges_acts MSE): a 1-D grid of clipping thresholds for symmetric quantisers and one-sided data, a 2-D grid (threshold x integer
+    skew of the zero point) for asymmetric quantisers on two-sided data, or scipy's bounded golden-section search over the same
+    spaces.  Losses are accumulated over the batches without momentum; the search space is fixed by the first batch.
+
+    Every candidate's grid (scale, zero point, integer limits) is derived on the host by the float32 tensor arithmetic of the
+    quantiser's set_quant_range, vectorised over the candidates, once; the table then stays on the device and `ops.quant_mse` adds
+    the losses of ALL candidates to a float64 device array from one read of the data per 256 candidates.  argmin and the chosen range
+    follow by torch ops: after the first batch's one read of (min, max) the grid searches never synchronise.  Golden section is
+    sequential: one K = 1 call and one host read per evaluation.  CPU tensors take `quant_mse_eager`.
+    Deviation: fp16 / bf16 data is widened to fp32 for the error terms (the reference squares and sums in the storage type)."""
+
+    def __init__(self, *args, num_candidates=100, opt_method=OptMethod.grid, range_margin=0.5, **kwargs):
+        super().__init__(*args, **kwargs)
+        assert opt_method in OptMethod
+        self.opt_method = opt_method
+        self.num_candidates = num_candidates
+        self.loss_array = None        # float64 (1, N + 1) or (1, N + 1, max_int_skew, 2) on the data's device; index 0 stays +inf
+        self.max_pos_thr = None
+        self.max_neg_thr = None
+        self.max_search_range = None
+        self.one_sided_dist = None
+        self.range_margin = range_margin
+        self._cand = None             # (K, 4) fp32 candidate table of the grid searches, on the data's device
+        self._range_table = None      # (loss_array.numel(), 2) fp32: the (x_min, x_max) that each entry of loss_array stands for
+        if self.quantizer is None:
+            raise NotImplementedError("A Quantizer must be given as an argument to the MSE RangeEstimator")
+        self.max_int_skew = (2 ** self.quantizer.n_bits) // 4  # for asymmetric quantisation
+
+    # ---- candidate grids: the arithmetic of _tensorize_min_max / set_quant_range, vectorised over the candidates
+    def _current_grid(self):
+        q = self.quantizer
+        if not q.is_initialized:
+            raise QuantizerNotInitializedError()
+        zp = float(q.zero_point)
+        return float(q.scale), float(q.int_min) - zp, float(q.int_max) - zp
+
+    def candidate_rows(self, neg_thr, pos_thr) -> torch.Tensor:
+        """(K, 4) fp32 rows (scale, int_min - zero_point, int_max - zero_point, 0) of the grids that the quantiser's set_quant_range
+        would take from the thresholds (float64 values, as the reference's Python arithmetic produces them)."""
+        q = self.quantizer
+        neg, pos = np.broadcast_arrays(np.atleast_1d(np.asarray(neg_thr, dtype=np.float64)), np.atleast_1d(np.asarray(pos_thr, dtype=np.float64)))
+        x_min, x_max = torch.from_numpy(neg.copy()).float(), torch.from_numpy(pos.copy()).float()
+        x_min = torch.min(x_min, torch.zeros_like(x_min))
+        x_max = torch.max(x_max, torch.ones_like(x_max) * q.eps)
+        if q.symmetric:
+            signed = x_min < 0
+            int_min = torch.where(signed, torch.full_like(x_min, -(2.0 ** (q.n_bits - 1))), torch.zeros_like(x_min))
+            int_max = torch.where(signed, torch.full_like(x_min, 2.0 ** (q.n_bits - 1) - 1), torch.full_like(x_min, 2.0 ** q.n_bits - 1))
+            delta = torch.max(x_min.abs(), x_max) / int_max
+            zero_point = torch.zeros_like(x_min)
+        else:
+            int_min, int_max = torch.zeros_like(x_min), torch.full_like(x_min, 2.0 ** q.n_bits - 1)
+            delta = (x_max - x_min) / (2.0 ** q.n_bits - 1)
+            zero_point = torch.clamp(torch.round(-x_min / delta), 0.0, 2.0 ** q.n_bits - 1)
+        scale = torch.clamp(delta, min=q.eps)
+        rows = torch.stack([scale, int_min - zero_point, int_max - zero_point, torch.zeros_like(scale)], dim=1)
+        # `if x_min or x_max` (range_estimators.py:178): two thresholds of exactly 0 leave the copy of the quantiser on its CURRENT range
+        same = torch.from_numpy((neg == 0) & (pos == 0))
+        if bool(same.any()):
+            rows[same] = torch.tensor(self._current_grid() + (0.0,), dtype=torch.float32)
+        return rows.contiguous()
+
+    def _losses(self, data, cand, loss=None):
+        """The candidates' losses on `data`: added to `loss` (float64, on the device) when given, else returned."""
+        if data.is_cuda:
+            return ops.quant_mse(data, cand.to(data.device), loss, accumulate=loss is not None)
+        got = quant_mse_eager(data, cand)
+        if loss is None:
+            return got
+        loss += got
+        return loss
+
+    def loss_fx(self, data, neg_thr, pos_thr):
+        return float(self._losses(self._prepare(data), self.candidate_rows(neg_thr, pos_thr))[0])
+
+    @staticmethod
+    def _prepare(data):
+        data = data.detach()
+        return data if data.dtype in (torch.float16, torch.bfloat16, torch.float32) else data.float()
+
+    @property
+    def step_size(self):
+        if self.one_sided_dist is None:
+            raise NoDataPassedError()
+        return self.max_search_range / self.num_candidates
+
+    @property
+    def optimization_method(self):
+        if self.one_sided_dist is None:
+            raise NoDataPassedError()
+        one_d = self.one_sided_dist or self.quantizer.symmetric
+        if self.opt_method == OptMethod.grid:
+            return self._perform_1D_search if one_d else self._perform_2D_search
+        if self.opt_method == OptMethod.golden_section:
+            return self._golden_section_symmetric if one_d else self._golden_section_asymmetric
+        raise NotImplementedError("Optimization Method not Implemented")
+
+    def _define_search_range(self, data, d_min: float, d_max: float):
+        self.channel_groups = 1
+        dev = data.device
+        self.current_xmax = torch.zeros(1, device=dev)
+        self.current_xmin = torch.zeros(1, device=dev)
+        N, S = self.num_candidates, self.max_int_skew
+        one_d = self.one_sided_dist or self.quantizer.symmetric
+        if one_d:
+            self.loss_array = torch.zeros((1, N + 1), dtype=torch.float64, device=dev)
+            self.loss_array[:, 0] = float("inf")  # exclude interval_start = interval_finish
+            self.max_pos_thr = max(abs(d_min), d_max) + self.range_margin
+            self.max_neg_thr = -self.max_pos_thr
+            self.max_search_range = self.max_pos_thr
+        else:
+            self.loss_array = torch.zeros((1, N + 1, S, 2), dtype=torch.float64, device=dev)
+            self.loss_array[:, 0] = float("inf")
+            self.max_pos_thr = d_max + self.range_margin
+            self.max_neg_thr = d_min - self.range_margin
+            self.max_search_range = max(abs(self.max_pos_thr), abs(self.max_neg_thr))
+        self._cand = self._range_table = None
+        if self.opt_method != OptMethod.grid:
+            return
+        # the thresholds of every entry of loss_array, in its own (flattened) order, by the reference's float64 arithmetic
+        step = self.step_size
+        if one_d:
+            idx = np.arange(N + 1)
+            pos = step * idx
+            neg = np.zeros(N + 1) if self.one_sided_dist else -step * idx
+        else:
+            idx = np.arange(N + 1).reshape(-1, 1, 1)
+            start, finish = -step * idx, step * idx
+            delta = (finish - start) / (2 ** self.quantizer.n_bits - 1)
+            skew = (np.array([1, -1]).reshape(1, 1, 2) * np.arange(S).reshape(1, -1, 1)) * delta
+            neg = np.maximum(start + skew, self.max_neg_thr).reshape(-1)
+            pos = np.minimum(finish + skew, self.max_pos_thr).reshape(-1)
+        first = neg.size // (N + 1)  # entries of candidate index 0: never evaluated
+        self._cand = self.candidate_rows(neg[first:], pos[first:]).to(dev)
+        self._range_table = torch.from_numpy(np.stack([neg, pos], axis=1).astype(np.single)).to(dev)
+
+    def _grid_search(self, data):
+        """Add this batch's losses of all candidates, then take the range of the smallest accumulated loss (torch ops on the data's
+        device: no host read)."""
+        if self.loss_array.device != data.device:
+            self.loss_array, self._cand, self._range_table = (t.to(data.device) for t in (self.loss_array, self._cand, self._range_table))
+        flat = self.loss_array.view(-1)
+        self._losses(data, self._cand, flat[flat.numel() - self._cand.shape[0]:])
+        best = self._range_table.index_select(0, torch.argmin(flat).reshape(1))[0]  # (a tensor index, not a host integer: no synchronisation)
+        self.current_xmin, self.current_xmax = best[0:1].clone(), best[1:2].clone()
+
+    def _perform_1D_search(self, data):
+        self._grid_search(data)
+
+    def _perform_2D_search(self, data):
+        self._grid_search(data)
+
+    @staticmethod
+    def _minimize_scalar():
+        try:
+            from scipy.optimize import minimize_scalar
+        except ImportError as e:
+            raise ImportError("MSE_Estimator with OptMethod.golden_section needs scipy (scipy.optimize.minimize_scalar); "
+                              "OptMethod.grid does not") from e
+        return minimize_scalar
+
+    def golden_sym_loss(self, range, data):
+        return self.loss_fx(data, 0 if self.one_sided_dist else -range, range)
+
+    def golden_asym_shift_loss(self, shift, range, data):
+        return self.loss_fx(data, -range + shift, range + shift)
+
+    def golden_asym_range_loss(self, range, data):
+        max_shift = 2 * range / (2 ** self.quantizer.n_bits - 1) * self.max_int_skew
+        return self._minimize_scalar()(self.golden_asym_shift_loss, args=(range, data), bounds=(-max_shift, max_shift), method="Bounded").fun
+
+    def _golden_section_symmetric(self, data):
+        self.result = self._minimize_scalar()(self.golden_sym_loss, args=data, bounds=(0.01 * self.max_search_range, self.max_search_range),
+                                              method="Bounded")
+        self.current_xmax = torch.tensor([self.result.x], dtype=torch.float32).to(data.device)
+        self.current_xmin = torch.zeros(1, device=data.device) if self.one_sided_dist else -self.current_xmax
+
+    def _golden_section_asymmetric(self, data):
+        minimize_scalar = self._minimize_scalar()
+        self.result = minimize_scalar(self.golden_asym_range_loss, args=data, bounds=(0.01 * self.max_search_range, self.max_search_range),
+                                      method="Bounded")
+        self.final_range = self.result.x
+        max_shift = 2 * self.final_range / (2 ** self.quantizer.n_bits - 1) * self.max_int_skew
+        self.subresult = minimize_scalar(self.golden_asym_shift_loss, args=(self.final_range, data), bounds=(-max_shift, max_shift), method="Bounded")
+        self.final_shift = self.subresult.x
+        self.current_xmax = torch.tensor([self.final_range + self.final_shift], dtype=torch.float32).to(data.device)
+        self.current_xmin = torch.tensor([-self.final_range + self.final_shift], dtype=torch.float32).to(data.device)
+
+    def forward(self, data):
+        data = self._prepare(data)
+        if self.loss_array is None:
+            # the search space is set by the first batch: one host read of (min, max)
+            mm = ops.minmax(data) if data.is_cuda else torch.stack([data.min(), data.max()]).float()
+            d_min, d_max = (float(v) for v in mm.tolist())
+            if self.one_sided_dist is None:
+                self.one_sided_dist = bool(d_min >= 0)
+            self._define_search_range(data, d_min, d_max)
+        self.optimization_method(data)
+        return self.current_xmin, self.current_xmax
+
+    def reset(self):
+        super().reset()
+        self.loss_array = None
+        self._cand = self._range_table = None
+
+    def extra_repr(self):
+        repr = "opt_method={}".format(self.opt_method.name)
+        if self.opt_method == OptMethod.grid:
+            repr += " ,num_candidates={}".format(self.num_candidates)
+        return repr
+
+
 class _ClsEnum(Enum):
     @property
     def cls(self):
@@ -333,6 +575,7 @@ class QMethods(_ClsEnum):
 class RangeEstimators(_ClsEnum):
     current_minmax = CurrentMinMaxEstimator
     running_minmax = RunningMinMaxEstimator
+    MSE = MSE_Estimator
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1348,6 +1591,11 @@ def get_quant_config() -> DotDict:
 
 
 def val_qparams(config) -> dict:
+    weight_range_options = {}
+    if config.quant.weight_quant_method == RangeEstimators.MSE:
+        weight_range_options = dict(opt_method=config.quant.weight_opt_method)
+    if config.quant.num_candidates is not None:
+        weight_range_options["num_candidates"] = config.quant.num_candidates
     return {
         "method": config.quant.qmethod.cls,
         "n_bits": config.quant.n_bits,
@@ -1357,7 +1605,7 @@ def val_qparams(config) -> dict:
         "percentile": config.quant.percentile,
         "quant_setup": config.quant.quant_setup,
         "weight_range_method": config.quant.weight_quant_method.cls,
-        "weight_range_options": {},
+        "weight_range_options": weight_range_options,
         "act_range_method": config.act_quant.quant_method.cls,
         "act_range_options": config.act_quant.options,
     }

@@ -125,6 +125,144 @@ def _fill_fq(dst: oeh_fq, spec: Optional[FakeQuantSpec]):
         dst.dump_idx = spec.dump.data_ptr()
 
 
+# ---- host marshalling shared by the entry points: argument checks, the descriptors of include/oeh.h, the per-stream scratch
+def _need_dtype(x: torch.Tensor) -> None:
+    if x.dtype not in _DT:
+        raise ValueError(f"unsupported dtype {x.dtype}")
+
+
+def _need_f64(t: torch.Tensor, n: int, message: str) -> None:
+    """A device-side float64 vector of the C ABI (a range, a running state, a meter, the losses): n contiguous elements."""
+    if t.dtype != torch.float64 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(message)
+
+
+def _check_qkv(q, k, v):
+    """q (B,H,Sq,D), k and v (B,H,Sk,D) in one of the storage dtypes; an input whose head-dim stride is not 1 comes back as a contiguous
+    copy (the kernels read contiguous head dims)."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k, v must be 4-D (B,H,S,D) views")
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if k.shape != (B, H, Sk, D) or v.shape != (B, H, Sk, D):
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in _DT:
+        raise ValueError(f"q/k/v dtypes must match and be fp16/bf16/fp32, got {q.dtype}, {k.dtype}, {v.dtype}")
+    fix = lambda t: t if t.stride(3) == 1 else t.contiguous()  # noqa: E731
+    return fix(q), fix(k), fix(v)
+
+
+def _attn_desc(q, k, v, o, dtype: int, o_dtype: int, softmax: SoftmaxSpec, scale, scale_div, causal, clamp_min, mask_min: Optional[float],
+               scores_dtype: torch.dtype) -> oeh_attn_desc:
+    """The part of an `oeh_attn_desc` every launching entry point fills: the geometry of q (B,H,Sq,D) against Sk keys, the storage and output
+    dtype codes, the (batch, head, row) strides of the four tensors, scale, softmax, causal / clamp_min / mask_min.  mask_min None: finfo.min
+    of `scores_dtype`, the dtype the reference would hold the scores in (include/oeh.h).  Masks and gate: `_set_key_pad`, `_set_full_mask`,
+    `_set_gate`."""
+    d = oeh_attn_desc()
+    d.B, d.H, d.Sq, d.D = q.shape
+    d.Sk = k.shape[2]
+    d.dtype, d.o_dtype = dtype, o_dtype
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
+        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    d.scale, d.scale_div = float(scale), float(scale_div)
+    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
+    d.mask_min = float(torch.finfo(scores_dtype).min if mask_min is None else mask_min)
+    return d
+
+
+def _probe_desc(B, H, Sq, Sk, D, dtype, *, scale=1.0, scale_div=0.0, base=1, clip=False, gamma=-0.025, causal=False, mask_min=None) -> oeh_attn_desc:
+    """The host-only descriptor of the `*_variant` probes: what decides the kernel, without tensors - no strides, no o_dtype, and of a
+    pointer only its nullness matters (nothing is dereferenced: the callers set 1 for "present").  Clipping as the registry has it (eta 1)."""
+    d = oeh_attn_desc()
+    d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[dtype]
+    d.scale, d.scale_div = float(scale), float(scale_div)
+    d.softmax_base, d.causal = int(base), int(bool(causal))
+    d.mask_min = float(torch.finfo(torch.float32).min if mask_min is None else mask_min)  # (no tensor to take the default's dtype from)
+    if clip:
+        d.clip, d.gamma, d.eta = 1, float(gamma), 1.0
+    return d
+
+
+def _set_key_pad(d: oeh_attn_desc, keep: list, mask: torch.Tensor, i8: bool = False) -> None:
+    """The additive key-padding vector as the kernel reads it: fp16 / fp32, (B,Sk) with contiguous keys (anything else is converted to
+    fp32).  `i8`, the INT8-storage path: a mask of ONE row serves every batch through a zero batch stride, and rows that are a stride
+    apart are read in place; the other paths always hand over a dense (B,Sk) copy.  `key_pad_boolean` is the caller's to set."""
+    B, Sk = d.B, d.Sk
+    if i8:
+        m = mask if mask.dtype in (torch.float16, torch.float32) else mask.float()
+        m = m.reshape(B, Sk) if m.numel() == B * Sk else m.reshape(1, Sk).expand(B, Sk)
+        if m.stride(1) != 1:
+            m = m.contiguous()
+    else:
+        m = mask.reshape(B, Sk)
+        if m.dtype not in (torch.float16, torch.float32):
+            m = m.float()
+        m = m.contiguous()
+    keep.append(m)
+    d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
+
+
+def _set_full_mask(d: oeh_attn_desc, keep: list, full_mask: torch.Tensor) -> None:
+    """The additive (B,1,Sq,Sk) mask: fp16 / fp32 with contiguous keys, read in place where it already is."""
+    B, Sq, Sk = d.B, d.Sq, d.Sk
+    if full_mask.shape != (B, 1, Sq, Sk):
+        raise ValueError(f"Attention mask should be of size {(B, 1, Sq, Sk)}, but is {tuple(full_mask.shape)}")
+    m = full_mask if full_mask.dtype in (torch.float16, torch.float32) else full_mask.float()
+    m = m if m.stride(3) == 1 else m.contiguous()
+    keep.append(m)
+    d.full_mask, d.full_mask_dtype = m.data_ptr(), _DT[m.dtype]
+    d.full_mask_stride[:] = [m.stride(0), m.stride(2)]
+
+
+def _set_gate(d: oeh_attn_desc, keep: list, gate: torch.Tensor) -> None:
+    """Gate values, fp32, broadcast to (B,H,Sq,1) by zero strides."""
+    g = gate.to(torch.float32)
+    while g.dim() < 4:
+        g = g.unsqueeze(0)
+    g = g.expand(d.B, d.H, d.Sq, 1)
+    keep.append(g)
+    d.gate = g.data_ptr()
+    d.gate_stride[:] = [g.stride(0), g.stride(1), g.stride(2)]
+
+
+def _fq_desc(fq: Optional[AttnFakeQuant], always: bool = False) -> Optional[oeh_fq_desc]:
+    """The `oeh_fq_desc` of `fq`; None when no quantiser is enabled (the entry points then run their forms without quantisers), unless
+    `always`."""
+    if not always and (fq is None or not (fq.scores or fq.probs or fq.ctx)):
+        return None
+    fqd = oeh_fq_desc()
+    _fill_fq(fqd.scores, fq.scores)
+    _fill_fq(fqd.probs, fq.probs)
+    _fill_fq(fqd.ctx, fq.ctx)
+    fqd.ctx_quant_before_gate = int(bool(fq.ctx_before_gate))
+    fqd.ctx_emit_index = int(bool(fq.ctx_emit_index))
+    return fqd
+
+
+# what the `*_variant` probes ask about with fq=True: scores and probabilities on full 8-bit grids of scale 1 (every other field zero)
+_PROBE_FQ = AttnFakeQuant(FakeQuantSpec(1.0, 0.0), FakeQuantSpec(1.0, 0.0), ctx_before_gate=False)
+
+
+def _scratch(table: dict, dev, nbytes: int) -> torch.Tensor:
+    """The current stream's work buffer of one entry point on `dev`, from that entry point's `table`: (device index, stream handle) ->
+    buffer, grown to the largest request so far.  Per stream, because two calls on different streams of one GPU may run at the same time
+    and must not share partial results.  Bounded, because streams come and go (a recycled handle simply reuses its buffer): at 32 entries
+    the table starts over instead of keeping one buffer per stream ever seen.  Under graph capture the call gets a buffer of its own
+    instead, allocated inside the capture: it then lives in the graph's private pool for as long as the graph does - a cached buffer may
+    be replaced (a larger request, the table starting over) and freed while a graph that recorded its address is still replayed."""
+    with _on_device(dev):
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    work = table.get(key)
+    if work is None or work.numel() * 8 < nbytes:
+        if len(table) >= 32:
+            table.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
+        work = table[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    return work
+
+
 def attn_fwd(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -183,16 +321,9 @@ def attn_fwd(
                 _lib.check(rc, "oeh_attn_fwd")
             return o
     dev = _need_gpu(q, k, v, key_pad_mask, full_mask, gate, out)
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k, v must be 4-D (B,H,S,D) views")
+    q, k, v = _check_qkv(q, k, v)
     B, H, Sq, D = q.shape
     Sk = k.shape[2]
-    if k.shape != (B, H, Sk, D) or v.shape != (B, H, Sk, D):
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
-    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in _DT:
-        raise ValueError(f"q/k/v dtypes must match and be fp16/bf16/fp32, got {q.dtype}, {k.dtype}, {v.dtype}")
-    fix = lambda t: t if t.stride(3) == 1 else t.contiguous()  # noqa: E731
-    q, k, v = fix(q), fix(k), fix(v)
     odt = q.dtype if out_dtype is None else out_dtype
     if odt != q.dtype and not (odt == torch.float32 and q.dtype in (torch.float16, torch.bfloat16)):
         raise ValueError(f"out_dtype must be the input dtype, or float32 for fp16 / bf16 inputs (got {odt} for {q.dtype})")
@@ -215,41 +346,16 @@ def attn_fwd(
     elif out.shape != (B, H, Sq, D) or out.dtype != odt or out.stride(3) != 1:
         raise ValueError("out must be a (B,H,Sq,D) view with unit head-dim stride and the input dtype (or out_dtype)")
 
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D = B, H, Sq, Sk, D
-    d.dtype = _DT[q.dtype]
-    d.o_dtype = _DT[odt]  # (read for 16-bit inputs only when it says OEH_F32)
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    d.scale, d.scale_div = float(scale), float(scale_div)
-    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    # o_dtype: the dtype of `out` (read for 16-bit inputs only when it says OEH_F32)
+    d = _attn_desc(q, k, v, out, _DT[q.dtype], _DT[odt], softmax, scale, scale_div, causal, clamp_min, mask_min, q.dtype)
     keep = []
     if key_pad_mask is not None:
-        m = key_pad_mask.reshape(B, Sk)
-        if m.dtype not in (torch.float16, torch.float32):
-            m = m.float()
-        m = m.contiguous()
-        keep.append(m)
-        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
-        d.key_pad_boolean = int(bool(key_pad_boolean))
+        _set_key_pad(d, keep, key_pad_mask)
+        d.key_pad_boolean = int(bool(key_pad_boolean))  # the caller's promise (include/oeh.h): this entry point alone passes it on
     if full_mask is not None:
-        if full_mask.shape != (B, 1, Sq, Sk):
-            raise ValueError(f"Attention mask should be of size {(B, 1, Sq, Sk)}, but is {tuple(full_mask.shape)}")
-        m = full_mask if full_mask.dtype in (torch.float16, torch.float32) else full_mask.float()
-        m = m if m.stride(3) == 1 else m.contiguous()
-        keep.append(m)
-        d.full_mask, d.full_mask_dtype = m.data_ptr(), _DT[m.dtype]
-        d.full_mask_stride[:] = [m.stride(0), m.stride(2)]
-    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
-    d.mask_min = float(torch.finfo(q.dtype).min if mask_min is None else mask_min)
+        _set_full_mask(d, keep, full_mask)
     if gate is not None:
-        g = gate.to(torch.float32)
-        while g.dim() < 4:
-            g = g.unsqueeze(0)
-        g = g.expand(B, H, Sq, 1)
-        keep.append(g)
-        d.gate = g.data_ptr()
-        d.gate_stride[:] = [g.stride(0), g.stride(1), g.stride(2)]
+        _set_gate(d, keep, gate)
     if gate_mlp is not None:
         if gate is not None:
             raise ValueError("pass either `gate` (values) or `gate_mlp` (predictor evaluated in the kernel), not both")
@@ -272,14 +378,7 @@ def attn_fwd(
             if gm.out.shape != (B, H, Sq) or gm.out.dtype != torch.float32 or not gm.out.is_contiguous():
                 raise ValueError("gate_mlp.out must be a contiguous fp32 (B,H,Sq) tensor")
             d.gate_out = gm.out.data_ptr()
-    fqd = None
-    if fq is not None and (fq.scores or fq.probs or fq.ctx):
-        fqd = oeh_fq_desc()
-        _fill_fq(fqd.scores, fq.scores)
-        _fill_fq(fqd.probs, fq.probs)
-        _fill_fq(fqd.ctx, fq.ctx)
-        fqd.ctx_quant_before_gate = int(bool(fq.ctx_before_gate))
-        fqd.ctx_emit_index = int(bool(fq.ctx_emit_index))
+    fqd = _fq_desc(fq)
     lib = _lib.load()
     fn, what = lib.oeh_attn_fwd, "oeh_attn_fwd"
     if pv_pairs:  # oeh_attn_fwd_ex with the options bound: the same call signature as oeh_attn_fwd from here on
@@ -567,41 +666,18 @@ def attn_fwd_i8(q: torch.Tensor, k: torch.Tensor, v_t: torch.Tensor, grids, *, f
         out = torch.empty((B, Sq, H, D), dtype=out_dtype, device=q.device).permute(0, 2, 1, 3)
     elif out.shape != (B, H, Sq, D) or out.dtype != out_dtype or out.stride(3) != 1:
         raise ValueError("out must be a (B,H,Sq,D) view with unit head-dim stride and dtype out_dtype")
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D, d.dtype, d.o_dtype = B, H, Sq, Sk, D, _lib.OEH_I8, (_lib.OEH_I8 if out_dtype == torch.int8 else _DT[out_dtype])
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v_t), ("o_stride", out)):
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    # mask_min: q holds int8 indices here, not a dtype to take finfo.min of - the default is fp32's, whatever `out_dtype` is
+    d = _attn_desc(q, k, v_t, out, _lib.OEH_I8, _lib.OEH_I8 if out_dtype == torch.int8 else _DT[out_dtype], softmax, scale, scale_div, causal, clamp_min,
+                   mask_min, torch.float32)
     for name, gr in zip(("q_grid", "k_grid", "v_grid"), grids):
         getattr(d, name).scale, getattr(d, name).zero_point = float(gr.scale), float(gr.zero_point)
-    d.scale, d.scale_div = float(scale), float(scale_div)
-    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
-    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
-    d.mask_min = float(torch.finfo(torch.float32).min if mask_min is None else mask_min)
     keep = []
     if key_pad_mask is not None:
-        pm = key_pad_mask
-        if pm.dtype not in (torch.float16, torch.float32):
-            pm = pm.float()
-        pm = pm.reshape(B, Sk) if pm.numel() == B * Sk else pm.reshape(1, Sk).expand(B, Sk)
-        if pm.stride(1) != 1:
-            pm = pm.contiguous()
-        keep.append(pm)
-        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = pm.data_ptr(), _DT[pm.dtype], pm.stride(0)
+        _set_key_pad(d, keep, key_pad_mask, i8=True)
         d.key_pad_boolean = 1  # (this path always reads the mask that way: include/oeh.h)
     if gate is not None:
-        g = gate.to(torch.float32)
-        while g.dim() < 4:
-            g = g.unsqueeze(0)
-        g = g.expand(B, H, Sq, 1)
-        keep.append(g)
-        d.gate = g.data_ptr()
-        d.gate_stride[:] = [g.stride(0), g.stride(1), g.stride(2)]
-    fqd = oeh_fq_desc()
-    _fill_fq(fqd.scores, fq.scores)
-    _fill_fq(fqd.probs, fq.probs)
-    _fill_fq(fqd.ctx, fq.ctx)
-    fqd.ctx_quant_before_gate = int(bool(fq.ctx_before_gate))
-    fqd.ctx_emit_index = int(bool(fq.ctx_emit_index))
+        _set_gate(d, keep, gate)
+    fqd = _fq_desc(fq, always=True)  # (the library refuses this path without the scores' and probabilities' quantisers: that is its answer to give)
     if _prepared is not None:  # hand back the prebuilt C call instead of launching (bench / A-B loops)
         _prepared.extend([_lib.load().oeh_attn_fwd, (C.byref(d), _ptr(q), _ptr(k), _ptr(v_t), _ptr(out), C.byref(fqd)), (d, fqd, keep, q, k, v_t, out)])
         return out
@@ -669,23 +745,12 @@ def attn_variant(B, H, Sq, Sk, D, dtype=torch.float16, fq: bool = False, clip: b
     """Name of the kernel variant the library would pick for this problem (host only; no GPU needed).  `gate_hidden`: with the
     per-token gate predictor evaluated in the kernel (it narrows the choice).  `pv_pairs`: with attn_fwd(..., pv_pairs=True) (None where
     that is refused; the forms with probability pairs end in "+pv2")."""
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[dtype]
-    d.scale, d.scale_div = float(scale), float(scale_div)
-    d.mask_min = float(torch.finfo(torch.float32).min if mask_min is None else mask_min)
-    d.softmax_base, d.causal = int(base), int(bool(causal))
-    # only nullness of the mask pointers matters to the selection (host only: nothing is dereferenced)
+    d = _probe_desc(B, H, Sq, Sk, D, dtype, scale=scale, scale_div=scale_div, base=base, clip=clip, gamma=gamma, causal=causal, mask_min=mask_min)
     d.key_pad_mask, d.key_pad_dtype, d.key_pad_boolean = (1 if key_pad else None), OEH_F32, int(bool(key_pad_boolean))
     d.full_mask, d.full_mask_dtype = (1 if full_mask else None), OEH_F32
     if gate_hidden:
         d.gate_hidden, d.gate_w1, d.gate_b1 = 1, 1, 1
-    if clip:
-        d.clip, d.gamma, d.eta = 1, float(gamma), 1.0
-    fqd = None
-    if fq:
-        fqd = oeh_fq_desc()
-        fqd.scores.enable, fqd.scores.scale, fqd.scores.qmax = 1, 1.0, 255.0
-        fqd.probs.enable, fqd.probs.scale, fqd.probs.qmax = 1, 1.0, 255.0
+    fqd = _fq_desc(_PROBE_FQ) if fq else None
     if pv_pairs:
         r = _lib.load().oeh_attn_variant_ex(C.byref(d), C.byref(oeh_attn_opts(pv_pairs=1)), None if fqd is None else C.byref(fqd))
     else:
@@ -698,20 +763,8 @@ _decode_work = {}  # (device index, stream handle) -> the split-key scratch of t
 
 
 def _decode_scratch(dev, nbytes: int):
-    """The current stream's scratch for `oeh_attn_decode` on `dev`, grown to the largest request so far (bounded like `_calib_scratch`).
-    Under graph capture the call gets a buffer of its own instead, allocated inside the capture: it then lives in the graph's private
-    pool for as long as the graph does - a cached buffer may be replaced (a larger request, the table starting over) and freed while a
-    graph that recorded its address is still replayed."""
-    with _on_device(dev):
-        if torch.cuda.is_current_stream_capturing():
-            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    work = _decode_work.get(key)
-    if work is None or work.numel() * 8 < nbytes:
-        if len(_decode_work) >= 32:
-            _decode_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
-        work = _decode_work[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    return work
+    """The current stream's split-key scratch for `oeh_attn_decode` on `dev` (`_scratch`)."""
+    return _scratch(_decode_work, dev, nbytes)
 
 
 def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax: SoftmaxSpec = SoftmaxSpec(), scale: float = 1.0, scale_div: float = 0.0,
@@ -724,60 +777,28 @@ def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softmax: S
     `attn_fwd`; what the entry point does not take (another head dim, more query rows, fp32 storage, gamma > 0) raises OehError -95.
     `fq`: the fused INT8 chain as in `attn_fwd` (`oeh_attn_decode_fq`: any subset of the three quantisers, index dumps included;
     `ctx_emit_index` is refused, -95); None or nothing enabled: `oeh_attn_decode` itself.
-    Bitwise reproducible; graph-capture safe (a captured call owns its scratch: `_decode_scratch`)."""
+    Bitwise reproducible; graph-capture safe (a captured call owns its scratch: `_scratch`)."""
     global DECODE_CALLS
     dev = _need_gpu(q, k, v, key_pad_mask, gate)
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k, v must be 4-D (B,H,S,D) views")
+    q, k, v = _check_qkv(q, k, v)
     B, H, Sq, D = q.shape
-    Sk = k.shape[2]
-    if k.shape != (B, H, Sk, D) or v.shape != (B, H, Sk, D):
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
-    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in _DT:
-        raise ValueError(f"q/k/v dtypes must match and be fp16/bf16/fp32, got {q.dtype}, {k.dtype}, {v.dtype}")
-    fix = lambda t: t if t.stride(3) == 1 else t.contiguous()  # noqa: E731
-    q, k, v = fix(q), fix(k), fix(v)
     odt = q.dtype if out_dtype is None else out_dtype
     if odt != q.dtype and odt != torch.float32:
         raise ValueError(f"out_dtype must be the input dtype or float32 (got {odt} for {q.dtype})")
     out = torch.empty((B, Sq, H, D), dtype=odt, device=q.device).permute(0, 2, 1, 3)
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D = B, H, Sq, Sk, D
-    d.dtype, d.o_dtype = _DT[q.dtype], _DT[odt]
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    d.scale, d.scale_div = float(scale), float(scale_div)
-    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    d = _attn_desc(q, k, v, out, _DT[q.dtype], _DT[odt], softmax, scale, scale_div, causal, clamp_min, mask_min, q.dtype)
     keep = []
     if key_pad_mask is not None:
-        m = key_pad_mask.reshape(B, Sk)
-        if m.dtype not in (torch.float16, torch.float32):
-            m = m.float()
-        m = m.contiguous()
-        keep.append(m)
-        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
-    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
-    d.mask_min = float(torch.finfo(q.dtype).min if mask_min is None else mask_min)
+        _set_key_pad(d, keep, key_pad_mask)  # (key_pad_boolean stays 0: this entry point has no such argument)
     if gate is not None:
-        g = gate.to(torch.float32)
-        while g.dim() < 4:
-            g = g.unsqueeze(0)
-        g = g.expand(B, H, Sq, 1)
-        keep.append(g)
-        d.gate = g.data_ptr()
-        d.gate_stride[:] = [g.stride(0), g.stride(1), g.stride(2)]
+        _set_gate(d, keep, gate)
     lib = _lib.load()
     nbytes = lib.oeh_attn_decode_work_bytes(C.byref(d), int(splits))
     if nbytes < 0:
         _lib.check(int(nbytes), "oeh_attn_decode")
     work = _decode_scratch(dev, int(nbytes))
-    if fq is not None and (fq.scores or fq.probs or fq.ctx):
-        fqd = oeh_fq_desc()
-        _fill_fq(fqd.scores, fq.scores)
-        _fill_fq(fqd.probs, fq.probs)
-        _fill_fq(fqd.ctx, fq.ctx)
-        fqd.ctx_quant_before_gate = int(bool(fq.ctx_before_gate))
-        fqd.ctx_emit_index = int(bool(fq.ctx_emit_index))
+    fqd = _fq_desc(fq)
+    if fqd is not None:
         with _on_device(dev):
             rc = lib.oeh_attn_decode_fq(C.byref(d), C.byref(fqd), int(splits), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(work), _stream())
         _lib.check(rc, "oeh_attn_decode_fq")
@@ -793,17 +814,9 @@ def attn_decode_variant(B, H, Sq, Sk, D=64, dtype=torch.float16, *, clip: bool =
                         fq: bool = False) -> Optional[str]:
     """Name of the form `attn_decode` would run ("decode16/SP<effective splits>/D64/f16[/clip][/fq]"; `fq`: with the fused INT8 chain), or None
     where it refuses (host only)."""
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[dtype]
-    d.scale, d.softmax_base, d.causal = 1.0, 1, int(bool(causal))
-    d.mask_min = float(torch.finfo(torch.float32).min)
-    if clip:
-        d.clip, d.gamma, d.eta = 1, float(gamma), 1.0
+    d = _probe_desc(B, H, Sq, Sk, D, dtype, clip=clip, gamma=gamma, causal=causal)
     if fq:
-        fqd = oeh_fq_desc()
-        fqd.scores.enable, fqd.scores.scale, fqd.scores.qmax = 1, 1.0, 255.0
-        fqd.probs.enable, fqd.probs.scale, fqd.probs.qmax = 1, 1.0, 255.0
-        r = _lib.load().oeh_attn_decode_fq_variant(C.byref(d), C.byref(fqd), int(splits))
+        r = _lib.load().oeh_attn_decode_fq_variant(C.byref(d), C.byref(_fq_desc(_PROBE_FQ)), int(splits))
     else:
         r = _lib.load().oeh_attn_decode_variant(C.byref(d), int(splits))
     return None if r is None else r.decode()
@@ -812,8 +825,7 @@ def attn_decode_variant(B, H, Sq, Sk, D=64, dtype=torch.float16, *, clip: bool =
 def softmax_rows(x: torch.Tensor, spec: SoftmaxSpec = SoftmaxSpec(), dim: int = -1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """SOFTMAX_MAPPING callable on the GPU: softmax / softmax_1 / clipped variants along `dim`."""
     dev = _need_gpu(x, out)
-    if x.dtype not in _DT:
-        raise ValueError(f"unsupported dtype {x.dtype}")
+    _need_dtype(x)
     nd = x.dim()
     dim = dim % nd
     xt = x if dim == nd - 1 else x.transpose(dim, -1)
@@ -832,8 +844,7 @@ def softmax_rows(x: torch.Tensor, spec: SoftmaxSpec = SoftmaxSpec(), dim: int = 
 def fake_quant(x: torch.Tensor, spec: FakeQuantSpec, want_idx: bool = False):
     """Fixed-range per-tensor asymmetric fake-quant; returns x_q (and the uint8 indices if asked)."""
     dev = _need_gpu(x)
-    if x.dtype not in _DT:
-        raise ValueError(f"unsupported dtype {x.dtype}")
+    _need_dtype(x)
     xc = x.contiguous()
     y = torch.empty_like(xc)
     idx = torch.empty(xc.shape, dtype=torch.uint8, device=x.device) if want_idx else None
@@ -843,33 +854,17 @@ def fake_quant(x: torch.Tensor, spec: FakeQuantSpec, want_idx: bool = False):
     return (y, idx) if want_idx else y
 
 
-_calib_work = {}  # (device index, stream) -> scratch buffer of the on-device percentile selection (two calibrations on different
-                   # streams of one GPU must not share histograms: ADVICE r2)
-
-
-def _calib_scratch(dev):
-    """The current stream's 36-KB selection scratch on `dev`.  Bounded: streams come and go (a recycled handle simply reuses its
-    buffer), so beyond 32 entries the table starts over instead of keeping one buffer per stream ever seen."""
-    with _on_device(dev):
-        key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    work = _calib_work.get(key)
-    if work is None:
-        if len(_calib_work) >= 32:
-            _calib_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
-        work = _calib_work[key] = torch.empty(_lib.CALIB_WORK_BYTES // 8, dtype=torch.int64, device=dev)
-    return work
+_calib_work = {}  # (device index, stream handle) -> the 36-KB histograms of that stream's on-device percentile selection
 
 
 def percentile_ema(x: torch.Tensor, q_lo: float, q_hi: float, state: torch.Tensor, momentum: float = 0.9, first: bool = False) -> torch.Tensor:
     """(np.percentile(x, q_lo), np.percentile(x, q_hi)) blended into `state` (float64[2] on x's GPU) with the running average of
     RunningMinMaxEstimator (range_estimators.py:101-104), without leaving the device: `include/oeh.h: oeh_percentile_ema`."""
     dev = _need_gpu(x, state)
-    if x.dtype not in _DT:
-        raise ValueError(f"unsupported dtype {x.dtype}")
-    if state.dtype != torch.float64 or state.numel() != 2 or not state.is_contiguous():
-        raise ValueError("state must be a contiguous float64 tensor of 2 elements")
+    _need_dtype(x)
+    _need_f64(state, 2, "state must be a contiguous float64 tensor of 2 elements")
     xc = x.detach().contiguous()
-    work = _calib_scratch(dev)
+    work = _scratch(_calib_work, dev, _lib.CALIB_WORK_BYTES)
     with _on_device(dev):
         rc = _lib.load().oeh_percentile_ema(_ptr(xc), xc.numel(), _DT[x.dtype], float(q_lo), float(q_hi), float(momentum), int(bool(first)),
                                             _ptr(state), _ptr(work), _stream())
@@ -899,39 +894,26 @@ def attn_calibrate(q: torch.Tensor, k: torch.Tensor, v: Optional[torch.Tensor], 
         raise ValueError("q / k / v dtypes must match and be fp16 / bf16 / fp32")
     fix = lambda t: t if t is None or t.stride(3) == 1 else t.contiguous()  # noqa: E731
     q, k, v = fix(q), fix(k), fix(v)
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D, d.dtype = B, H, Sq, Sk, D, _DT[q.dtype]
     out = None
     if which == CALIB_CONTEXT:
         out = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v if v is not None else k), ("o_stride", out if out is not None else q)):
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    d.scale, d.scale_div = float(scale), float(scale_div)
-    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    # The statistics passes have no v (scores) and no output: the stride triples of the absent tensors are k's and q's.  o_dtype stays 0:
+    # the context is fp32 whatever the storage, and the entry point does not read the field.
+    d = _attn_desc(q, k, v if v is not None else k, out if out is not None else q, _DT[q.dtype], 0, softmax, scale, scale_div, causal, clamp_min,
+                   mask_min, q.dtype)
     keep = []
     if key_pad_mask is not None:
-        m = key_pad_mask.reshape(B, Sk)
-        m = (m if m.dtype in (torch.float16, torch.float32) else m.float()).contiguous()
-        keep.append(m)
-        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
+        _set_key_pad(d, keep, key_pad_mask)  # (key_pad_boolean stays 0: this entry point has no such argument)
     if full_mask is not None:
-        if full_mask.shape != (B, 1, Sq, Sk):
-            raise ValueError(f"Attention mask should be of size {(B, 1, Sq, Sk)}, but is {tuple(full_mask.shape)}")
-        m = full_mask if full_mask.dtype in (torch.float16, torch.float32) else full_mask.float()
-        m = m if m.stride(3) == 1 else m.contiguous()
-        keep.append(m)
-        d.full_mask, d.full_mask_dtype = m.data_ptr(), _DT[m.dtype]
-        d.full_mask_stride[:] = [m.stride(0), m.stride(2)]
-    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
-    d.mask_min = float(torch.finfo(q.dtype).min if mask_min is None else mask_min)
+        _set_full_mask(d, keep, full_mask)
     for r_ in (scores_range, probs_range, state):
-        if r_ is not None and (r_.dtype != torch.float64 or r_.numel() != 2 or not r_.is_contiguous()):
-            raise ValueError("ranges / state must be contiguous float64 tensors of 2 elements")
+        if r_ is not None:
+            _need_f64(r_, 2, "ranges / state must be contiguous float64 tensors of 2 elements")
     work = None
     if which != CALIB_CONTEXT:
         if state is None:
             raise ValueError("state (float64[2] on the device) is required for the statistics passes")
-        work = _calib_scratch(dev)
+        work = _scratch(_calib_work, dev, _lib.CALIB_WORK_BYTES)
     with _on_device(dev):
         rc = _lib.load().oeh_attn_calibrate(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out), int(which), _ptr(scores_range), _ptr(probs_range), int(n_bits),
                                             float(eps), float(q_lo), float(q_hi), float(momentum), int(bool(first)), _ptr(state), _ptr(work), _stream())
@@ -943,10 +925,8 @@ def fake_quant_range(x: torch.Tensor, xmin_xmax: torch.Tensor, n_bits: int = 8, 
     """Fake-quant with the grid derived on the device from a float64 (x_min, x_max) pair (`oeh_fake_quant_range`): the
     quantiser's forward while its range is still being estimated, without a host read of the range."""
     dev = _need_gpu(x, xmin_xmax)
-    if x.dtype not in _DT:
-        raise ValueError(f"unsupported dtype {x.dtype}")
-    if xmin_xmax.dtype != torch.float64 or xmin_xmax.numel() != 2 or not xmin_xmax.is_contiguous():
-        raise ValueError("xmin_xmax must be a contiguous float64 tensor of 2 elements")
+    _need_dtype(x)
+    _need_f64(xmin_xmax, 2, "xmin_xmax must be a contiguous float64 tensor of 2 elements")
     xc = x.contiguous()
     y = torch.empty_like(xc)
     with _on_device(dev):
@@ -993,21 +973,6 @@ STATS_INF_NORM, STATS_KURTOSIS, STATS_MEAN, STATS_STD = 0, 1, 2, 3  # columns of
 _stats_work = {}  # (device index, stream handle) -> the chunk records of that stream
 
 
-def _stats_scratch(dev, nbytes: int):
-    """The current stream's chunk-record buffer for `oeh_outlier_stats` on `dev`: kept, grown and bounded as `_decode_scratch` keeps the
-    split-key scratch, with a buffer of its own for a call under graph capture (it then lives in the graph's pool)."""
-    with _on_device(dev):
-        if torch.cuda.is_current_stream_capturing():
-            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    work = _stats_work.get(key)
-    if work is None or work.numel() * 8 < nbytes:
-        if len(_stats_work) >= 32:
-            _stats_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
-        work = _stats_work[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    return work
-
-
 def outlier_stats(x: torch.Tensor, eps: float = 1e-6, meter: Optional[torch.Tensor] = None, accumulate: int = 0, *,
                   out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-sample (inf_norm, kurtosis, mean, std) of `x` viewed as (x.shape[0], -1): a (rows, 4) fp32 tensor from one pass over the
@@ -1016,8 +981,7 @@ def outlier_stats(x: torch.Tensor, eps: float = 1e-6, meter: Optional[torch.Tens
     GPU, {sum_inf, n_inf, sum_kurt, n_kurt}; accumulate: 1 adds this call's inf-norms, 2 its kurtoses, 3 both.  out / work: caller's
     buffers (tests); by default the result is new and the chunk records live in one buffer per stream."""
     dev = _need_gpu(x, meter, out, work)
-    if x.dtype not in _DT:
-        raise ValueError(f"unsupported dtype {x.dtype}")
+    _need_dtype(x)
     if x.dim() < 2:
         raise ValueError("outlier_stats needs at least 2 dimensions: (samples, ...)")
     x = x.detach()
@@ -1026,8 +990,8 @@ def outlier_stats(x: torch.Tensor, eps: float = 1e-6, meter: Optional[torch.Tens
     if not (rows >= 1 and cols >= 1 and (x[0].is_contiguous() or cols == 1) and (rows == 1 or x.stride(0) >= cols)):
         x = x.contiguous()
     row_stride = x.stride(0) if rows > 1 else cols
-    if meter is not None and (meter.dtype != torch.float64 or meter.numel() != 4 or not meter.is_contiguous()):
-        raise ValueError("meter must be a contiguous float64 tensor of 4 elements")
+    if meter is not None:
+        _need_f64(meter, 4, "meter must be a contiguous float64 tensor of 4 elements")
     if out is None:
         out = torch.empty((rows, 4), dtype=torch.float32, device=x.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (rows, 4) or not out.is_contiguous():
@@ -1035,7 +999,7 @@ def outlier_stats(x: torch.Tensor, eps: float = 1e-6, meter: Optional[torch.Tens
     lib = _lib.load()
     nbytes = lib.oeh_outlier_stats_work_bytes(rows, cols)
     if work is None:
-        work = _stats_scratch(dev, nbytes) if nbytes else None
+        work = _scratch(_stats_work, dev, nbytes) if nbytes else None
     elif work.numel() * work.element_size() < nbytes:
         raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, the call needs {nbytes}")
     with _on_device(dev):
@@ -1066,20 +1030,6 @@ QMSE_F64_K = _lib.QMSE_F64_K            # calls of at most this many candidates 
 _qmse_work = {}  # (device index, stream handle) -> the per-workgroup sums of that stream
 
 
-def _qmse_scratch(dev, nbytes: int):
-    """The current stream's buffer of per-workgroup sums for `oeh_quant_mse` on `dev`, kept as `_stats_scratch` keeps the chunk records."""
-    with _on_device(dev):
-        if torch.cuda.is_current_stream_capturing():
-            return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    work = _qmse_work.get(key)
-    if work is None or work.numel() * 8 < nbytes:
-        if len(_qmse_work) >= 32:
-            _qmse_work.clear()  # (buffers still referenced by enqueued work stay alive in the caching allocator's stream order)
-        work = _qmse_work[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    return work
-
-
 def quant_grid_candidates(scale, lo, hi) -> torch.Tensor:
     """The (K, 4) fp32 candidate table of `quant_mse` from per-candidate scale, lo = int_min - zero_point and hi = int_max - zero_point
     (tensors or sequences of equal length; include/oeh.h documents the record)."""
@@ -1099,8 +1049,7 @@ def quant_mse(x: torch.Tensor, cand: torch.Tensor, loss: Optional[torch.Tensor] 
     Deviation: fp16 and bf16 elements are widened to fp32 first - the reference would square and sum in the storage type and overflow
     fp16.  A dense view is read in place (any starting element); anything else is made contiguous.  work: caller's scratch (tests)."""
     dev = _need_gpu(x, cand, loss, work)
-    if x.dtype not in _DT:
-        raise ValueError(f"unsupported dtype {x.dtype}")
+    _need_dtype(x)
     if cand.dtype != torch.float32 or cand.dim() != 2 or cand.shape[1] != 4 or not cand.is_contiguous():
         raise ValueError("cand must be a contiguous float32 tensor of shape (K, 4)")
     K = cand.shape[0]
@@ -1109,12 +1058,12 @@ def quant_mse(x: torch.Tensor, cand: torch.Tensor, loss: Optional[torch.Tensor] 
         x = x.contiguous()
     if loss is None:
         loss = (torch.zeros if accumulate else torch.empty)(K, dtype=torch.float64, device=x.device)
-    elif loss.dtype != torch.float64 or loss.numel() != K or not loss.is_contiguous():
-        raise ValueError("loss must be a contiguous float64 tensor of K elements")
+    else:
+        _need_f64(loss, K, "loss must be a contiguous float64 tensor of K elements")
     lib = _lib.load()
     nbytes = lib.oeh_quant_mse_work_bytes(x.numel(), K)
     if work is None:
-        work = _qmse_scratch(dev, max(nbytes, 8))
+        work = _scratch(_qmse_work, dev, max(nbytes, 8))
     elif work.numel() * work.element_size() < nbytes:
         raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, the call needs {nbytes}")
     with _on_device(dev):
@@ -1126,37 +1075,14 @@ def quant_mse(x: torch.Tensor, cand: torch.Tensor, loss: Optional[torch.Tensor] 
 # ---- training: the forward with its row statistic and the fused backward (include/oeh.h: oeh_attn_fwd_train / oeh_attn_bwd)
 def _train_desc(q, k, v, o, softmax, scale, scale_div, key_pad_mask, full_mask, causal, clamp_min, mask_min):
     """Descriptor + the mask views it points into, for the training entry points (fp16 / bf16, D = 64; the library refuses the rest)."""
-    B, H, Sq, D = q.shape
-    Sk = k.shape[2]
-    if k.shape != (B, H, Sk, D) or v.shape != (B, H, Sk, D):
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
-    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in _DT:
-        raise ValueError(f"q/k/v dtypes must match and be fp16/bf16/fp32, got {q.dtype}, {k.dtype}, {v.dtype}")
-    d = oeh_attn_desc()
-    d.B, d.H, d.Sq, d.Sk, d.D = B, H, Sq, Sk, D
-    d.dtype = _DT[q.dtype]
-    d.o_dtype = d.dtype
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    d.scale, d.scale_div = float(scale), float(scale_div)
-    d.softmax_base, d.clip, d.gamma, d.eta = int(softmax.base), int(bool(softmax.clip)), float(softmax.gamma), float(softmax.eta)
+    _check_qkv(q, k, v)  # (the callers hand over what `_rows16` made of their inputs: unit head-dim strides, nothing to replace)
+    d = _attn_desc(q, k, v, o, _DT[q.dtype], _DT[q.dtype], softmax, scale, scale_div, causal, clamp_min, mask_min, q.dtype)
     keep = []
+    # the masks may be part of an autograd graph here (the entry points allow it): detached, the views below record nothing
     if key_pad_mask is not None:
-        m = key_pad_mask.detach().reshape(B, Sk)
-        m = (m if m.dtype in (torch.float16, torch.float32) else m.float()).contiguous()
-        keep.append(m)
-        d.key_pad_mask, d.key_pad_dtype, d.key_pad_stride = m.data_ptr(), _DT[m.dtype], m.stride(0)
+        _set_key_pad(d, keep, key_pad_mask.detach())  # (key_pad_boolean stays 0: the training entry points have no such argument)
     if full_mask is not None:
-        if full_mask.shape != (B, 1, Sq, Sk):
-            raise ValueError(f"Attention mask should be of size {(B, 1, Sq, Sk)}, but is {tuple(full_mask.shape)}")
-        m = full_mask.detach()
-        m = m if m.dtype in (torch.float16, torch.float32) else m.float()
-        m = m if m.stride(3) == 1 else m.contiguous()
-        keep.append(m)
-        d.full_mask, d.full_mask_dtype = m.data_ptr(), _DT[m.dtype]
-        d.full_mask_stride[:] = [m.stride(0), m.stride(2)]
-    d.causal, d.clamp_min = int(bool(causal)), int(bool(clamp_min))
-    d.mask_min = float(torch.finfo(q.dtype).min if mask_min is None else mask_min)
+        _set_full_mask(d, keep, full_mask.detach())
     return d, keep
 
 

@@ -30,16 +30,8 @@ FORMS = {"softmax1": ops.SoftmaxSpec(1, False, 0.0, 1.0), "clippedsoftmax1(-.025
 
 
 def make_desc(q, k, v, o, spec):
-    d = _lib.oeh_attn_desc()
-    B, H, Sq, D = q.shape
-    d.B, d.H, d.Sq, d.Sk, d.D = B, H, Sq, k.shape[2], D
-    d.dtype = d.o_dtype = _lib.OEH_F16
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    d.scale = 1.0
-    d.softmax_base, d.clip, d.gamma, d.eta = spec.base, int(spec.clip), spec.gamma, spec.eta
-    d.causal, d.clamp_min, d.mask_min = 1, 1, float(np.finfo(np.float32).min)
-    return d
+    """fp16, unscaled, causal with clamp_min at fp32's minimum (OPT's decoder step)"""
+    return ops._attn_desc(q, k, v, o, _lib.OEH_F16, _lib.OEH_F16, spec, 1.0, 0.0, True, True, None, torch.float32)
 
 
 def calibrated_fq(q, k, v, spec):

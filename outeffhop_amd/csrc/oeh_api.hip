@@ -17,9 +17,9 @@ int launch_attn_mfma_d128(const AttnParams& P, int in, bool fq, hipStream_t st);
 int launch_attn_fast_d32(const AttnParams& P, int in, hipStream_t st);
 int launch_attn_fast_d64(const AttnParams& P, int in, hipStream_t st);
 int launch_attn_fast_d128(const AttnParams& P, int in, hipStream_t st);
-int launch_attn_flash_d32(const AttnParams& P, int in, int mq, hipStream_t st);
-int launch_attn_flash_d64(const AttnParams& P, int in, int mq, hipStream_t st);
-int launch_attn_flash_d128(const AttnParams& P, int in, int mq, hipStream_t st);
+int launch_attn_flash_d32(const AttnParams& P, const oeh::AttnHot* hot, int in, int mq, hipStream_t st);
+int launch_attn_flash_d64(const AttnParams& P, const oeh::AttnHot* hot, int in, int mq, hipStream_t st);
+int launch_attn_flash_d128(const AttnParams& P, const oeh::AttnHot* hot, int in, int mq, hipStream_t st);
 int launch_attn_generic(const AttnParams& P, int in, hipStream_t st);
 int launch_attn_small(const AttnParams& P, int in, hipStream_t st);
 int launch_attn_i8(const AttnParams& P, int out, hipStream_t st);
@@ -65,13 +65,15 @@ enum Hook {
   HOOK_PLAIN_ORDER = 1 << 9,    // tools/microbench.py only: plain block order in the one-pass kernel (no snake placement)
   HOOK_FORCE_SMALL = 1 << 10,   // tests: the small-shape kernel wherever it can run (no size heuristic)
   HOOK_NO_D128_RULE = 1 << 11,  // tests: the full-row kernel also for head dim 128 with clip / INT8 (the comparison against the general kernel)
-  HOOK_ALL = 0xfff              // (bit 12 and up: reserved, ignored)
+  HOOK_NO_HOT_ARGS = 1 << 13,   // tests / A-B: the one-pass kernel's plain forms from the AttnParams block alone (no hot argument prefix)
+  HOOK_ALL = 0x2fff             // (bit 12, bit 14 and up: reserved, ignored)
 };
 struct Hooks {
   int off;                      // off_mask & HOOK_ALL
   int flash_mq;                 // tools/microbench.py only: force query blocks per wave
   int head_group;               // tools/microbench.py only (OEH_HEAD_GROUP): block order of the fp32-storage kernels in groups of heads
   unsigned long long* stamps;   // tools/timeline.py only
+  long hot_launches;            // one-pass launches that took the hot argument prefix (oeh_debug_hot_launches)
 } g_hooks = {};
 
 // rows must be 16-byte aligned for the MFMA path's 16-B loads / 8..16-B stores
@@ -375,6 +377,24 @@ void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const voi
                std::isfinite(d->mask_min) && d->mask_min < -1e4f) ? 1 : 0;
 }
 
+// The hot argument prefix of the one-pass kernel (oeh_attn_params.h: AttnHot; P as the V_FLASH case has completed it).  True = the launch may
+// take the prefix form: the plain 16-bit kernel (no key padding / (B,1,Sq,Sk) mask, no in-kernel gate predictor, no clip / INT8 chain, no fp32
+// storage or output), q, k and v with the same three strides, and every packed field inside its bits.  Everything else keeps the AttnParams-only
+// launch.
+bool fill_hot(oeh::AttnHot& hot, const AttnParams& P) {
+  if (g_hooks.off & HOOK_NO_HOT_ARGS) return false;
+  if (P.pad != nullptr || P.full != nullptr || P.gh != nullptr || P.clip || P.fq_s.en || P.src32 || P.out32) return false;
+  if (P.qs_b != P.ks_b || P.qs_b != P.vs_b || P.qs_h != P.ks_h || P.qs_h != P.vs_h || P.qs_s != P.ks_s || P.qs_s != P.vs_s) return false;
+  // (strides: validate() keeps them in [0, 2^32))
+  if (P.H > oeh::kHotMaxH || P.nQT > oeh::kHotMaxNQT || P.Sq > oeh::kHotMaxS || P.Sk > oeh::kHotMaxS || P.nBHpad != ((P.nBH + 7) & ~7)) return false;
+  hot.q = P.q; hot.k = P.k; hot.v = P.v;
+  hot.nBH = P.nBH; hot.magic_nbh = P.magic_nbh; hot.magic_h = P.magic_h;
+  hot.geom = (unsigned)P.H | ((unsigned)P.nQT << 16) | (P.causal ? 1u << 30 : 0u) | (P.snake ? 1u << 31 : 0u);
+  hot.sqsk = (unsigned)P.Sq | ((unsigned)P.Sk << 16);
+  hot.s_b = (unsigned)P.qs_b; hot.s_h = (unsigned)P.qs_h; hot.s_s = (unsigned)P.qs_s;
+  return true;
+}
+
 // Everything oeh_attn_fwd[_ex] decides before it launches, and what oeh_attn_variant[_ex] print
 struct AttnPlan {
   int rc;       // OEH_OK, or the refusal (OEH_EINVAL / OEH_ENOTSUP / OEH_EALIGN)
@@ -482,9 +502,13 @@ int oeh_attn_fwd_ex(const oeh_attn_desc* desc, const oeh_attn_opts* opts, const 
       P.magic_nbh = (unsigned)(0x100000000ULL / (unsigned long long)P.nBHpad);
       return oeh::launch_attn_i8(P, desc->o_dtype, st);
     }
-    case V_FLASH:
+    case V_FLASH: {
       P.nQT = (desc->Sq + 64 * pl.mq - 1) / (64 * pl.mq);
-      return OEH_LAUNCH_BY_D(flash, P, desc->dtype, pl.mq, st);
+      oeh::AttnHot hot;
+      const bool with_hot = fill_hot(hot, P);
+      if (with_hot) ++g_hooks.hot_launches;  // (process-global like the hooks that read it: include/oeh_debug.h)
+      return OEH_LAUNCH_BY_D(flash, P, with_hot ? &hot : nullptr, desc->dtype, pl.mq, st);
+    }
     case V_FAST: return OEH_LAUNCH_BY_D(fast, P, desc->dtype, st);
     case V_MFMA: return OEH_LAUNCH_BY_D(mfma, P, desc->dtype, any_fq(fq), st);
     default: return oeh::launch_attn_generic(P, desc->dtype, st);
@@ -689,6 +713,8 @@ int oeh_debug_set_stamps(void* device_buffer) {
   g_hooks.stamps = static_cast<unsigned long long*>(device_buffer);
   return OEH_OK;
 }
+
+long oeh_debug_hot_launches(void) { return debug_hooks_on() ? g_hooks.hot_launches : (long)OEH_ENOTSUP; }
 
 int oeh_abi_version(void) { return OEH_ABI_VERSION; }
 

@@ -2,5 +2,5 @@
 #include "oeh_attn_flash.inl"
 
 namespace oeh {
-int launch_attn_flash_d32(const AttnParams& P, int in, int mq, hipStream_t st) { return launch_flash_d<32>(P, in, mq, st); }
+int launch_attn_flash_d32(const AttnParams& P, const AttnHot* hot, int in, int mq, hipStream_t st) { return launch_flash_d<32>(P, hot, in, mq, st); }
 }  // namespace oeh

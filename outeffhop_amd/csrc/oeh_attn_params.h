@@ -55,6 +55,24 @@ struct AttnParams {
   unsigned long long* stamps; // diagnostic builds only: per-wave s_memtime stamps (null in production)
 };
 
+// The hot argument prefix of the one-pass kernel's plain 16-bit forms (oeh_attn_flash.inl: oeh_attn_flash_hot_kernel): what the block-id
+// decode and the Q / K / V requests read, as LEADING SCALAR kernel arguments in front of the AttnParams block.  gfx950 delivers leading
+// scalar arguments in user SGPRs at wave launch (kernarg preload: 16 user SGPRs less the 2 of the segment pointer = 14 dwords; a by-value
+// struct is never preloaded), so a wave needs no memory round trip before its first request.  Exactly 14 dwords: nBHpad is the kernel's
+// (nBH + 7) & ~7, Sq and Sk share a dword, q / k / v share one set of strides (the host launches this form only then: oeh_api.hip,
+// fill_hot).  The kernel's parameter list spells the same fields in the same order (OEH_HOT_PARAMS / OEH_HOT_ARGS).
+struct AttnHot {
+  const void *q, *k, *v;
+  int nBH;
+  unsigned magic_nbh, magic_h;
+  unsigned geom;              // H [15:0] | nQT [27:16] | causal [30] | snake [31]
+  unsigned sqsk;              // Sq [15:0] | Sk [31:16]
+  unsigned s_b, s_h, s_s;     // (batch, head, row) strides in elements, the same for q, k and v
+};
+#define OEH_HOT_PARAMS const void *hq, const void *hk, const void *hv, int h_nbh, unsigned h_mnbh, unsigned h_mh, unsigned h_geom, unsigned h_sqsk, unsigned h_sb, unsigned h_sh, unsigned h_ss
+#define OEH_HOT_ARGS(X) (X).q, (X).k, (X).v, (X).nBH, (X).magic_nbh, (X).magic_h, (X).geom, (X).sqsk, (X).s_b, (X).s_h, (X).s_s
+constexpr int kHotMaxH = 0xffff, kHotMaxNQT = 0xfff, kHotMaxS = 0xffff;
+
 // The kernels' view of one quantiser from the ABI's oeh_fq (include/oeh.h; a template only so that this header does not need it): host side,
 // shared by every entry point that takes an oeh_fq_desc.
 template <class OehFq>

@@ -28,7 +28,8 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 TRANS = ("v_exp_f32", "v_log_f32", "v_rcp_f32", "v_rsq_f32", "v_sqrt_f32", "v_sin_f32", "v_cos_f32", "v_exp_f16", "v_log_f16", "v_rcp_f16",
          "v_rsq_f16", "v_sqrt_f16", "v_sin_f16", "v_cos_f16", "v_rcp_iflag_f32", "v_exp_legacy_f32", "v_log_legacy_f32")
 M0_FORBIDDEN = ("s_set_gpr_idx", "s_movrel", "v_movrel", "ds_gws", "s_sendmsg", "s_ttrace", "v_interp")
-NO_SPILL = ("oeh_attn_flash_kernelILi64ELi0ELi2ELb0ELb0ELb0ELi0ELb0E", "oeh_attn_flash_kernelILi64ELi1ELi2ELb0ELb0ELb0ELi0ELb0E")
+NO_SPILL = ("oeh_attn_flash_kernelILi64ELi0ELi2ELb0ELb0ELb0ELi0ELb0E", "oeh_attn_flash_kernelILi64ELi1ELi2ELb0ELb0ELb0ELi0ELb0E",
+            "oeh_attn_flash_hot_kernelILi64ELi0ELi2E", "oeh_attn_flash_hot_kernelILi64ELi1ELi2E")  # (and their hot-argument-prefix entries)
 
 
 def regs_of(tok: str):

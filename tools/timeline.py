@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic (GPU box): per-wave s_memtime timeline of the one-pass attention kernel: timeline.py causal B S [off_bits] [MQ] [Sk].
+off_bits 8192 (include/oeh_debug.h, bit 13): the launch form without the hot argument prefix.  The last table - launch entry - attributes the
+stretch between a wave's first instruction and its first data: entry -> arguments ready -> first LDS-DMA request -> Q + K tile 0 landed.
 Needs the stamped build: `make -C outeffhop_amd/csrc timeline` (-> outeffhop_amd/lib/timeline/liboeh_hip.so; the production
 kernels carry no stamp code), loaded here through OEH_LIB.
 Never quote run times from this build path: the stamps perturb the schedule; read the SHARES."""
@@ -28,8 +30,11 @@ q = (torch.randn(B, S, H * D, device="cuda", generator=g) * D ** -0.5).half().vi
 k = torch.randn(B, SK, H * D, device="cuda", generator=g).half().view(B, SK, H, D).permute(0, 2, 1, 3)
 v = torch.randn(B, SK, H * D, device="cuda", generator=g).half().view(B, SK, H, D).permute(0, 2, 1, 3)
 kw = dict(causal=bool(causal), clamp_min=bool(causal), mask_min=float(np.finfo(np.float32).min))
+lib.oeh_debug_hot_launches.restype = C.c_long
+hot0 = lib.oeh_debug_hot_launches()
 for _ in range(3):
     ops.attn_fwd(q, k, v, **kw)
+print(f"launch form: {'hot argument prefix (SGPR preload)' if lib.oeh_debug_hot_launches() > hot0 else 'AttnParams block only'}; B={B} H={H} S={S} Sk={SK} MQ={MQ} causal={causal}")
 nqt = (S + 64 * MQ - 1) // (64 * MQ)
 nwg = nqt * B * H
 buf = torch.zeros(nwg * 4 * 32, dtype=torch.int64, device="cuda")
@@ -38,8 +43,9 @@ ops.attn_fwd(q, k, v, **kw)
 torch.cuda.synchronize()
 lib.oeh_debug_set_stamps(C.c_void_p(0))
 st = buf.cpu().numpy().reshape(nwg, 4, 32).astype(np.int64)
-names = ["start", "prologue", "loopdone", "end"] + [f"{a}{i}" for i in range(8) for a in ("bar", "iss", "cmp")]
-order = [0, 1] + list(range(4, 28)) + [2, 3]
+# slot 0: the wave's entry (its second instruction; slot 30: s_memrealtime, its first); 28: arguments ready; 4: first LDS-DMA request issued; 5: first stages issued
+names = ["start", "prologue", "loopdone", "end"] + [f"{a}{i}" for i in range(8) for a in ("req" if i == 0 else "bar", "iss", "cmp")] + ["args"]
+order = [0, 28, 4, 5, 1] + list(range(6, 28)) + [2, 3]
 for wg in (0, nwg // 3, nwg - 1):   # block ids: heaviest q tiles first
     w0 = st[wg, :, 0].min()
     print(f"--- workgroup {wg}: s_memtime ticks since its first wave started")
@@ -80,3 +86,15 @@ for lv in sorted(set(loads.tolist())):
     sel = loads == lv
     print(f"  CUs with {lv:3d} tiles: {int(sel.sum()):3d}, last workgroup ends at median +{int(np.median(ends[sel])) * 10} ns")
 print("example CU -> block ids:", list(per_cu.items())[:4])
+
+# ---- launch entry: where a wave's time goes between its first instruction and its first data (per q-tile class, medians over the waves)
+ghz = float(np.median(clk))
+e2a, a2r, r2l = st[:, :, 28] - st[:, :, 0], st[:, :, 4] - st[:, :, 28], st[:, :, 1] - st[:, :, 4]
+first = rs - r0   # the workgroup's first entry stamp after the launch's first (100 MHz real time)
+print(f"launch entry, medians in ticks (ns at {ghz:.2f} GHz): entry -> arguments ready | arguments ready -> first request issued | first request -> Q + K tile 0 landed | first stamp after the launch's first wave")
+def _row(label, sel):
+    f = lambda x: f"{int(np.median(x[sel])):6d} ({np.median(x[sel]) / ghz:7.0f} ns)"
+    print(f" {label:12s} {f(e2a)} | {f(a2r)} | {f(r2l)} | +{int(np.median(first[sel])) * 10} ns")
+for qt in range(nqt):
+    _row(f"q tile {qt}", slice((nqt - 1 - qt) * B * H, (nqt - qt) * B * H))
+_row("all", slice(0, nwg))

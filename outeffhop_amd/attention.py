@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from ._watch import cached
 from .ops import AttnFakeQuant, SoftmaxSpec
 from .softmax import spec_of
 
@@ -152,23 +153,20 @@ class GateState:
 
     @staticmethod
     def packed_weights(mod: nn.Module):
-        """Per-head predictor weights stacked as (H,d)/(H) or (H,m,d)/(H,m)/(H,m)/(H); cached until a parameter changes."""
+        """Per-head predictor weights stacked as (H,d)/(H) or (H,m,d)/(H,m)/(H,m)/(H); cached until a parameter (or a head module) changes."""
         heads = mod.alpha
-        sig = tuple((p.data_ptr(), p._version) for p in heads.parameters())
-        cache = getattr(mod, "_oeh_gate_cache", None)
-        if cache is not None and cache[0] == sig:
-            return cache[1]
-        with torch.no_grad():
-            if isinstance(heads[0], nn.Linear):
-                packed = (torch.stack([h.weight[0] for h in heads]).float().contiguous(),
-                          torch.stack([h.bias[0] for h in heads]).float().contiguous(), None, None)
-            else:
-                packed = (torch.stack([h[0].weight for h in heads]).float().contiguous(),
-                          torch.stack([h[0].bias for h in heads]).float().contiguous(),
-                          torch.stack([h[2].weight[0] for h in heads]).float().contiguous(),
-                          torch.stack([h[2].bias[0] for h in heads]).float().contiguous())
-        mod._oeh_gate_cache = (sig, packed)
-        return packed
+        layers = tuple(heads.modules())
+
+        def pack():
+            with torch.no_grad():
+                if isinstance(heads[0], nn.Linear):
+                    return (torch.stack([h.weight[0] for h in heads]).float().contiguous(),
+                            torch.stack([h.bias[0] for h in heads]).float().contiguous(), None, None)
+                return (torch.stack([h[0].weight for h in heads]).float().contiguous(),
+                        torch.stack([h[0].bias for h in heads]).float().contiguous(),
+                        torch.stack([h[2].weight[0] for h in heads]).float().contiguous(),
+                        torch.stack([h[2].bias[0] for h in heads]).float().contiguous())
+        return cached(mod.__dict__, "_oeh_gate_cache", layers, lambda: [(m._parameters, n_) for m in layers for n_ in m._parameters], pack)
 
     @staticmethod
     def predictor(mod: nn.Module, hidden_states: torch.Tensor, num_heads: int, scaling: float):
@@ -233,19 +231,18 @@ def fused_qkv(owner: nn.Module, x: torch.Tensor, lq: nn.Linear, lk: nn.Linear, l
     mant, _ = math.frexp(q_scale)
     if mant != 0.5:
         return None
-    key = tuple((t._version, t.data_ptr()) for t in ws + tuple(b for b in bs if b is not None)) + (q_scale, x.dtype)
-    cache = owner.__dict__.get("_oeh_qkv_cache")
     triple = triple_gemm_ok(x, lq, lk, lv)
-    key = key + (triple,)
-    if cache is None or cache[0] != key:
+
+    def concat():  # (the two layouts: the triple GEMM's operand with the bias inside | weight and bias)
         w = torch.cat([ws[0].detach() * q_scale, ws[1].detach(), ws[2].detach()], dim=0).contiguous()
         b = None if bs[0] is None else torch.cat([bs[0].detach() * q_scale, bs[1].detach(), bs[2].detach()], dim=0).contiguous()
-        cache = (key, triple_weights(w, b), None) if triple else (key, w, b)
-        owner.__dict__["_oeh_qkv_cache"] = cache
+        return (triple_weights(w, b), None) if triple else (w, b)
+    w, b = cached(owner.__dict__, "_oeh_qkv_cache", (lq, lk, lv, q_scale, x.dtype, triple),
+                  lambda: [(m._parameters, n_) for m in (lq, lk, lv) for n_ in ("weight", "bias")], concat)
     if triple:  # fp32 model: one fp16 GEMM on operand triples (bias inside), fp32-accurate
-        y = torch.mm(ops.split_triples(x.reshape(-1, x.shape[-1])), cache[1], out_dtype=torch.float32).view(*x.shape[:-1], cache[1].shape[1])
+        y = torch.mm(ops.split_triples(x.reshape(-1, x.shape[-1])), w, out_dtype=torch.float32).view(*x.shape[:-1], w.shape[1])
     else:
-        y = torch.nn.functional.linear(x, cache[1], cache[2])
+        y = torch.nn.functional.linear(x, w, b)
     e = ws[0].shape[0]
     return y[..., :e], y[..., e:2 * e], y[..., 2 * e:]
 
@@ -284,17 +281,20 @@ def linear_fp32(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
     parameter changes), the module's own forward otherwise."""
     if not triple_gemm_ok(x, lin):
         return lin(x)
-    key = (lin.weight._version, lin.weight.data_ptr(), None if lin.bias is None else (lin.bias._version, lin.bias.data_ptr()))
-    cache = lin.__dict__.get("_oeh_triple_cache")
-    if cache is None or cache[0] != key:
-        cache = (key, triple_weights(lin.weight, lin.bias))
-        lin.__dict__["_oeh_triple_cache"] = cache
+    w3 = cached(lin.__dict__, "_oeh_triple_cache", None, lambda: [(lin._parameters, "weight"), (lin._parameters, "bias")],
+                lambda: triple_weights(lin.weight, lin.bias))
     a = ops.split_triples(x.reshape(-1, x.shape[-1]))
-    return torch.mm(a, cache[1], out_dtype=torch.float32).view(*x.shape[:-1], lin.out_features)
+    return torch.mm(a, w3, out_dtype=torch.float32).view(*x.shape[:-1], lin.out_features)
 
 
 def has_hooks(*mods: nn.Module) -> bool:
     return any(len(m._forward_hooks) or len(m._forward_pre_hooks) for m in mods)
+
+
+def mask_min_of(attention_mask: Optional[torch.Tensor], fallback_dtype: torch.dtype) -> float:
+    """The floor of a masked score: finfo.min of a floating mask's dtype, else of `fallback_dtype` (the activations')."""
+    mdt = attention_mask.dtype if attention_mask is not None and attention_mask.is_floating_point() else fallback_dtype
+    return float(torch.finfo(mdt).min)
 
 
 def split_mask(mask: Optional[torch.Tensor], B: int, Sq: int, Sk: int):
@@ -433,8 +433,7 @@ def attention_core(
         if causal:
             full, pad = None, padvec
     if mask_min is None:
-        mdt = attention_mask.dtype if attention_mask is not None and attention_mask.is_floating_point() else q.dtype
-        mask_min = float(torch.finfo(mdt).min)
+        mask_min = mask_min_of(attention_mask, q.dtype)
     # the fused INT8 chain stays on the quantiser grid with padded keys when the mask is a mask (0 / finfo.min entries - what
     # classify_causal has verified for a decoder mask; else one look per mask tensor object): include/oeh.h key_pad_boolean
     pad_bool = pad is not None and fq is not None and (causal or pad_is_boolean(attention_mask))

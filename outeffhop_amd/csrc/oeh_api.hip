@@ -3,46 +3,12 @@
 #include "../../include/oeh.h"
 #include "../../include/oeh_debug.h"
 #include "oeh_gemm.h"
-#include "oeh_attn_params.h"
+#include "oeh_launch.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-
-namespace oeh {
-int launch_attn_mfma_d32(const AttnParams& P, int in, bool fq, hipStream_t st);
-int launch_attn_mfma_d64(const AttnParams& P, int in, bool fq, hipStream_t st);
-int launch_attn_mfma_d128(const AttnParams& P, int in, bool fq, hipStream_t st);
-int launch_attn_fast_d32(const AttnParams& P, int in, hipStream_t st);
-int launch_attn_fast_d64(const AttnParams& P, int in, hipStream_t st);
-int launch_attn_fast_d128(const AttnParams& P, int in, hipStream_t st);
-int launch_attn_flash_d32(const AttnParams& P, const oeh::AttnHot* hot, int in, int mq, hipStream_t st);
-int launch_attn_flash_d64(const AttnParams& P, const oeh::AttnHot* hot, int in, int mq, hipStream_t st);
-int launch_attn_flash_d128(const AttnParams& P, const oeh::AttnHot* hot, int in, int mq, hipStream_t st);
-int launch_attn_generic(const AttnParams& P, int in, hipStream_t st);
-int launch_attn_small(const AttnParams& P, int in, hipStream_t st);
-int launch_attn_i8(const AttnParams& P, int out, hipStream_t st);
-int launch_softmax_rows(const void* x, void* y, long rows, int cols, int in, int base, int clip, float w, float g, hipStream_t st);
-int launch_fake_quant(const void* x, void* y, unsigned char* idx, long n, int in, FqP f, hipStream_t st);
-int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_b, long hs_t, const float* w1, const float* b1,
-                const float* w2, const float* b2, int m_units, int pool, float scaling, float* out, hipStream_t st);
-int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st);
-int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_hi, double momentum, int first, double* state, void* work,
-                          hipStream_t st);
-long stats_chunks(long cols);
-int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,
-                         hipStream_t st);
-long qmse_blocks(long n, long* nch_out, long* cpb_out);
-int launch_quant_mse(const void* x, long n, int in, const float* cand, int K, double* loss, int accumulate, void* work, hipStream_t st);
-int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st);
-int launch_attn_calibrate(const AttnParams& P, int in, int which, const double* s_range, const double* p_range, float qmax, double eps, double q_lo,
-                          double q_hi, double momentum, int first, double* state, void* work, hipStream_t st);
-int launch_split_pairs(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st);
-int launch_split_triples(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st);
-int launch_quantize_heads_i8(const void* x, signed char* out, void* y, long B, int S, int H, long x_sb, long x_ss, long y_sb, long y_ss, int in,
-                             FqP f, int transpose, float alpha, const float* bias, hipStream_t st);
-}  // namespace oeh
 
 using oeh::AttnParams;
 using oeh::FqP;

@@ -22,7 +22,7 @@
 // probabilities therefore is, for the next product, the lane's own k-slots: slot j of lane group g is row 16 t0 + 4 g + j (j < 4)
 // or 16 t1 + 4 g + j - 4, and the other operand is read from a TRANSPOSED LDS image in that order (two ds_read_b64).
 #include "../../include/oeh.h"
-#include "oeh_common.h"
+#include "oeh_launch.h"
 #include "oeh_philox.h"
 
 #include <algorithm>
@@ -604,8 +604,6 @@ void fill(Params& P, const oeh_attn_desc* d) {
   P.nKT = (d->Sk + T - 1) / T;
 }
 
-int launched() { return hipGetLastError() == hipSuccess ? OEH_OK : OEH_ELAUNCH; }
-
 // the dropout descriptor (include/oeh.h: oeh_dropout): p in [0, 1), NaN refused; checked before anything else of an entry point
 int check_drop(const oeh_dropout* drop) {
   if (drop == nullptr) return OEH_EINVAL;
@@ -657,7 +655,7 @@ int fwd_train(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q,
     if (dr) hipLaunchKernelGGL((fwd_kernel<IN_F16, true>), grid, dim3(256), 0, st, P);
     else hipLaunchKernelGGL((fwd_kernel<IN_F16, false>), grid, dim3(256), 0, st, P);
   }
-  return launched();
+  return oeh::launch_status();
 }
 
 int bwd_run(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, const void* k, const void* v, const void* o, const void* do_,
@@ -704,7 +702,7 @@ int bwd_run(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, c
       hipLaunchKernelGGL((dkdv_kernel<IN_F16, false>), gk, dim3(256), 0, st, P);
     }
   }
-  return launched();
+  return oeh::launch_status();
 }
 
 }  // namespace bwd
@@ -759,7 +757,7 @@ int oeh_attn_dropout_mask(const oeh_attn_desc* desc, const oeh_dropout* drop, ui
   const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 16384);
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), keep, desc->B * desc->H, desc->Sq,
                      desc->Sk, P.drop_k0, P.drop_k1, P.drop_thr);
-  return launched();
+  return oeh::launch_status();
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 //    bf16), a plain sum that applies the probability scale in fp32; the context quantiser and the gate, in either order, sit in the last launch.
 //    Exponentials that feed a quantiser are the ~1 ulp exp_acc_nonpos, as in the other fake-quant kernels.
 #include "../../include/oeh.h"
-#include "oeh_attn_params.h"
+#include "oeh_launch.h"
 
 #include <cmath>
 #include <cstdio>
@@ -392,7 +392,7 @@ int launch_decode_in(const DecodeParams& DP, hipStream_t st, const bool fq) {
     hipLaunchKernelGGL((oeh_attn_decode_partial<IN, DEC_PLAIN>), grid, block, 0, st, DP);
     hipLaunchKernelGGL((oeh_attn_decode_combine<false>), cgrid, block, 0, st, DP);
   }
-  return hipGetLastError() == hipSuccess ? OEH_OK : OEH_ELAUNCH;
+  return launch_status();
 }
 
 }  // namespace

@@ -944,7 +944,7 @@ static int launch_fast_nt_d(const AttnParams& P, int in, hipStream_t st) {
   const unsigned grid = (unsigned)(P.nQT * P.nBHpad);
   const bool launched = in == IN_BF16 ? launch_fast_nt_d_in<NT, D, IN_BF16>(P, grid, st) : launch_fast_nt_d_in<NT, D, IN_F16>(P, grid, st);
   if (!launched) return -95;  // OEH_ENOTSUP
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 template <int D>

@@ -171,7 +171,7 @@ static int launch_flash_d_mq(const AttnParams& P, const AttnHot* hot, int in, hi
   const unsigned grid = (unsigned)(P.nQT * P.nBHpad);
   const bool launched = in == IN_BF16 ? launch_flash_d_mq_in<D, MQ, IN_BF16>(P, hot, grid, st) : launch_flash_d_mq_in<D, MQ, IN_F16>(P, hot, grid, st);
   if (!launched) return -95;  // OEH_ENOTSUP
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 // P.nQT = ceil(Sq / (64*MQ)) workgroups per head; MQ is AttnPlan.mq (oeh_api.hip: flash_mq)

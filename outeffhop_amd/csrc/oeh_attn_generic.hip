@@ -3,10 +3,11 @@
 // path (STanHop's tiny (L,S<=64, E=16) problems hopfield.py:42-51, ViT head dims, Sk > 512); the MFMA
 // kernel in oeh_attn_mfma.hip is the fast path for D in {32,64,128}, Sk <= 512.  Same op order as the
 // reference chain; the score row lives in LDS as fp32.
-#include "oeh_attn_params.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
+// (the butterflies written out, not oeh_stream.h's wave_max / wave_sum: either one reorders this kernel - profiles/stream_helpers.txt)
 __device__ __forceinline__ float block_reduce_max(float v, float* red) {
   for (int o = 32; o > 0; o >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, o));
   const int w = threadIdx.x >> 6;
@@ -118,12 +119,8 @@ int launch_attn_generic(const AttnParams& P, int in, hipStream_t st) {
   if (shmem > 64 * 1024) return -95;  // default dynamic-LDS limit; Sk up to ~16k
   const long nblk = (long)P.B * P.H * P.Sq;
   if (nblk > 0x7fffffffL) return -95;
-  switch (in) {
-    case IN_F16: hipLaunchKernelGGL(oeh_attn_generic_kernel<IN_F16>, dim3((unsigned)nblk), dim3(128), shmem, st, P); break;
-    case IN_BF16: hipLaunchKernelGGL(oeh_attn_generic_kernel<IN_BF16>, dim3((unsigned)nblk), dim3(128), shmem, st, P); break;
-    default: hipLaunchKernelGGL(oeh_attn_generic_kernel<IN_F32>, dim3((unsigned)nblk), dim3(128), shmem, st, P); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(oeh_attn_generic_kernel<decltype(t)::value>, dim3((unsigned)nblk), dim3(128), shmem, st, P); });
+  return launch_status();
 }
 
 }  // namespace oeh

@@ -447,15 +447,15 @@ static int launch_i8_nt(const AttnParams& P, int out, hipStream_t st) {
   if (P.fq_s.dump != nullptr || P.fq_p.dump != nullptr || P.fq_c.dump != nullptr) {  // tests: the index tensors written out (fp32 output only)
     if (out != IN_F32) return -95;
     launch_i8_variant<NT, IN_F32, true>(P, grid, st);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_status();
   }
-  switch (out) {
+  switch (out) {  // (not dispatch_in: the OUTPUT type, with the int8 indices as a fourth case)
     case IN_F16: launch_i8_variant<NT, IN_F16, false>(P, grid, st); break;
     case IN_BF16: launch_i8_variant<NT, IN_BF16, false>(P, grid, st); break;
     case 3: launch_i8_variant<NT, 3, false>(P, grid, st); break;  // int8 centred indices (ctx_emit_index)
     default: launch_i8_variant<NT, IN_F32, false>(P, grid, st); break;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 // D == 64, Sk <= 512 and a multiple of 16, scores and probabilities on 8-bit grids (oeh_api.hip: i8_eligible)

@@ -21,7 +21,7 @@
 //  * One workgroup = 4 waves = 64 query rows of one (batch, head); q tiles of a head sit on one XCD
 //    (block ids a multiple of 8 apart) so K/V re-reads hit that XCD's L2; heaviest causal tiles first.
 #pragma once
-#include "oeh_attn_params.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
@@ -526,31 +526,17 @@ template <int NT, int D, int IN, int FQ>
 static int launch_one(const AttnParams& P, hipStream_t st) {
   const unsigned grid = (unsigned)(P.nQT * P.nBHpad);
   hipLaunchKernelGGL((oeh_attn_mfma_kernel<NT, D, IN, FQ>), dim3(grid), dim3(256), 0, st, P);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 template <int NT, int D>
 static int launch_nt_d(const AttnParams& P, int in, bool fq, hipStream_t st) {
   if (fq) {
     const bool grid_chain = P.fq_s.en && P.fq_p.en && P.pad == nullptr && P.full == nullptr && P.scale_div == 0.0f;
-    if (grid_chain) {
-      switch (in) {
-        case IN_F16: return launch_one<NT, D, IN_F16, 1>(P, st);
-        case IN_BF16: return launch_one<NT, D, IN_BF16, 1>(P, st);
-        default: return launch_one<NT, D, IN_F32, 1>(P, st);
-      }
-    }
-    switch (in) {
-      case IN_F16: return launch_one<NT, D, IN_F16, 2>(P, st);
-      case IN_BF16: return launch_one<NT, D, IN_BF16, 2>(P, st);
-      default: return launch_one<NT, D, IN_F32, 2>(P, st);
-    }
+    if (grid_chain) return dispatch_in(in, [&](auto t) { return launch_one<NT, D, decltype(t)::value, 1>(P, st); });
+    return dispatch_in(in, [&](auto t) { return launch_one<NT, D, decltype(t)::value, 2>(P, st); });
   }
-  switch (in) {
-    case IN_F16: return launch_one<NT, D, IN_F16, 0>(P, st);
-    case IN_BF16: return launch_one<NT, D, IN_BF16, 0>(P, st);
-    default: return launch_one<NT, D, IN_F32, 0>(P, st);
-  }
+  return dispatch_in(in, [&](auto t) { return launch_one<NT, D, decltype(t)::value, 0>(P, st); });
 }
 
 template <int D>

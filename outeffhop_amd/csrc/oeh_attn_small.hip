@@ -16,7 +16,7 @@
 //   * the reference's op order on the elements: scale (multiply or true division), max, 1-ulp exp, sum, [+exp(-m)], divide,
 //     [clip]; all four Association modes (softmax, softmax1, clip, clip_softmax1) and an optional gate.
 // Masks, fake-quant and the in-kernel gate predictor are not part of this path (oeh_api.hip: small_eligible).
-#include "oeh_attn_params.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
@@ -165,12 +165,8 @@ static int launch_small_et_st(const AttnParams& P, int in, hipStream_t st) {
   const long waves = Q.nQT == 1 ? (long)P.nBH * nqb : (long)P.nBH;
   Q.magic_nbh = Q.nQT == 1 ? (unsigned)(0x100000000ULL / (unsigned long long)nqb) : 0xffffffffu;  // floor(2^32 / waves per problem)
   const unsigned grid = (unsigned)((waves + 3) / 4);
-  switch (in) {
-    case IN_F16: hipLaunchKernelGGL((oeh_attn_small_kernel<ET, ST, IN_F16>), dim3(grid), dim3(256), 0, st, Q); break;
-    case IN_BF16: hipLaunchKernelGGL((oeh_attn_small_kernel<ET, ST, IN_BF16>), dim3(grid), dim3(256), 0, st, Q); break;
-    default: hipLaunchKernelGGL((oeh_attn_small_kernel<ET, ST, IN_F32>), dim3(grid), dim3(256), 0, st, Q); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  dispatch_in(in, [&](auto t) { hipLaunchKernelGGL((oeh_attn_small_kernel<ET, ST, decltype(t)::value>), dim3(grid), dim3(256), 0, st, Q); });
+  return launch_status();
 }
 
 template <int ET>

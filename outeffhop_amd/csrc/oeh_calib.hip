@@ -11,7 +11,7 @@
 //                        kernel from the (x_min, x_max) pair in device memory exactly as set_quant_range does
 //                        (uniform_quantizers.py:72-82), so the host never reads the range while it is still moving.
 // The selection reads the tensor four times (a 50 M-element score tensor: ~0.2 ms) instead of sorting it.
-#include "oeh_attn_params.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void calib_next_kernel(const void* __restrict_
     if (k > alo) nx_lo = min(nx_lo, k);
     if (k > ahi) nx_hi = min(nx_hi, k);
   }
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // (four butterflies interleaved; oeh_stream.h's one after the other are a different stream)
     cle_lo += __shfl_xor(cle_lo, o);
     cle_hi += __shfl_xor(cle_hi, o);
     nx_lo = min(nx_lo, (unsigned)__shfl_xor((int)nx_lo, o));
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256) void attn_calib_kernel(const AttnParams P, con
       }
     }
   } else {
-    for (int o_ = 32; o_ > 0; o_ >>= 1) {
+    for (int o_ = 32; o_ > 0; o_ >>= 1) {  // (interleaved, as in calib_next_kernel)
       cle_lo += __shfl_xor(cle_lo, o_);
       cle_hi += __shfl_xor(cle_hi, o_);
       nx_lo = min(nx_lo, (unsigned)__shfl_xor((int)nx_lo, o_));
@@ -440,15 +440,11 @@ int launch_attn_calibrate(const AttnParams& P, int in, int which, const double* 
   A.which = which; A.pass = 0; A.s_range = s_range; A.p_range = p_range; A.qmax = qmax; A.eps = eps; A.work = work;
   auto pass = [&](int p) {
     A.pass = p;
-    switch (in) {
-      case IN_F16: launch_attn_calib_pass<IN_F16>(P, A, st); break;
-      case IN_BF16: launch_attn_calib_pass<IN_BF16>(P, A, st); break;
-      default: launch_attn_calib_pass<IN_F32>(P, A, st); break;
-    }
+    dispatch_in(in, [&](auto t) { launch_attn_calib_pass<decltype(t)::value>(P, A, st); });
   };
   if (which == 2) {
     pass(0);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_status();
   }
   const long n = (long)P.B * P.H * P.Sq * P.Sk;
   const double h_lo = (double)(n - 1) * (q_lo / 100.0), h_hi = (double)(n - 1) * (q_hi / 100.0);
@@ -463,11 +459,8 @@ int launch_attn_calibrate(const AttnParams& P, int in, int which, const double* 
   hipLaunchKernelGGL((calib_scan_kernel<8>), dim3(1), dim3(256), 0, st, work);
   pass(3);
   hipLaunchKernelGGL(calib_finish_kernel, dim3(1), dim3(1), 0, st, work, i_lo, i_hi, f_lo, f_hi, (unsigned long long)n, momentum, first, state);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
-
-namespace {
-}  // namespace
 
 int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_hi, double momentum, int first, double* state, void* workv,
                           hipStream_t st) {
@@ -478,13 +471,9 @@ int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_h
   const double f_lo = h_lo - (double)i_lo, f_hi = h_hi - (double)i_hi;
   const unsigned blocks = (unsigned)((n + 256L * 16 - 1) / (256L * 16) < 2048 ? (n + 256L * 16 - 1) / (256L * 16) : 2048);
   hipLaunchKernelGGL(calib_init_kernel, dim3(1), dim3(256), 0, st, work, i_lo, i_hi);
-  switch (in) {
-    case IN_F16: launch_passes<IN_F16>(x, n, work, blocks, st); break;
-    case IN_BF16: launch_passes<IN_BF16>(x, n, work, blocks, st); break;
-    default: launch_passes<IN_F32>(x, n, work, blocks, st); break;
-  }
+  dispatch_in(in, [&](auto t) { launch_passes<decltype(t)::value>(x, n, work, blocks, st); });
   hipLaunchKernelGGL(calib_finish_kernel, dim3(1), dim3(1), 0, st, work, i_lo, i_hi, f_lo, f_hi, (unsigned long long)n, momentum, first, state);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 // ---- fake-quant with the grid derived from a device-resident (x_min, x_max) pair
@@ -510,12 +499,8 @@ __global__ __launch_bounds__(256) void fake_quant_range_kernel(const void* __res
 
 int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st) {
   const unsigned blocks = (unsigned)((n + 256L * 8 - 1) / (256L * 8) < 4096 ? (n + 256L * 8 - 1) / (256L * 8) : 4096);
-  switch (in) {
-    case IN_F16: hipLaunchKernelGGL(fake_quant_range_kernel<IN_F16>, dim3(blocks), dim3(256), 0, st, x, y, n, range, qmax, eps); break;
-    case IN_BF16: hipLaunchKernelGGL(fake_quant_range_kernel<IN_BF16>, dim3(blocks), dim3(256), 0, st, x, y, n, range, qmax, eps); break;
-    default: hipLaunchKernelGGL(fake_quant_range_kernel<IN_F32>, dim3(blocks), dim3(256), 0, st, x, y, n, range, qmax, eps); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(fake_quant_range_kernel<decltype(t)::value>, dim3(blocks), dim3(256), 0, st, x, y, n, range, qmax, eps); });
+  return launch_status();
 }
 
 }  // namespace oeh
@@ -536,7 +521,7 @@ __device__ __forceinline__ void load16_affine(const void* xp_, float (&v)[16], f
       const f4 t = p[q];
       v[4 * q] = t[0]; v[4 * q + 1] = t[1]; v[4 * q + 2] = t[2]; v[4 * q + 3] = t[3];
     }
-  } else {
+  } else {  // (not unpack16: it reorders quantize_heads_t_kernel<IN_F16, true>, which no bench times - profiles/stream_helpers.txt)
     const u4* p = reinterpret_cast<const u4*>(xp_);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -568,7 +553,7 @@ __device__ __forceinline__ void store16(void* yp_, const float (&v)[16]) {
     f4* p = reinterpret_cast<f4*>(yp_);
 #pragma unroll
     for (int q = 0; q < 4; ++q) p[q] = f4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-  } else {
+  } else {  // (per-element conversions, not pack16's packed ones: profiles/stream_helpers.txt)
     u4* p = reinterpret_cast<u4*>(yp_);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -651,28 +636,20 @@ int launch_quantize_heads_i8(const void* x, signed char* out, void* y, long B, i
     const long rows = B * S;  // requires x_sb == S * x_ss (checked by the caller)
     const long total = rows * (H * 64 / 16);
     const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-#define OEH_QR(IN_) \
-    if (wy) hipLaunchKernelGGL((quantize_rows_kernel<IN_, true>), dim3(blocks), dim3(256), 0, st, x, out, y, rows, H * 64, x_ss, y_ss, f, alpha, bias); \
-    else hipLaunchKernelGGL((quantize_rows_kernel<IN_, false>), dim3(blocks), dim3(256), 0, st, x, out, y, rows, H * 64, x_ss, y_ss, f, alpha, bias)
-    switch (in) {
-      case IN_F16: OEH_QR(IN_F16); break;
-      case IN_BF16: OEH_QR(IN_BF16); break;
-      default: OEH_QR(IN_F32); break;
-    }
-#undef OEH_QR
+    dispatch_in(in, [&](auto t) {
+      constexpr int IN = decltype(t)::value;
+      if (wy) hipLaunchKernelGGL((quantize_rows_kernel<IN, true>), dim3(blocks), dim3(256), 0, st, x, out, y, rows, H * 64, x_ss, y_ss, f, alpha, bias);
+      else hipLaunchKernelGGL((quantize_rows_kernel<IN, false>), dim3(blocks), dim3(256), 0, st, x, out, y, rows, H * 64, x_ss, y_ss, f, alpha, bias);
+    });
   } else {
     const unsigned blocks = (unsigned)(B * H * ((S + 63) / 64));
-#define OEH_QT(IN_) \
-    if (wy) hipLaunchKernelGGL((quantize_heads_t_kernel<IN_, true>), dim3(blocks), dim3(256), 0, st, x, out, y, S, H, x_sb, x_ss, y_sb, y_ss, f, alpha, bias); \
-    else hipLaunchKernelGGL((quantize_heads_t_kernel<IN_, false>), dim3(blocks), dim3(256), 0, st, x, out, y, S, H, x_sb, x_ss, y_sb, y_ss, f, alpha, bias)
-    switch (in) {
-      case IN_F16: OEH_QT(IN_F16); break;
-      case IN_BF16: OEH_QT(IN_BF16); break;
-      default: OEH_QT(IN_F32); break;
-    }
-#undef OEH_QT
+    dispatch_in(in, [&](auto t) {
+      constexpr int IN = decltype(t)::value;
+      if (wy) hipLaunchKernelGGL((quantize_heads_t_kernel<IN, true>), dim3(blocks), dim3(256), 0, st, x, out, y, S, H, x_sb, x_ss, y_sb, y_ss, f, alpha, bias);
+      else hipLaunchKernelGGL((quantize_heads_t_kernel<IN, false>), dim3(blocks), dim3(256), 0, st, x, out, y, S, H, x_sb, x_ss, y_sb, y_ss, f, alpha, bias);
+    });
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 }  // namespace oeh
@@ -743,14 +720,14 @@ int launch_split_triples(const float* x, void* out, long rows, int K, long x_sr,
   const long total = rows * ((long)K / 8 + 1);
   const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(split_triples_kernel, dim3(blocks), dim3(256), 0, st, x, static_cast<unsigned short*>(out), rows, K, x_sr);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 int launch_split_pairs(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st) {
   const long total = rows * (K / 8);
   const unsigned blocks = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
   hipLaunchKernelGGL(split_pairs_kernel, dim3(blocks), dim3(256), 0, st, x, static_cast<unsigned short*>(out), rows, K, x_sr);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 }  // namespace oeh

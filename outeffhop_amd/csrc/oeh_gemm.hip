@@ -33,6 +33,7 @@
 #include "../../include/oeh.h"
 #include "oeh_common.h"
 #include "oeh_gemm.h"
+#include "oeh_launch.h"
 
 #include <cstdio>
 #include <type_traits>
@@ -516,7 +517,7 @@ static int launch_gemm_t(const GemmParams& P, hipStream_t st) {
     attr[dev] = true;
   }
   hipLaunchKernelGGL((oeh_gemm_kernel<AM, MI, NJ, LOOP>), dim3(P.MT * P.NT), dim3(256), ldsb, st, P);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 // Tile choice.  128 x 288 (two workgroups per CU, 144 accumulator registers) when the problem fills the chip with such tiles and the

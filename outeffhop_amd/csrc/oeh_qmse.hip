@@ -24,8 +24,8 @@
 //
 // Plain launches in a linear chain: no atomics, no allocation, no host synchronisation; the geometry is a function of (n, K) only and
 // every sum has a fixed order, so results are bitwise reproducible.
-#include "oeh_common.h"
-#include "../../include/oeh.h"
+#include "oeh_stream.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
@@ -42,45 +42,15 @@ struct QmseCand {  // include/oeh.h: one candidate grid, 16 bytes
 };
 static_assert(sizeof(QmseCand) == OEH_QMSE_CAND_BYTES, "candidate record");
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-template <int IN>
-__device__ __forceinline__ void qmse_unpack16(const u4 w, float* out) {
-  if constexpr (IN == IN_F32) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[i] = bits_f32(w[i]);
-  } else if constexpr (IN == IN_BF16) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned u = w[i];
-      out[2 * i] = bits_f32(u << 16);
-      out[2 * i + 1] = bits_f32(u & 0xffff0000u);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned u = w[i];
-      const h2 p = __builtin_bit_cast(h2, u);
-      out[2 * i] = (float)p[0];
-      out[2 * i + 1] = (float)p[1];
-    }
-  }
-}
-
 // One chunk into thread t's registers: slot s of the chunk's 16-byte slots (s * 256 + t) holds the lane's elements [s * V, (s + 1) * V).
 // The whole chunk is covered by the array: 16-byte loads, all in flight before the first is used.
 template <int IN>
 __device__ __forceinline__ void qmse_load_full(const char* __restrict__ p, const int t, float (&xs)[kQmseLane]) {
   constexpr int V = 16 / In<IN>::bytes, S = kQmseLane / V;
   u4 raw[S];
+  load_chunk_full<IN, 256, S>(p, t, raw);
 #pragma unroll
-  for (int s = 0; s < S; ++s) raw[s] = *reinterpret_cast<const u4*>(p + (size_t)((s * 256 + t) * V) * In<IN>::bytes);
-#pragma unroll
-  for (int s = 0; s < S; ++s) qmse_unpack16<IN>(raw[s], &xs[s * V]);
+  for (int s = 0; s < S; ++s) unpack16<IN>(raw[s], &xs[s * V]);
 }
 // The array's first or last chunk, covered in [lo_c, hi_c) only (indices relative to `p`, the chunk's 16-byte aligned base): the same
 // placement by element loads of the covered elements - nothing outside the array is touched.  An element outside is 0 and its bit in
@@ -139,7 +109,7 @@ __device__ __forceinline__ void qmse_candidates(const float (&xs)[kQmseLane], co
     f.rscale = 1.0f / c.scale;   // a true (correctly rounded) division, once per candidate
     f.lo = c.lo;
     f.hi = c.hi;
-    const double s = wave_sum_f64(qmse_lane<FULL, F64>(xs, valid, f));
+    const double s = wave_sum(qmse_lane<FULL, F64>(xs, valid, f));
     if ((t & 63) == 0) acc[t >> 6][k] += s;  // (this wave's own slot: nobody else touches it before the barrier at the end)
   }
 }
@@ -153,9 +123,8 @@ __global__ __launch_bounds__(256, 4) void oeh_qmse_chunk_kernel(const void* __re
 #pragma unroll
   for (int w = 0; w < 4; ++w) acc[w][t] = 0.0;
   __syncthreads();
-  const int mis = (int)(reinterpret_cast<uintptr_t>(x) & 15);
-  const int a = mis / In<IN>::bytes;  // elements between the 16-byte boundary below the array and its first element
-  const char* base = reinterpret_cast<const char*>(x) - mis;
+  int a;
+  const char* base = aligned_base(x, In<IN>::bytes, a);
   const long c0 = (long)blockIdx.x * cpb;
   for (long j = 0; j < cpb; ++j) {
     const long ch = c0 + j;
@@ -187,14 +156,14 @@ __global__ __launch_bounds__(256) void oeh_qmse_merge_kernel(const double* __res
   const int lane = threadIdx.x & 63;
   double s = 0.0;
   for (int b = lane; b < blocks; b += 64) s += work[(size_t)b * ks + k];
-  s = wave_sum_f64(s);
+  s = wave_sum(s);
   if (lane == 0) loss[k] = accumulate ? loss[k] + s : s;
 }
 
 }  // namespace
 
 long qmse_blocks(long n, long* nch_out, long* cpb_out) {
-  const long nch = (n + 7 + kQmseC - 1) / kQmseC;  // (7: the most elements an array can start after a 16-byte boundary)
+  const long nch = chunks_for(n, kQmseC);
   const long cpb = (nch + kQmseMaxBlocks - 1) / kQmseMaxBlocks;
   if (nch_out) *nch_out = nch;
   if (cpb_out) *cpb_out = cpb;
@@ -209,18 +178,14 @@ int launch_quant_mse(const void* x, long n, int in, const float* cand, int K, do
   const bool f64 = K <= OEH_QMSE_F64_K;
   for (int k0 = 0; k0 < K; k0 += kQmseSlice) {
     const int ks = K - k0 < kQmseSlice ? K - k0 : kQmseSlice;
-#define OEH_QMSE_LAUNCH(IN)                                                                                                                  \
-  if (f64) hipLaunchKernelGGL((oeh_qmse_chunk_kernel<IN, true>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, nch, cpb, c + k0, ks, w); \
-  else hipLaunchKernelGGL((oeh_qmse_chunk_kernel<IN, false>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, nch, cpb, c + k0, ks, w)
-    switch (in) {
-      case IN_F16: OEH_QMSE_LAUNCH(IN_F16); break;
-      case IN_BF16: OEH_QMSE_LAUNCH(IN_BF16); break;
-      default: OEH_QMSE_LAUNCH(IN_F32); break;
-    }
-#undef OEH_QMSE_LAUNCH
+    dispatch_in(in, [&](auto t) {
+      constexpr int IN = decltype(t)::value;
+      if (f64) hipLaunchKernelGGL((oeh_qmse_chunk_kernel<IN, true>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, nch, cpb, c + k0, ks, w);
+      else hipLaunchKernelGGL((oeh_qmse_chunk_kernel<IN, false>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, nch, cpb, c + k0, ks, w);
+    });
     hipLaunchKernelGGL(oeh_qmse_merge_kernel, dim3((unsigned)((ks + 3) / 4)), dim3(256), 0, st, w, (int)blocks, ks, loss + k0, accumulate);
   }
-  return hipGetLastError() == hipSuccess ? OEH_OK : OEH_ELAUNCH;
+  return launch_status();
 }
 
 }  // namespace oeh

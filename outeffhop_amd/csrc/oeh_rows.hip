@@ -2,7 +2,8 @@
 // (models/softmax.py:22-64), QuantizedActivation in fixed-range mode (base_quantized_classes.py:182-199),
 // the per-head gate predictors (bert_attention.py:301-327) and min/max range statistics
 // (range_estimators.py:71-72,96-97).  All HBM-bound: 16-B accesses, one pass where the row fits LDS.
-#include "oeh_common.h"
+#include "oeh_stream.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
@@ -25,11 +26,11 @@ __global__ __launch_bounds__(256) void oeh_softmax_rows_kernel(const void* __res
       if (STAGED) rowbuf[j] = v;
       lmax = __builtin_fmaxf(lmax, v);
     }
-    for (int o = 32; o > 0; o >>= 1) lmax = __builtin_fmaxf(lmax, __shfl_xor(lmax, o));
+    for (int o = 32; o > 0; o >>= 1) lmax = __builtin_fmaxf(lmax, __shfl_xor(lmax, o));  // (wave_max moves this kernel's prologue: profiles/stream_helpers.txt)
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = lmax;
     __syncthreads();
-    const float m = __builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3]));
+    const float m = block4_max(red);
     float lsum = 0.0f;
     for (int j = tid; j < cols; j += 256) {
       const float v = STAGED ? rowbuf[j] : In<IN>::to_f32(x[j]);
@@ -37,11 +38,11 @@ __global__ __launch_bounds__(256) void oeh_softmax_rows_kernel(const void* __res
       if (STAGED) rowbuf[j] = e;
       lsum += e;
     }
-    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
+    lsum = wave_sum(lsum);
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = lsum;
     __syncthreads();
-    const float sum = ((red[0] + red[1]) + red[2]) + red[3];
+    const float sum = ((red[0] + red[1]) + red[2]) + red[3];  // (in wave order, not block4's pairs: the sum's order is part of the result)
     float den = sum;
     if (base != 0) den = sum + exp_acc(m * -1.0f);
     for (int j = tid; j < cols; j += 256) {
@@ -57,36 +58,6 @@ __global__ __launch_bounds__(256) void oeh_softmax_rows_kernel(const void* __res
     __syncthreads();
   }
 }
-
-// ---- 16-byte vector access for the streaming kernels: VEC elements per access (4 fp32 / 8 x 16-bit)
-template <int IN>
-struct Vec16 {
-  static constexpr int N = 16 / In<IN>::bytes;
-  static __device__ __forceinline__ void load(const void* p, float* out) {
-    const u4 w = *reinterpret_cast<const u4*>(p);
-    if constexpr (IN == IN_F32) {
-      out[0] = bits_f32(w.x); out[1] = bits_f32(w.y); out[2] = bits_f32(w.z); out[3] = bits_f32(w.w);
-    } else {
-      const unsigned ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        out[2 * i] = In<IN>::to_f32((unsigned short)(ws[i] & 0xffffu));
-        out[2 * i + 1] = In<IN>::to_f32((unsigned short)(ws[i] >> 16));
-      }
-    }
-  }
-  static __device__ __forceinline__ void store(void* p, const float* v) {
-    u4 w;
-    if constexpr (IN == IN_F32) {
-      w = u4{f32_bits(v[0]), f32_bits(v[1]), f32_bits(v[2]), f32_bits(v[3])};
-    } else if constexpr (IN == IN_BF16) {
-      w = u4{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])};
-    } else {
-      w = u4{pack2_f16(v[0], v[1]), pack2_f16(v[2], v[3]), pack2_f16(v[4], v[5]), pack2_f16(v[6], v[7])};
-    }
-    *reinterpret_cast<u4*>(p) = w;
-  }
-};
 
 // softmax rows of up to 64*VEC*CH elements: ONE WAVE per row, the row in registers (16-B loads, lane-strided chunks), wave
 // reductions by shuffles - no LDS, no workgroup barrier; four rows per 256-thread workgroup.  Same per-element arithmetic as
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(256) void oeh_softmax_rows_wave_kernel(const void* 
       for (int i = 0; i < N; ++i) m = __builtin_fmaxf(m, v[c][i]);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) m = __builtin_fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   float sum = 0.0f;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
@@ -124,7 +95,7 @@ __global__ __launch_bounds__(256) void oeh_softmax_rows_wave_kernel(const void* 
       }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  sum = wave_sum(sum);
   float den = sum;
   if (base != 0) den = sum + exp_acc(m * -1.0f);
   const float rden = 1.0f / den;  // RN(1/den): e/den below is the three-instruction correctly rounded quotient (oeh_common.h: fq_quot)
@@ -165,27 +136,18 @@ static bool launch_softmax_rows_wave(const void* x, void* y, long rows, int cols
 
 int launch_softmax_rows(const void* x, void* y, long rows, int cols, int in, int base, int clip, float w, float g, hipStream_t st) {
   {  // rows that fit a wave's registers (<= 2048 fp32 / 4096 16-bit elements, multiple of the 16-B vector)
-    bool done;
-    switch (in) {
-      case IN_F16: done = launch_softmax_rows_wave<IN_F16>(x, y, rows, cols, base, clip, w, g, st); break;
-      case IN_BF16: done = launch_softmax_rows_wave<IN_BF16>(x, y, rows, cols, base, clip, w, g, st); break;
-      default: done = launch_softmax_rows_wave<IN_F32>(x, y, rows, cols, base, clip, w, g, st); break;
-    }
-    if (done) return hipGetLastError() == hipSuccess ? 0 : -5;
+    const bool done = dispatch_in(in, [&](auto t) { return launch_softmax_rows_wave<decltype(t)::value>(x, y, rows, cols, base, clip, w, g, st); });
+    if (done) return launch_status();
   }
   const bool staged = cols <= 15872;
   const size_t shmem = staged ? (size_t)cols * 4 : 0;
   const unsigned grid = (unsigned)(rows < 65536 ? rows : 65536);
-#define OEH_SMX(INV)                                                                                                   \
-  if (staged) hipLaunchKernelGGL((oeh_softmax_rows_kernel<INV, true>), dim3(grid), dim3(256), shmem, st, x, y, rows, cols, base, clip, w, g); \
-  else hipLaunchKernelGGL((oeh_softmax_rows_kernel<INV, false>), dim3(grid), dim3(256), 0, st, x, y, rows, cols, base, clip, w, g);
-  switch (in) {
-    case IN_F16: OEH_SMX(IN_F16) break;
-    case IN_BF16: OEH_SMX(IN_BF16) break;
-    default: OEH_SMX(IN_F32) break;
-  }
-#undef OEH_SMX
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  dispatch_in(in, [&](auto t) {
+    constexpr int IN = decltype(t)::value;
+    if (staged) hipLaunchKernelGGL((oeh_softmax_rows_kernel<IN, true>), dim3(grid), dim3(256), shmem, st, x, y, rows, cols, base, clip, w, g);
+    else hipLaunchKernelGGL((oeh_softmax_rows_kernel<IN, false>), dim3(grid), dim3(256), 0, st, x, y, rows, cols, base, clip, w, g);
+  });
+  return launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -246,22 +208,14 @@ int launch_fake_quant(const void* x, void* y, unsigned char* idx, long n, int in
     long blocks = (nvec + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
-    switch (in) {
-      case IN_F16: hipLaunchKernelGGL(oeh_fake_quant_vec_kernel<IN_F16>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); break;
-      case IN_BF16: hipLaunchKernelGGL(oeh_fake_quant_vec_kernel<IN_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); break;
-      default: hipLaunchKernelGGL(oeh_fake_quant_vec_kernel<IN_F32>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(oeh_fake_quant_vec_kernel<decltype(t)::value>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); });
+    return launch_status();
   }
   long blocks = (n + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
   if (blocks < 1) blocks = 1;
-  switch (in) {
-    case IN_F16: hipLaunchKernelGGL(oeh_fake_quant_kernel<IN_F16>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); break;
-    case IN_BF16: hipLaunchKernelGGL(oeh_fake_quant_kernel<IN_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); break;
-    default: hipLaunchKernelGGL(oeh_fake_quant_kernel<IN_F32>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(oeh_fake_quant_kernel<decltype(t)::value>, dim3((unsigned)blocks), dim3(256), 0, st, x, y, idx, n, f); });
+  return launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -304,7 +258,7 @@ __global__ __launch_bounds__(64) void oeh_gate_pool_kernel(float* io, int T, flo
   float* row = io + (long)blockIdx.x * T;
   float s = 0.0f;
   for (int t = threadIdx.x; t < T; t += 64) s += row[t];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (threadIdx.x == 0) {
     const float a = s / (float)T;
     row[0] = (1.0f / (1.0f + exp_acc(-a))) * scaling;
@@ -345,13 +299,7 @@ __global__ __launch_bounds__(64 * NW) void oeh_gate_logit_fast_kernel(const void
   } else {
 #pragma unroll
     for (int k = 0; k < D; k += 8) {
-      const u4 v = *reinterpret_cast<const u4*>(xp + k);
-      const unsigned int wds[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        x[k + 2 * q] = In<IN>::to_f32((unsigned short)(wds[q] & 0xffffu));
-        x[k + 2 * q + 1] = In<IN>::to_f32((unsigned short)(wds[q] >> 16));
-      }
+      unpack16<IN>(*reinterpret_cast<const u4*>(xp + k), &x[k]);
     }
   }
   const float* wh = w1 + (long)h * mm * D;  // wave-uniform addresses from here on: scalar loads
@@ -546,24 +494,17 @@ element_kernel:
 
 int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_b, long hs_t, const float* w1, const float* b1,
                 const float* w2, const float* b2, int m_units, int pool, float scaling, float* out, hipStream_t st) {
-  bool done = false;
-  switch (in) {
-    case IN_F16: done = launch_gate_fast<IN_F16>(hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out, st); break;
-    case IN_BF16: done = launch_gate_fast<IN_BF16>(hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out, st); break;
-    default: done = launch_gate_fast<IN_F32>(hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out, st); break;
-  }
+  const bool done = dispatch_in(in, [&](auto t) {
+    return launch_gate_fast<decltype(t)::value>(hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out, st);
+  });
   if (!done) {  // any head dim / alignment: one thread per (b,t,h), element loads
     const long n = (long)B * T * H;
     long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    switch (in) {
-      case IN_F16: hipLaunchKernelGGL(oeh_gate_logit_kernel<IN_F16>, dim3((unsigned)blocks), dim3(256), 0, st, hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out); break;
-      case IN_BF16: hipLaunchKernelGGL(oeh_gate_logit_kernel<IN_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out); break;
-      default: hipLaunchKernelGGL(oeh_gate_logit_kernel<IN_F32>, dim3((unsigned)blocks), dim3(256), 0, st, hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out); break;
-    }
+    dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(oeh_gate_logit_kernel<decltype(t)::value>, dim3((unsigned)blocks), dim3(256), 0, st, hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out); });
   }
   if (pool) hipLaunchKernelGGL(oeh_gate_pool_kernel, dim3((unsigned)(B * H)), dim3(64), 0, st, out, T, scaling);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 
@@ -588,7 +529,7 @@ __global__ __launch_bounds__(256) void oeh_minmax_kernel(const void* __restrict_
     lo = __builtin_fminf(lo, v);
     hi = __builtin_fmaxf(hi, v);
   }
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // (two butterflies interleaved; one after the other is a different stream: profiles/stream_helpers.txt)
     lo = __builtin_fminf(lo, __shfl_xor(lo, o));
     hi = __builtin_fmaxf(hi, __shfl_xor(hi, o));
   }
@@ -636,15 +577,15 @@ __global__ __launch_bounds__(256) void oeh_minmax_vec_kernel(const void* __restr
       hi = __builtin_fmaxf(hi, v);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // (two butterflies interleaved; one after the other is a different stream: profiles/stream_helpers.txt)
     lo = __builtin_fminf(lo, __shfl_xor(lo, o));
     hi = __builtin_fmaxf(hi, __shfl_xor(hi, o));
   }
   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = lo; red[4 + (threadIdx.x >> 6)] = hi; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicMin(&keys[0], f2key(__builtin_fminf(__builtin_fminf(red[0], red[1]), __builtin_fminf(red[2], red[3]))));
-    atomicMax(&keys[1], f2key(__builtin_fmaxf(__builtin_fmaxf(red[4], red[5]), __builtin_fmaxf(red[6], red[7]))));
+    atomicMin(&keys[0], f2key(block4_min(red)));
+    atomicMax(&keys[1], f2key(block4_max(red + 4)));
   }
 }
 
@@ -656,24 +597,16 @@ int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st) {
     long vb = (nvec + 1023) / 1024;  // four vectors per thread
     if (vb > 2048) vb = 2048;
     if (vb < 1) vb = 1;
-    switch (in) {
-      case IN_F16: hipLaunchKernelGGL(oeh_minmax_vec_kernel<IN_F16>, dim3((unsigned)vb), dim3(256), 0, st, x, n, keys); break;
-      case IN_BF16: hipLaunchKernelGGL(oeh_minmax_vec_kernel<IN_BF16>, dim3((unsigned)vb), dim3(256), 0, st, x, n, keys); break;
-      default: hipLaunchKernelGGL(oeh_minmax_vec_kernel<IN_F32>, dim3((unsigned)vb), dim3(256), 0, st, x, n, keys); break;
-    }
+    dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(oeh_minmax_vec_kernel<decltype(t)::value>, dim3((unsigned)vb), dim3(256), 0, st, x, n, keys); });
     hipLaunchKernelGGL(oeh_minmax_fin_kernel, dim3(1), dim3(1), 0, st, keys);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_status();
   }
   long blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  switch (in) {
-    case IN_F16: hipLaunchKernelGGL(oeh_minmax_kernel<IN_F16>, dim3((unsigned)blocks), dim3(256), 0, st, x, n, keys); break;
-    case IN_BF16: hipLaunchKernelGGL(oeh_minmax_kernel<IN_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, x, n, keys); break;
-    default: hipLaunchKernelGGL(oeh_minmax_kernel<IN_F32>, dim3((unsigned)blocks), dim3(256), 0, st, x, n, keys); break;
-  }
+  dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(oeh_minmax_kernel<decltype(t)::value>, dim3((unsigned)blocks), dim3(256), 0, st, x, n, keys); });
   hipLaunchKernelGGL(oeh_minmax_fin_kernel, dim3(1), dim3(1), 0, st, keys);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return launch_status();
 }
 
 }  // namespace oeh

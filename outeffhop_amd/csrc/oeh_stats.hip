@@ -21,8 +21,8 @@
 // buffer; longer rows take one workgroup per (row, chunk), which writes a 48-byte record to `work`, and a second small launch with one
 // wave per row that merges the records and writes `stats`.  The optional running meter is added by a one-wave launch at the end of the
 // same chain, rows in ascending order in float64.  Plain launches on one stream: no atomics, no allocation, no host synchronisation.
-#include "oeh_common.h"
-#include "../../include/oeh.h"
+#include "oeh_stream.h"
+#include "oeh_launch.h"
 
 namespace oeh {
 
@@ -40,45 +40,6 @@ struct StatsRec {  // one chunk, or a merged run of chunks (48 bytes in `work`)
 };
 static_assert(sizeof(StatsRec) == OEH_STATS_RECORD_BYTES, "work buffer record");
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, m));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_umin(unsigned v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, m));
-  return v;
-}
-
-template <int IN>
-__device__ __forceinline__ void unpack16(const u4 w, float* out) {
-  if constexpr (IN == IN_F32) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[i] = bits_f32(w[i]);
-  } else if constexpr (IN == IN_BF16) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned u = w[i];
-      out[2 * i] = bits_f32(u << 16);
-      out[2 * i + 1] = bits_f32(u & 0xffff0000u);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned u = w[i];
-      const h2 p = __builtin_bit_cast(h2, u);
-      out[2 * i] = (float)p[0];
-      out[2 * i + 1] = (float)p[1];
-    }
-  }
-}
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // The statistics of the elements [lo_c, hi_c) of one chunk (element indices relative to `p`, the chunk's 16-byte aligned base) by a
@@ -91,11 +52,15 @@ __device__ __forceinline__ StatsRec chunk_pass(const char* __restrict__ p, const
   float xs[K][V];
   u4 raw[K];
   // every 16-byte load of the chunk is issued before the first value is used
+  if constexpr (FULL) {
+    load_chunk_full<IN, T, K>(p, t, raw);
+  } else {
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int o = (k * T + t) * V;
-    raw[k] = u4{0u, 0u, 0u, 0u};
-    if (FULL || (o >= lo_c && o + V <= hi_c)) raw[k] = *reinterpret_cast<const u4*>(p + (size_t)o * In<IN>::bytes);
+    for (int k = 0; k < K; ++k) {
+      const int o = (k * T + t) * V;
+      raw[k] = u4{0u, 0u, 0u, 0u};
+      if (o >= lo_c && o + V <= hi_c) raw[k] = *reinterpret_cast<const u4*>(p + (size_t)o * In<IN>::bytes);
+    }
   }
   float s = 0.0f;
   unsigned amax = 0u, maxb = 0u, minb = 0xffffffffu;
@@ -137,9 +102,9 @@ __device__ __forceinline__ StatsRec chunk_pass(const char* __restrict__ p, const
     }
   }
   s = wave_sum(s);
-  amax = wave_umax(amax);
-  maxb = wave_umax(maxb);
-  minb = wave_umin(minb);
+  amax = wave_max(amax);
+  maxb = wave_max(maxb);
+  minb = wave_min(minb);
   if constexpr (WAVES > 1) {
     static_assert(WAVES == 4, "the fixed order below is written for four waves");
     if ((t & 63) == 0) {
@@ -149,10 +114,11 @@ __device__ __forceinline__ StatsRec chunk_pass(const char* __restrict__ p, const
       lds[3][t >> 6] = minb;
     }
     __syncthreads();
+    // (the float sums in block4's order, written out: behind a helper the compiler pairs them differently - profiles/stream_helpers.txt)
     s = (bits_f32(lds[0][0]) + bits_f32(lds[0][1])) + (bits_f32(lds[0][2]) + bits_f32(lds[0][3]));
-    amax = max(max(lds[1][0], lds[1][1]), max(lds[1][2], lds[1][3]));
-    maxb = max(max(lds[2][0], lds[2][1]), max(lds[2][2], lds[2][3]));
-    minb = min(min(lds[3][0], lds[3][1]), min(lds[3][2], lds[3][3]));
+    amax = block4_max(lds[1]);
+    maxb = block4_max(lds[2]);
+    minb = block4_min(lds[3]);
   }
   const int n = hi_c - lo_c;
   // the centre: any value near the mean serves (its distance from the mean is taken out below); a constant chunk is centred on its value
@@ -243,20 +209,13 @@ __device__ __forceinline__ void stats_store(const StatsRec& r, const double eps,
   *reinterpret_cast<f4*>(out) = o;
 }
 
-__device__ __forceinline__ const char* row_base(const void* x, const long row, const long row_stride_bytes, const int elem_bytes, int& a) {
-  const char* addr = reinterpret_cast<const char*>(x) + row * row_stride_bytes;
-  const int mis = (int)(reinterpret_cast<uintptr_t>(addr) & 15);
-  a = mis / elem_bytes;  // elements between the 16-byte boundary below the row and its first element
-  return addr - mis;
-}
-
 template <int IN>
 __global__ __launch_bounds__(256) void oeh_stats_wave_kernel(const void* __restrict__ x, const long rows, const int cols, const long row_stride_bytes,
                                                              const double eps, float* __restrict__ stats) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;  // (whole waves; this form has no barrier)
   int a;
-  const char* p = row_base(x, row, row_stride_bytes, In<IN>::bytes, a);
+  const char* p = aligned_base(reinterpret_cast<const char*>(x) + row * row_stride_bytes, In<IN>::bytes, a);
   const StatsRec r = chunk_pass<IN, 1, false>(p, a, a + cols, threadIdx.x & 63, nullptr);
   if ((threadIdx.x & 63) == 0) stats_store(r, eps, stats + row * 4);
 }
@@ -267,7 +226,7 @@ __global__ __launch_bounds__(256) void oeh_stats_chunk_kernel(const void* __rest
   __shared__ unsigned lds[8][4];
   const unsigned row = blockIdx.x / (unsigned)nch, ch = blockIdx.x - row * (unsigned)nch;
   int a;
-  const char* p = row_base(x, (long)row, row_stride_bytes, In<IN>::bytes, a);
+  const char* p = aligned_base(reinterpret_cast<const char*>(x) + (long)row * row_stride_bytes, In<IN>::bytes, a);
   const long cbase = (long)ch * kStatsC;
   const long lo_l = (long)a - cbase, hi_l = (long)a + cols - cbase;
   const int lo_c = (int)(lo_l < 0 ? 0 : (lo_l > kStatsC ? kStatsC : lo_l)), hi_c = (int)(hi_l < 0 ? 0 : (hi_l > kStatsC ? kStatsC : hi_l));
@@ -343,7 +302,7 @@ __global__ __launch_bounds__(64) void oeh_stats_meter_kernel(const float* __rest
 
 }  // namespace
 
-long stats_chunks(long cols) { return cols <= kStatsW ? 0 : (cols + 7 + kStatsC - 1) / kStatsC; }
+long stats_chunks(long cols) { return cols <= kStatsW ? 0 : chunks_for(cols, kStatsC); }
 
 int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,
                          hipStream_t st) {
@@ -352,23 +311,21 @@ int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, i
   const long blocks4 = (rows + 3) / 4;
   if (blocks4 >= ((long)1 << 31) || rows * (nch > 0 ? nch : 1) >= ((long)1 << 31)) return OEH_ENOTSUP;
   if (nch == 0) {
-    switch (in) {
-      case IN_F16: hipLaunchKernelGGL(oeh_stats_wave_kernel<IN_F16>, dim3((unsigned)blocks4), dim3(256), 0, st, x, rows, (int)cols, row_stride * eb, eps, stats); break;
-      case IN_BF16: hipLaunchKernelGGL(oeh_stats_wave_kernel<IN_BF16>, dim3((unsigned)blocks4), dim3(256), 0, st, x, rows, (int)cols, row_stride * eb, eps, stats); break;
-      default: hipLaunchKernelGGL(oeh_stats_wave_kernel<IN_F32>, dim3((unsigned)blocks4), dim3(256), 0, st, x, rows, (int)cols, row_stride * eb, eps, stats); break;
-    }
+    dispatch_in(in, [&](auto t) {
+      constexpr int IN = decltype(t)::value;
+      hipLaunchKernelGGL(oeh_stats_wave_kernel<IN>, dim3((unsigned)blocks4), dim3(256), 0, st, x, rows, (int)cols, row_stride * eb, eps, stats);
+    });
   } else {
     StatsRec* w = reinterpret_cast<StatsRec*>(work);
     const unsigned grid = (unsigned)(rows * nch);
-    switch (in) {
-      case IN_F16: hipLaunchKernelGGL(oeh_stats_chunk_kernel<IN_F16>, dim3(grid), dim3(256), 0, st, x, cols, row_stride * eb, (int)nch, w); break;
-      case IN_BF16: hipLaunchKernelGGL(oeh_stats_chunk_kernel<IN_BF16>, dim3(grid), dim3(256), 0, st, x, cols, row_stride * eb, (int)nch, w); break;
-      default: hipLaunchKernelGGL(oeh_stats_chunk_kernel<IN_F32>, dim3(grid), dim3(256), 0, st, x, cols, row_stride * eb, (int)nch, w); break;
-    }
+    dispatch_in(in, [&](auto t) {
+      constexpr int IN = decltype(t)::value;
+      hipLaunchKernelGGL(oeh_stats_chunk_kernel<IN>, dim3(grid), dim3(256), 0, st, x, cols, row_stride * eb, (int)nch, w);
+    });
     hipLaunchKernelGGL(oeh_stats_merge_kernel, dim3((unsigned)blocks4), dim3(256), 0, st, w, rows, (int)nch, eps, stats);
   }
   if (accumulate != 0) hipLaunchKernelGGL(oeh_stats_meter_kernel, dim3(1), dim3(64), 0, st, stats, rows, meter, accumulate);
-  return hipGetLastError() == hipSuccess ? OEH_OK : OEH_ELAUNCH;
+  return launch_status();
 }
 
 }  // namespace oeh

@@ -2,6 +2,7 @@
 // variant selection and launch.  No allocation, no synchronisation: safe under hipGraph capture.
 #include "../../include/oeh.h"
 #include "../../include/oeh_debug.h"
+#include "oeh_desc.h"
 #include "oeh_gemm.h"
 #include "oeh_launch.h"
 
@@ -12,10 +13,11 @@
 
 using oeh::AttnParams;
 using oeh::FqP;
+// the descriptor predicates and the descriptor -> kernel block fill (oeh_desc.h)
+using oeh::addr; using oeh::aligned16; using oeh::all16; using oeh::any_fq; using oeh::desc_sane; using oeh::dtype_ok; using oeh::softmax_base_ok;
 
 namespace {
 
-bool dtype_ok(int d) { return d == OEH_F16 || d == OEH_BF16 || d == OEH_F32; }
 int elem_bytes(int d) { return d == OEH_F32 ? 4 : d == OEH_I8 ? 1 : 2; }
 
 using oeh::make_fq;  // (oeh_attn_params.h)
@@ -42,21 +44,6 @@ struct Hooks {
   long hot_launches;            // one-pass launches that took the hot argument prefix (oeh_debug_hot_launches)
 } g_hooks = {};
 
-// rows must be 16-byte aligned for the MFMA path's 16-B loads / 8..16-B stores
-bool aligned16(const void* p, const int64_t* st, int eb) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
-  for (int i = 0; i < 3; ++i)
-    if (((st[i] * eb) & 15) != 0) return false;
-  return true;
-}
-
-// The descriptor sanity every entry point starts with: positive sizes (the head dim where the caller does not judge it itself) and a
-// storage type (INT8 where the caller takes it)
-bool desc_sane(const oeh_attn_desc* d, bool with_D, bool with_i8) {
-  if (d == nullptr || d->B <= 0 || d->H <= 0 || d->Sq <= 0 || d->Sk <= 0 || (with_D && d->D <= 0)) return false;
-  return dtype_ok(d->dtype) || (with_i8 && d->dtype == OEH_I8);
-}
-
 int validate(const oeh_attn_desc* d, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq) {
   if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || !desc_sane(d, true, true)) return OEH_EINVAL;
   if (d->dtype == OEH_I8) {
@@ -69,20 +56,13 @@ int validate(const oeh_attn_desc* d, const void* q, const void* k, const void* v
     for (int i = 0; i < 3; ++i)
       if (!(ss[i] > 0.0f) || !(zs[i] >= 0.0f && zs[i] <= 255.0f) || zs[i] != std::nearbyint(zs[i])) return OEH_EINVAL;
   }
-  if (d->softmax_base != OEH_SOFTMAX_VANILLA && d->softmax_base != OEH_SOFTMAX_ONE) return OEH_EINVAL;
-  {  // strides are element counts in [0, 2^32): the kernels form batch / head offsets from 32-bit products (views with negative
-     // strides are not a layout any caller of the reference produces)
-    const int64_t* sts[4] = {d->q_stride, d->k_stride, d->v_stride, d->o_stride};
-    for (const int64_t* st : sts)
-      for (int i = 0; i < 3; ++i)
-        if (st[i] < 0 || st[i] >= ((int64_t)1 << 32)) return OEH_ENOTSUP;
-  }
+  if (!softmax_base_ok(d->softmax_base)) return OEH_EINVAL;
+  if (!oeh::desc_strides_in_range(d)) return OEH_ENOTSUP;
   if (fq != nullptr && fq->ctx_emit_index) {  // the integers idx - zp instead of values: only where the context quantiser is the last op
     const bool gated = d->gate != nullptr || d->gate_hidden != nullptr;
     if (!fq->ctx.enable || (gated && fq->ctx_quant_before_gate)) return OEH_EINVAL;
   }
-  if (d->key_pad_mask != nullptr && d->key_pad_dtype != OEH_F16 && d->key_pad_dtype != OEH_F32) return OEH_EINVAL;
-  if (d->full_mask != nullptr && d->full_mask_dtype != OEH_F16 && d->full_mask_dtype != OEH_F32) return OEH_EINVAL;
+  if (!oeh::key_pad_ok(d) || !oeh::full_mask_ok(d)) return OEH_EINVAL;
   if (d->gate == nullptr && d->gate_hidden != nullptr) {
     if (d->gate_w1 == nullptr || d->gate_b1 == nullptr || d->gate_units < 0) return OEH_EINVAL;
     if (d->gate_units > 0 && (d->gate_w2 == nullptr || d->gate_b2 == nullptr)) return OEH_EINVAL;
@@ -91,14 +71,12 @@ int validate(const oeh_attn_desc* d, const void* q, const void* k, const void* v
     const oeh_fq* fs[3] = {&fq->scores, &fq->probs, &fq->ctx};
     for (const oeh_fq* f : fs) {
       if (!f->enable) continue;
-      if (!(f->scale > 0.0f) || !(f->qmax >= 1.0f) || f->zero_point < 0.0f || f->zero_point > f->qmax) return OEH_EINVAL;
-      if (f->dump_idx != nullptr && f->qmax > 255.0f) return OEH_ENOTSUP;
+      if (!oeh::fq_grid_ok(*f, false)) return OEH_EINVAL;
+      if (!oeh::fq_dump_fits(*f)) return OEH_ENOTSUP;
     }
   }
   return OEH_OK;
 }
-
-bool any_fq(const oeh_fq_desc* fq) { return fq != nullptr && (fq->scores.enable || fq->probs.enable || fq->ctx.enable); }
 
 // the per-token gate predictor evaluated in the kernel (gate values given: they win)
 bool gate_in_kernel(const oeh_attn_desc* d) { return d->gate == nullptr && d->gate_hidden != nullptr; }
@@ -297,23 +275,11 @@ Variant pick_variant(const oeh_attn_desc* d, const void* q, const void* k, const
 
 void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const void* k, const void* v, void* o, const oeh_fq_desc* fq) {
   std::memset(&P, 0, sizeof(P));
+  oeh::fill_problem(P, d);
   P.q = q; P.k = k; P.v = v; P.o = o;
-  P.B = d->B; P.H = d->H; P.Sq = d->Sq; P.Sk = d->Sk; P.D = d->D;
-  P.qs_b = d->q_stride[0]; P.qs_h = d->q_stride[1]; P.qs_s = d->q_stride[2];
-  P.ks_b = d->k_stride[0]; P.ks_h = d->k_stride[1]; P.ks_s = d->k_stride[2];
-  P.vs_b = d->v_stride[0]; P.vs_h = d->v_stride[1]; P.vs_s = d->v_stride[2];
-  P.os_b = d->o_stride[0]; P.os_h = d->o_stride[1]; P.os_s = d->o_stride[2];
-  P.scale = d->scale; P.scale_div = d->scale_div;
-  P.base = d->softmax_base;
-  P.clip = d->clip ? 1 : 0;
-  // (eta - gamma) is formed in double and rounded to fp32 once, as Python does before the tensor multiply
-  P.clip_w = (float)((double)d->eta - (double)d->gamma);
-  P.clip_g = d->gamma;
-  P.pad = d->key_pad_mask; P.pad_f16 = d->key_pad_dtype == OEH_F16; P.pad_sb = d->key_pad_stride;
+  P.D = d->D;
+  P.scale = d->scale; P.scale_div = d->scale_div;  // (both: oeh_attn_fwd_ex folds the divisor for the one-pass and full-row kernels only)
   P.pad_bool = (d->key_pad_mask != nullptr && d->key_pad_boolean && d->mask_min < -1.0e4f) ? 1 : 0;
-  P.full = d->full_mask; P.full_f16 = d->full_mask_dtype == OEH_F16;
-  P.full_sb = d->full_mask_stride[0]; P.full_sq = d->full_mask_stride[1];
-  P.causal = d->causal ? 1 : 0; P.clamp_min = d->clamp_min ? 1 : 0; P.mask_min = d->mask_min;
   P.gate = d->gate; P.gs_b = d->gate_stride[0]; P.gs_h = d->gate_stride[1]; P.gs_s = d->gate_stride[2];
   if (gate_in_kernel(d)) {
     P.gh = d->gate_hidden; P.ghs_b = d->gate_hidden_stride[0]; P.ghs_t = d->gate_hidden_stride[1];
@@ -333,14 +299,7 @@ void fill_params(AttnParams& P, const oeh_attn_desc* d, const void* q, const voi
   P.nBHpad = (P.nBH + 7) & ~7;
   P.magic_nbh = (unsigned)(0x100000000ULL / (unsigned long long)P.nBHpad > 0xffffffffULL ? 0xffffffffULL : 0x100000000ULL / (unsigned long long)P.nBHpad);
   P.magic_h = (unsigned)(0x100000000ULL / (unsigned long long)P.H > 0xffffffffULL ? 0xffffffffULL : 0x100000000ULL / (unsigned long long)P.H);
-  // Causal tiles strictly above the diagonal contribute exactly 0 to P@V (and nothing to the row statistics)
-  // and may be skipped when: masked probabilities are exactly 0 before the clip and the clip maps 0 to 0
-  // (gamma <= 0); the row can never be fully masked under vanilla softmax (which would make it uniform over
-  // ALL keys) - guaranteed by the diagonal unless another mask is present; and no index dump wants every element.
-  const bool dump = (P.fq_s.dump != nullptr) || (P.fq_p.dump != nullptr);
-  const bool other_mask = (P.pad != nullptr) || (P.full != nullptr);
-  P.skip_ok = (P.causal && d->Sq <= d->Sk && (!P.clip || d->gamma <= 0.0f) && !dump && (P.base == 1 || !other_mask) &&
-               std::isfinite(d->mask_min) && d->mask_min < -1e4f) ? 1 : 0;
+  P.skip_ok = oeh::causal_skip_ok(d, P.fq_s.dump != nullptr || P.fq_p.dump != nullptr) ? 1 : 0;
 }
 
 // The hot argument prefix of the one-pass kernel (oeh_attn_params.h: AttnHot; P as the V_FLASH case has completed it).  True = the launch may
@@ -351,7 +310,7 @@ bool fill_hot(oeh::AttnHot& hot, const AttnParams& P) {
   if (g_hooks.off & HOOK_NO_HOT_ARGS) return false;
   if (P.pad != nullptr || P.full != nullptr || P.gh != nullptr || P.clip || P.fq_s.en || P.src32 || P.out32) return false;
   if (P.qs_b != P.ks_b || P.qs_b != P.vs_b || P.qs_h != P.ks_h || P.qs_h != P.vs_h || P.qs_s != P.ks_s || P.qs_s != P.vs_s) return false;
-  // (strides: validate() keeps them in [0, 2^32))
+  // (strides: in [0, 2^32), oeh_desc.h: strides_in_range)
   if (P.H > oeh::kHotMaxH || P.nQT > oeh::kHotMaxNQT || P.Sq > oeh::kHotMaxS || P.Sk > oeh::kHotMaxS || P.nBHpad != ((P.nBH + 7) & ~7)) return false;
   hot.q = P.q; hot.k = P.k; hot.v = P.v;
   hot.nBH = P.nBH; hot.magic_nbh = P.magic_nbh; hot.magic_h = P.magic_h;
@@ -401,7 +360,7 @@ AttnPlan plan_attn(const oeh_attn_desc* d, const oeh_attn_opts* opts, const void
     // up to four 16-unit MFMA tiles of hidden units; fp32 storage: the full-row kernel's operand-pair form only
     if (!matrix16 || d->gate_units > 64 || (d->dtype == OEH_F32 && pl.var != V_FAST)) { pl.rc = OEH_ENOTSUP; return pl; }
     const int geb = d->dtype == OEH_F32 ? 4 : 2;
-    if (((reinterpret_cast<uintptr_t>(d->gate_hidden) | (uintptr_t)(d->gate_hidden_stride[0] * geb) | (uintptr_t)(d->gate_hidden_stride[1] * geb)) & 15) != 0) { pl.rc = OEH_EALIGN; return pl; }
+    if (!all16(addr(d->gate_hidden) | (uintptr_t)(d->gate_hidden_stride[0] * geb) | (uintptr_t)(d->gate_hidden_stride[1] * geb))) { pl.rc = OEH_EALIGN; return pl; }
     if (d->gate_hidden_stride[1] <= 0 || d->gate_hidden_stride[1] >= (1 << 24)) { pl.rc = OEH_ENOTSUP; return pl; }  // (32-bit lane offsets of the input rows' LDS-DMA)
   }
   // 6. fp32 output
@@ -505,7 +464,7 @@ int oeh_softmax_rows(const void* x, void* y, int64_t rows, int32_t cols, int32_t
 int oeh_fake_quant(const void* x, void* y, uint8_t* idx, int64_t n, int32_t dtype, float scale, float zero_point, float qmax,
                    void* stream) {
   if (x == nullptr || n < 0 || !dtype_ok(dtype)) return OEH_EINVAL;
-  if (!(scale > 0.0f) || !(qmax >= 1.0f) || zero_point < 0.0f || zero_point > qmax) return OEH_EINVAL;
+  if (!oeh::fq_grid_ok(scale, zero_point, qmax, false)) return OEH_EINVAL;
   if (idx != nullptr && qmax > 255.0f) return OEH_ENOTSUP;
   if (n == 0 || (y == nullptr && idx == nullptr)) return OEH_OK;
   const oeh_fq f = {1, scale, zero_point, qmax, nullptr};
@@ -579,9 +538,7 @@ int oeh_attn_calibrate(const oeh_attn_desc* desc, const void* q, const void* k, 
   if (q == nullptr || k == nullptr || !desc_sane(desc, false, false)) return OEH_EINVAL;
   if (which < OEH_CALIB_SCORES || which > OEH_CALIB_CONTEXT || n_bits < 1 || n_bits > 16 || !(eps > 0.0)) return OEH_EINVAL;
   if (which == OEH_CALIB_CONTEXT ? (v == nullptr || ctx_out == nullptr) : (state == nullptr || work == nullptr)) return OEH_EINVAL;
-  if (desc->softmax_base != OEH_SOFTMAX_VANILLA && desc->softmax_base != OEH_SOFTMAX_ONE) return OEH_EINVAL;
-  if (desc->key_pad_mask != nullptr && desc->key_pad_dtype != OEH_F16 && desc->key_pad_dtype != OEH_F32) return OEH_EINVAL;
-  if (desc->full_mask != nullptr && desc->full_mask_dtype != OEH_F16 && desc->full_mask_dtype != OEH_F32) return OEH_EINVAL;
+  if (!softmax_base_ok(desc->softmax_base) || !oeh::key_pad_ok(desc) || !oeh::full_mask_ok(desc)) return OEH_EINVAL;
   if (!(desc->D == 32 || desc->D == 64 || desc->D == 128)) return OEH_ENOTSUP;
   if (which != OEH_CALIB_CONTEXT) {
     if (!(q_lo >= 0.0 && q_lo <= 100.0 && q_hi >= 0.0 && q_hi <= 100.0) || !(momentum >= 0.0 && momentum <= 1.0)) return OEH_EINVAL;
@@ -608,9 +565,9 @@ int oeh_quantize_heads_i8(const void* x, int8_t* out, void* y, int64_t B, int32_
   if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return OEH_EALIGN;
   {  // 16-byte vector loads of the input rows and of the bias
     const int eb = elem_bytes(dtype);
-    if (((reinterpret_cast<uintptr_t>(x) | (uintptr_t)(x_stride[0] * eb) | (uintptr_t)(x_stride[1] * eb) | reinterpret_cast<uintptr_t>(bias)) & 15) != 0) return OEH_EALIGN;
+    if (!all16(addr(x) | (uintptr_t)(x_stride[0] * eb) | (uintptr_t)(x_stride[1] * eb) | addr(bias))) return OEH_EALIGN;
   }
-  if (y != nullptr && ((reinterpret_cast<uintptr_t>(y) | (uintptr_t)(y_stride[0] * elem_bytes(dtype)) | (uintptr_t)(y_stride[1] * elem_bytes(dtype))) & 15) != 0) return OEH_EALIGN;  // 16-byte value stores
+  if (y != nullptr && !all16(addr(y) | (uintptr_t)(y_stride[0] * elem_bytes(dtype)) | (uintptr_t)(y_stride[1] * elem_bytes(dtype)))) return OEH_EALIGN;  // 16-byte value stores
   const oeh_fq f = {1, scale, zero_point, 255.0f, nullptr};
   return oeh::launch_quantize_heads_i8(x, reinterpret_cast<signed char*>(out), y, B, S, H, x_stride[0], x_stride[1], y != nullptr ? y_stride[0] : 0,
                                        y != nullptr ? y_stride[1] : 0, dtype, make_fq(&f), transpose ? 1 : 0, alpha, bias, reinterpret_cast<hipStream_t>(stream));

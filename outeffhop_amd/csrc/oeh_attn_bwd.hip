@@ -17,11 +17,12 @@
 //   dq    per (b, h, 64 queries): delta (rowsum(dO o O), or the clip's key sweep) -> work, then dQ^T += K^T dX^T over the key tiles
 //   dkdv  per (b, h, 64 keys):    S = Q K^T and dY = dO V^T per query tile, dV^T += dO^T y, dK^T += Q^T dX
 // Every gradient element is summed by ONE wave in a fixed order: no atomics, bitwise-reproducible.  Causal problems skip the
-// tiles that are fully hidden when that cannot change the result (the forward's skip rule, oeh_api.hip), and the block order puts
+// tiles that are fully hidden when that cannot change the result (the forward's skip rule, oeh_desc.h: causal_skip_ok), and the block order puts
 // the heaviest tiles first.  In the C/D layout of a 16x16 MFMA lane l holds column l & 15, rows 4 (l >> 4) + i; a 16x16 tile of
 // probabilities therefore is, for the next product, the lane's own k-slots: slot j of lane group g is row 16 t0 + 4 g + j (j < 4)
 // or 16 t1 + 4 g + j - 4, and the other operand is read from a TRANSPOSED LDS image in that order (two ds_read_b64).
 #include "../../include/oeh.h"
+#include "oeh_desc.h"
 #include "oeh_launch.h"
 #include "oeh_philox.h"
 
@@ -61,26 +62,6 @@ struct Params {
   unsigned drop_k0, drop_k1, drop_thr;  // dropout (the DROP instantiations): Philox key, keep threshold (oeh_philox.h),
   float drop_scale;                     // and 1 / (1 - p)
 };
-
-template <int IN>
-__device__ __forceinline__ f4 mma(u4 a, u4 b, f4 c) {
-  if constexpr (IN == IN_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
-
-template <int IN>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  if constexpr (IN == IN_BF16) return pack2_bf16(a, b);
-  else return pack2_f16(a, b);
-}
-
-// 8 16-bit operands from two rows of four fp32 values
-template <int IN>
-__device__ __forceinline__ u4 pack8(const f4& a, const f4& b) {
-  return u4{pack2<IN>(a[0], a[1]), pack2<IN>(a[2], a[3]), pack2<IN>(b[0], b[1]), pack2<IN>(b[2], b[3])};
-}
 
 __device__ __forceinline__ u4 ldg16(const void* base, long off, bool ok) {
   if (!ok) return u4{0u, 0u, 0u, 0u};
@@ -241,7 +222,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
       for (int t = 0; t < 4; ++t) {
         f4 s = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) s = mma<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
+        for (int kc = 0; kc < 2; ++kc) s = mfma16<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int kl = 16 * t + 4 * g + i;
@@ -299,7 +280,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const Params P) {
         for (int c = 0; c < 2; ++c) {
           const u4 bp = pack8<IN>(p[2 * c], p[2 * c + 1]);
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) acc[dt] = mma<IN>(a_tr(Vt, 16 * dt, 2 * c, 2 * c + 1, lane), bp, acc[dt]);
+          for (int dt = 0; dt < 4; ++dt) acc[dt] = mfma16<IN>(a_tr(Vt, 16 * dt, 2 * c, 2 * c + 1, lane), bp, acc[dt]);
         }
       }
     }
@@ -370,7 +351,7 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
       for (int t = 0; t < 4; ++t) {
         f4 s = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) s = mma<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
+        for (int kc = 0; kc < 2; ++kc) s = mfma16<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int kl = 16 * t + 4 * g + i;
@@ -417,8 +398,8 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
         f4 s = f4{0.f, 0.f, 0.f, 0.f}, dy = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-          s = mma<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
-          dy = mma<IN>(a_rows(Vs, 16 * t, kc, lane), df[kc], dy);
+          s = mfma16<IN>(a_rows(Ks, 16 * t, kc, lane), qf[kc], s);
+          dy = mfma16<IN>(a_rows(Vs, 16 * t, kc, lane), df[kc], dy);
         }
         if constexpr (DROP) dy = dy * drop4(P, bh, qi, kt * T + 16 * t + 4 * g);  // dY = keep / (1 - p) dZ
 #pragma unroll
@@ -441,7 +422,7 @@ __global__ __launch_bounds__(256) void dq_kernel(const Params P) {
         for (int c = 0; c < 2; ++c) {
           const u4 bx = pack8<IN>(dx[2 * c], dx[2 * c + 1]);
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) acc[dt] = mma<IN>(a_tr(Kt, 16 * dt, 2 * c, 2 * c + 1, lane), bx, acc[dt]);
+          for (int dt = 0; dt < 4; ++dt) acc[dt] = mfma16<IN>(a_tr(Kt, 16 * dt, 2 * c, 2 * c + 1, lane), bx, acc[dt]);
         }
       }
     }
@@ -506,8 +487,8 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
       f4 s = f4{0.f, 0.f, 0.f, 0.f}, dy = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc) {
-        s = mma<IN>(a_rows(Qs, 16 * t, kc, lane), kf[kc], s);
-        dy = mma<IN>(a_rows(Ds, 16 * t, kc, lane), vf[kc], dy);
+        s = mfma16<IN>(a_rows(Qs, 16 * t, kc, lane), kf[kc], s);
+        dy = mfma16<IN>(a_rows(Ds, 16 * t, kc, lane), vf[kc], dy);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -534,8 +515,8 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
       const u4 bx = pack8<IN>(dx[2 * c], dx[2 * c + 1]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        dvacc[dt] = mma<IN>(a_tr(Dt, 16 * dt, 2 * c, 2 * c + 1, lane), by, dvacc[dt]);
-        dkacc[dt] = mma<IN>(a_tr(Qt, 16 * dt, 2 * c, 2 * c + 1, lane), bx, dkacc[dt]);
+        dvacc[dt] = mfma16<IN>(a_tr(Dt, 16 * dt, 2 * c, 2 * c + 1, lane), by, dvacc[dt]);
+        dkacc[dt] = mfma16<IN>(a_tr(Qt, 16 * dt, 2 * c, 2 * c + 1, lane), bx, dkacc[dt]);
       }
     }
   }
@@ -552,54 +533,26 @@ __global__ __launch_bounds__(256) void dkdv_kernel(const Params P) {
 }
 
 // ---------------------------------------------------------------- host side
-bool aligned_rows(const void* p, const int64_t st[3]) {
-  return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)(st[0] * 2) | (uintptr_t)(st[1] * 2) | (uintptr_t)(st[2] * 2)) & 15) == 0;
-}
-bool strides_ok(const int64_t st[3]) {
-  for (int i = 0; i < 3; ++i)
-    if (st[i] < 0 || st[i] >= ((int64_t)1 << 32)) return false;
-  return true;
-}
+bool aligned_rows(const void* p, const int64_t st[3]) { return aligned16(p, st, 2); }
 
 // what both entry points accept (include/oeh.h): the pointer checks come after, per entry point
 int check_desc(const oeh_attn_desc* d) {
-  if (d == nullptr) return OEH_EINVAL;
-  if (d->B <= 0 || d->H <= 0 || d->Sq <= 0 || d->Sk <= 0 || d->D <= 0) return OEH_EINVAL;
-  if (d->dtype != OEH_F16 && d->dtype != OEH_BF16 && d->dtype != OEH_F32 && d->dtype != OEH_I8) return OEH_EINVAL;
-  if (d->softmax_base != OEH_SOFTMAX_VANILLA && d->softmax_base != OEH_SOFTMAX_ONE) return OEH_EINVAL;
-  if (d->key_pad_mask != nullptr && d->key_pad_dtype != OEH_F16 && d->key_pad_dtype != OEH_F32) return OEH_EINVAL;
-  if (d->full_mask != nullptr && d->full_mask_dtype != OEH_F16 && d->full_mask_dtype != OEH_F32) return OEH_EINVAL;
+  if (!desc_sane(d, true, true) || !softmax_base_ok(d->softmax_base) || !key_pad_ok(d) || !full_mask_ok(d)) return OEH_EINVAL;
   if (d->dtype == OEH_F32 || d->dtype == OEH_I8) return OEH_ENOTSUP;   // fp16 / bf16 storage only
   if (d->D != 64) return OEH_ENOTSUP;
   if (d->gate != nullptr || d->gate_hidden != nullptr) return OEH_ENOTSUP;  // the gate stays outside the differentiable core
   if (d->o_dtype == OEH_F32) return OEH_ENOTSUP;                       // (the inference kernels' fp32-accumulator output)
   if (d->scale_div != 0.0f ? !(std::isfinite(d->scale_div) && d->scale_div != 0.0f) : !std::isfinite(d->scale)) return OEH_EINVAL;
-  if (!strides_ok(d->q_stride) || !strides_ok(d->k_stride) || !strides_ok(d->v_stride) || !strides_ok(d->o_stride)) return OEH_ENOTSUP;
+  if (!desc_strides_in_range(d)) return OEH_ENOTSUP;
   if ((int64_t)d->B * d->H * (d->Sq > d->Sk ? d->Sq : d->Sk) >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
   return OEH_OK;
 }
 
 void fill(Params& P, const oeh_attn_desc* d) {
   std::memset(&P, 0, sizeof(P));
-  P.B = d->B; P.H = d->H; P.Sq = d->Sq; P.Sk = d->Sk;
-  P.qs_b = d->q_stride[0]; P.qs_h = d->q_stride[1]; P.qs_s = d->q_stride[2];
-  P.ks_b = d->k_stride[0]; P.ks_h = d->k_stride[1]; P.ks_s = d->k_stride[2];
-  P.vs_b = d->v_stride[0]; P.vs_h = d->v_stride[1]; P.vs_s = d->v_stride[2];
-  P.os_b = d->o_stride[0]; P.os_h = d->o_stride[1]; P.os_s = d->o_stride[2];
+  fill_problem(P, d);
   P.scale = d->scale_div != 0.0f ? (float)(1.0 / (double)d->scale_div) : d->scale;
-  P.base = d->softmax_base;
-  P.clip = d->clip ? 1 : 0;
-  P.clip_w = (float)((double)d->eta - (double)d->gamma);  // (formed in double, rounded once: as the Python scalar the reference multiplies by)
-  P.clip_g = d->gamma;
-  P.pad = d->key_pad_mask; P.pad_f16 = d->key_pad_dtype == OEH_F16; P.pad_sb = d->key_pad_stride;
-  P.full = d->full_mask; P.full_f16 = d->full_mask_dtype == OEH_F16;
-  P.full_sb = d->full_mask_stride[0]; P.full_sq = d->full_mask_stride[1];
-  P.causal = d->causal ? 1 : 0; P.clamp_min = d->clamp_min ? 1 : 0; P.mask_min = d->mask_min;
-  // the forward's rule (oeh_api.hip fill_params): hidden tiles contribute exactly 0 to every sum and gradient when masked
-  // probabilities are 0 before the clip, the clip maps 0 to 0 with zero gradient, and no vanilla row can be fully masked
-  const bool other_mask = d->key_pad_mask != nullptr || d->full_mask != nullptr;
-  P.skip_ok = (P.causal && d->Sq <= d->Sk && (!P.clip || d->gamma <= 0.0f) && (P.base == 1 || !other_mask) && std::isfinite(d->mask_min) &&
-               d->mask_min < -1e4f) ? 1 : 0;
+  P.skip_ok = causal_skip_ok(d, false) ? 1 : 0;  // (the inference forward's rule; the training kernels have no index dumps)
   P.nQT = (d->Sq + T - 1) / T;
   P.nKT = (d->Sk + T - 1) / T;
 }
@@ -648,13 +601,9 @@ int fwd_train(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q,
   if (dr) fill_drop(P, drop);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(P.nQT * P.B * P.H));
-  if (desc->dtype == OEH_BF16) {
-    if (dr) hipLaunchKernelGGL((fwd_kernel<IN_BF16, true>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((fwd_kernel<IN_BF16, false>), grid, dim3(256), 0, st, P);
-  } else {
-    if (dr) hipLaunchKernelGGL((fwd_kernel<IN_F16, true>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((fwd_kernel<IN_F16, false>), grid, dim3(256), 0, st, P);
-  }
+  dispatch_in16(desc->dtype, dr, [&](auto t, auto drop_on) {
+    hipLaunchKernelGGL((fwd_kernel<decltype(t)::value, decltype(drop_on)::value>), grid, dim3(256), 0, st, P);
+  });
   return oeh::launch_status();
 }
 
@@ -666,7 +615,7 @@ int bwd_run(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, c
   if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || do_ == nullptr || lse == nullptr || dq == nullptr || dk == nullptr ||
       dv == nullptr || work == nullptr || do_stride == nullptr || dq_stride == nullptr || dk_stride == nullptr || dv_stride == nullptr)
     return OEH_EINVAL;
-  if (!strides_ok(do_stride) || !strides_ok(dq_stride) || !strides_ok(dk_stride) || !strides_ok(dv_stride)) return OEH_ENOTSUP;
+  if (!strides_in_range(do_stride) || !strides_in_range(dq_stride) || !strides_in_range(dk_stride) || !strides_in_range(dv_stride)) return OEH_ENOTSUP;
   if (!aligned_rows(q, desc->q_stride) || !aligned_rows(k, desc->k_stride) || !aligned_rows(v, desc->v_stride) || !aligned_rows(o, desc->o_stride) ||
       !aligned_rows(do_, do_stride) || !aligned_rows(dq, dq_stride) || !aligned_rows(dk, dk_stride) || !aligned_rows(dv, dv_stride) ||
       ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(work)) & 3) != 0)
@@ -685,23 +634,10 @@ int bwd_run(const oeh_attn_desc* desc, const oeh_dropout* drop, const void* q, c
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 gq((unsigned)(P.nQT * P.B * P.H)), gk((unsigned)(P.nKT * P.B * P.H));
   // dq first: it writes delta, which dkdv reads (stream order)
-  if (desc->dtype == OEH_BF16) {
-    if (dr) {
-      hipLaunchKernelGGL((dq_kernel<IN_BF16, true>), gq, dim3(256), 0, st, P);
-      hipLaunchKernelGGL((dkdv_kernel<IN_BF16, true>), gk, dim3(256), 0, st, P);
-    } else {
-      hipLaunchKernelGGL((dq_kernel<IN_BF16, false>), gq, dim3(256), 0, st, P);
-      hipLaunchKernelGGL((dkdv_kernel<IN_BF16, false>), gk, dim3(256), 0, st, P);
-    }
-  } else {
-    if (dr) {
-      hipLaunchKernelGGL((dq_kernel<IN_F16, true>), gq, dim3(256), 0, st, P);
-      hipLaunchKernelGGL((dkdv_kernel<IN_F16, true>), gk, dim3(256), 0, st, P);
-    } else {
-      hipLaunchKernelGGL((dq_kernel<IN_F16, false>), gq, dim3(256), 0, st, P);
-      hipLaunchKernelGGL((dkdv_kernel<IN_F16, false>), gk, dim3(256), 0, st, P);
-    }
-  }
+  dispatch_in16(desc->dtype, dr, [&](auto t, auto drop_on) {
+    hipLaunchKernelGGL((dq_kernel<decltype(t)::value, decltype(drop_on)::value>), gq, dim3(256), 0, st, P);
+    hipLaunchKernelGGL((dkdv_kernel<decltype(t)::value, decltype(drop_on)::value>), gk, dim3(256), 0, st, P);
+  });
   return oeh::launch_status();
 }
 
@@ -747,8 +683,7 @@ int oeh_attn_bwd_dropout(const oeh_attn_desc* desc, const oeh_dropout* drop, con
 int oeh_attn_dropout_mask(const oeh_attn_desc* desc, const oeh_dropout* drop, uint8_t* keep, void* stream) {
   int rc = check_drop(drop);
   if (rc != OEH_OK) return rc;
-  if (desc == nullptr || keep == nullptr) return OEH_EINVAL;
-  if (desc->B <= 0 || desc->H <= 0 || desc->Sq <= 0 || desc->Sk <= 0) return OEH_EINVAL;
+  if (keep == nullptr || !desc_sizes_ok(desc, false)) return OEH_EINVAL;  // (the mask has no storage type and no head dim)
   if ((int64_t)desc->B * desc->H >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
   Params P;
   std::memset(&P, 0, sizeof(P));

@@ -24,6 +24,7 @@
 //    bf16), a plain sum that applies the probability scale in fp32; the context quantiser and the gate, in either order, sit in the last launch.
 //    Exponentials that feed a quantiser are the ~1 ulp exp_acc_nonpos, as in the other fake-quant kernels.
 #include "../../include/oeh.h"
+#include "oeh_desc.h"
 #include "oeh_launch.h"
 
 #include <cmath>
@@ -46,14 +47,6 @@ namespace {
 constexpr float kNegInf = -__builtin_huge_valf();
 
 enum { DEC_PLAIN = 0, DEC_STATS = 1, DEC_CLIP = 2 };
-
-template <int IN>
-__device__ __forceinline__ f4 dec_mfma(u4 a, u4 b, f4 c) {
-  if constexpr (IN == IN_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
 
 // e^(a - b) for a <= b or a = -inf; b finite
 __device__ __forceinline__ float exp_diff(float a, float b) { return __builtin_amdgcn_exp2f((a - b) * kLog2e); }
@@ -163,8 +156,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FQ && MODE 
     f4 s[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      s[t] = dec_mfma<IN>(kf[t][0], qf[0], f4{0.f, 0.f, 0.f, 0.f});
-      s[t] = dec_mfma<IN>(kf[t][1], qf[1], s[t]);
+      s[t] = mfma16<IN>(kf[t][0], qf[0], f4{0.f, 0.f, 0.f, 0.f});
+      s[t] = mfma16<IN>(kf[t][1], qf[1], s[t]);
     }
     float mx = kNegInf;
 #pragma unroll
@@ -280,8 +273,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FQ && MODE 
         const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0));
         const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0 + 16 * ROWB));
         const u2 l2 = __builtin_bit_cast(u2, lo), h2 = __builtin_bit_cast(u2, hi);
-        if constexpr (FQ && MODE == DEC_PLAIN) acc[dt] = dec_mfma<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pb2, acc[dt]);  // (the small part first)
-        acc[dt] = dec_mfma<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pb, acc[dt]);
+        if constexpr (FQ && MODE == DEC_PLAIN) acc[dt] = mfma16<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pb2, acc[dt]);  // (the small part first)
+        acc[dt] = mfma16<IN>(u4{l2.x, l2.y, h2.x, h2.y}, pb, acc[dt]);
       }
     }
   }
@@ -424,38 +417,25 @@ struct DecodePlan {
   int n, chunk;
 };
 
-bool rows_aligned16(const void* p, const int64_t* st, int eb) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
-  for (int i = 0; i < 3; ++i)
-    if (((st[i] * eb) & 15) != 0) return false;
-  return true;
-}
-
 // host_only (work_bytes / variant): no pointers to judge
 DecodePlan plan_decode(const oeh_attn_desc* d, int splits, bool host_only, const void* q, const void* k, const void* v, const void* o, const void* work) {
   DecodePlan pl = {OEH_OK, 0, 0};
   // 1. invalid arguments
-  if (d == nullptr || (!host_only && (q == nullptr || k == nullptr || v == nullptr || o == nullptr || work == nullptr))) { pl.rc = OEH_EINVAL; return pl; }
-  if (d->B <= 0 || d->H <= 0 || d->Sq <= 0 || d->Sk <= 0 || d->D <= 0 || splits < 0 || splits > OEH_DECODE_MAX_SPLITS) { pl.rc = OEH_EINVAL; return pl; }
-  if (d->dtype != OEH_F16 && d->dtype != OEH_BF16 && d->dtype != OEH_F32 && d->dtype != OEH_I8) { pl.rc = OEH_EINVAL; return pl; }
-  if (d->softmax_base != OEH_SOFTMAX_VANILLA && d->softmax_base != OEH_SOFTMAX_ONE) { pl.rc = OEH_EINVAL; return pl; }
-  if (d->key_pad_mask != nullptr && d->key_pad_dtype != OEH_F16 && d->key_pad_dtype != OEH_F32) { pl.rc = OEH_EINVAL; return pl; }
+  if (!host_only && (q == nullptr || k == nullptr || v == nullptr || o == nullptr || work == nullptr)) { pl.rc = OEH_EINVAL; return pl; }
+  if (!desc_sane(d, true, true) || splits < 0 || splits > OEH_DECODE_MAX_SPLITS || !softmax_base_ok(d->softmax_base) || !key_pad_ok(d)) { pl.rc = OEH_EINVAL; return pl; }
   // 2. outside the scope
   if (d->full_mask != nullptr || d->gate_hidden != nullptr || (d->dtype != OEH_F16 && d->dtype != OEH_BF16) || d->D != 64 || d->Sq > 16 ||
       (d->clip && d->gamma > 0.0f) || (d->causal && d->Sq > d->Sk)) { pl.rc = OEH_ENOTSUP; return pl; }
   if (d->scale_div != 0.0f ? !(d->scale_div > 0.0f && std::isfinite(d->scale_div)) : !std::isfinite(d->scale)) { pl.rc = OEH_ENOTSUP; return pl; }
   if ((int64_t)d->B * d->H * OEH_DECODE_MAX_SPLITS >= ((int64_t)1 << 31)) { pl.rc = OEH_ENOTSUP; return pl; }
-  {  // strides are element counts in [0, 2^32), as for oeh_attn_fwd (oeh_common.h: bh_offset)
-    const int64_t* sts[4] = {d->q_stride, d->k_stride, d->v_stride, d->o_stride};
-    for (const int64_t* st : sts)
-      for (int i = 0; i < 3; ++i)
-        if (!host_only && (st[i] < 0 || st[i] >= ((int64_t)1 << 32))) { pl.rc = OEH_ENOTSUP; return pl; }
-  }
+  if (!host_only && !desc_strides_in_range(d)) { pl.rc = OEH_ENOTSUP; return pl; }  // (the host-only calls do not judge strides)
   // 3. alignment
   if (!host_only) {
     const int ob = d->o_dtype == OEH_F32 ? 4 : 2;
-    if (!rows_aligned16(q, d->q_stride, 2) || !rows_aligned16(k, d->k_stride, 2) || !rows_aligned16(v, d->v_stride, 2) || !rows_aligned16(o, d->o_stride, ob) ||
-        (reinterpret_cast<uintptr_t>(work) & 15) != 0) { pl.rc = OEH_EALIGN; return pl; }
+    if (!aligned16(q, d->q_stride, 2) || !aligned16(k, d->k_stride, 2) || !aligned16(v, d->v_stride, 2) || !aligned16(o, d->o_stride, ob) || !all16(addr(work))) {
+      pl.rc = OEH_EALIGN;
+      return pl;
+    }
   }
   const int want = splits == 0 ? default_splits(d) : splits;
   const int per = (d->Sk + want - 1) / want;
@@ -466,19 +446,14 @@ DecodePlan plan_decode(const oeh_attn_desc* d, int splits, bool host_only, const
 
 int64_t ml_bytes(const oeh_attn_desc* d, int n) { return (((int64_t)d->B * d->H * n * d->Sq * 2 * 4) + 15) & ~(int64_t)15; }
 
-bool any_fq(const oeh_fq_desc* fq) { return fq != nullptr && (fq->scores.enable || fq->probs.enable || fq->ctx.enable); }
-
 // oeh_attn_decode_fq's own refusals, after those of the plan: OEH_EINVAL (a grid that is none), then OEH_ENOTSUP
 int check_fq(const oeh_fq_desc* fq) {
   const oeh_fq* fs[3] = {&fq->scores, &fq->probs, &fq->ctx};
-  for (const oeh_fq* f : fs) {
-    if (!f->enable) continue;
-    if (!(f->scale > 0.0f) || !std::isfinite(f->scale) || !std::isfinite(f->qmax) || !(f->qmax >= 1.0f) || !(f->zero_point >= 0.0f && f->zero_point <= f->qmax))
-      return OEH_EINVAL;
-  }
+  for (const oeh_fq* f : fs)
+    if (f->enable && !fq_grid_ok(*f, true)) return OEH_EINVAL;
   if (fq->ctx_emit_index) return OEH_ENOTSUP;
   for (const oeh_fq* f : fs)
-    if (f->enable && f->dump_idx != nullptr && f->qmax > 255.0f) return OEH_ENOTSUP;
+    if (f->enable && !fq_dump_fits(*f)) return OEH_ENOTSUP;
   return OEH_OK;
 }
 
@@ -487,19 +462,10 @@ int run_decode(const oeh_attn_desc* desc, const oeh_fq_desc* fq, const DecodePla
   DecodeParams DP;
   std::memset(&DP, 0, sizeof(DP));
   AttnParams& P = DP.A;
+  fill_problem(P, desc);  // (no (B,1,Sq,Sk) mask: the plan has refused it; nothing of the inference kernels' launch geometry)
   P.q = q; P.k = k; P.v = v; P.o = o;
-  P.B = desc->B; P.H = desc->H; P.Sq = desc->Sq; P.Sk = desc->Sk; P.D = desc->D;
-  P.qs_b = desc->q_stride[0]; P.qs_h = desc->q_stride[1]; P.qs_s = desc->q_stride[2];
-  P.ks_b = desc->k_stride[0]; P.ks_h = desc->k_stride[1]; P.ks_s = desc->k_stride[2];
-  P.vs_b = desc->v_stride[0]; P.vs_h = desc->v_stride[1]; P.vs_s = desc->v_stride[2];
-  P.os_b = desc->o_stride[0]; P.os_h = desc->o_stride[1]; P.os_s = desc->o_stride[2];
+  P.D = desc->D;
   P.scale = desc->scale_div != 0.0f ? 1.0f / desc->scale_div : desc->scale;  // (a divisor: one more rounding of 6e-8 relative, as in the other 16-bit kernels)
-  P.base = desc->softmax_base;
-  P.clip = desc->clip ? 1 : 0;
-  P.clip_w = (float)((double)desc->eta - (double)desc->gamma);
-  P.clip_g = desc->gamma;
-  P.pad = desc->key_pad_mask; P.pad_f16 = desc->key_pad_dtype == OEH_F16; P.pad_sb = desc->key_pad_stride;
-  P.causal = desc->causal ? 1 : 0; P.clamp_min = desc->clamp_min ? 1 : 0; P.mask_min = desc->mask_min;
   P.gate = desc->gate; P.gs_b = desc->gate_stride[0]; P.gs_h = desc->gate_stride[1]; P.gs_s = desc->gate_stride[2];
   P.nBH = desc->B * desc->H;
   if (fq != nullptr) {
@@ -513,7 +479,7 @@ int run_decode(const oeh_attn_desc* desc, const oeh_fq_desc* fq, const DecodePla
   DP.acc = reinterpret_cast<float*>(static_cast<unsigned char*>(work) + ml_bytes(desc, pl.n));
   DP.out = desc->o_dtype == OEH_F32 ? IN_F32 : (desc->dtype == OEH_BF16 ? IN_BF16 : IN_F16);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return desc->dtype == OEH_BF16 ? launch_decode_in<IN_BF16>(DP, st, fq != nullptr) : launch_decode_in<IN_F16>(DP, st, fq != nullptr);
+  return dispatch_in16(desc->dtype, [&](auto t) { return launch_decode_in<decltype(t)::value>(DP, st, fq != nullptr); });
 }
 
 }  // namespace

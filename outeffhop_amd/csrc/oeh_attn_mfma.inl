@@ -40,14 +40,6 @@ __device__ __forceinline__ int swz_v(int row) {
   return 0;
 }
 
-template <int IN>
-__device__ __forceinline__ f4 mfma16(u4 a, u4 b, f4 c) {
-  if constexpr (IN == IN_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
-
 // test-only index dump: up to 4 consecutive uint8 (byte stores: rows need not be 4-byte aligned)
 __device__ __forceinline__ void dump4(unsigned char* p, unsigned int word, int nvalid) {
 #pragma unroll

@@ -1,4 +1,4 @@
-// Kernel-argument block shared by the fused attention kernels (host fills it in oeh_api.hip).
+// Kernel-argument block shared by the fused attention kernels (the host fills it: the problem fields in oeh_desc.h fill_problem, the rest in oeh_api.hip fill_params).
 #pragma once
 #include "oeh_common.h"
 
@@ -47,7 +47,7 @@ struct AttnParams {
   int nQT;                    // q tiles (64 rows) per (b,h)
   int nBH, nBHpad;            // B*H and B*H rounded up to a multiple of 8 (XCD affinity of a head's q tiles)
   unsigned magic_nbh, magic_h;  // floor(2^32 / nBHpad), floor(2^32 / H): block id -> (q tile, batch, head) without integer divisions (oeh_common.h: div_magic)
-  int skip_ok;                // causal tiles above the diagonal may be skipped (see oeh_api.hip)
+  int skip_ok;                // causal tiles above the diagonal may be skipped (oeh_desc.h: causal_skip_ok)
   int pad_bool;   // key_pad_boolean (include/oeh.h): mask entries are 0 or <= -1e4
   int head_major;             // fp32-storage kernels: block order in groups of this many heads (0 = all heads' heaviest q tiles first;
                               // oeh_common.h: block_to_tile)

@@ -184,6 +184,25 @@ __device__ __forceinline__ unsigned int pack2_f16(float a, float b) {
 __device__ __forceinline__ unsigned int pack2_bf16(float a, float b) {
   return __builtin_bit_cast(unsigned int, __builtin_convertvector((f2{a, b}), b2));
 }
+// the same for the 16-bit storage type IN, and 8 operands from two rows of four fp32 values
+template <int IN>
+__device__ __forceinline__ unsigned int pack2(float a, float b) {
+  if constexpr (IN == IN_BF16) return pack2_bf16(a, b);
+  else return pack2_f16(a, b);
+}
+template <int IN>
+__device__ __forceinline__ u4 pack8(const f4& a, const f4& b) {
+  return u4{pack2<IN>(a[0], a[1]), pack2<IN>(a[2], a[3]), pack2<IN>(b[0], b[1]), pack2<IN>(b[2], b[3])};
+}
+
+// one v_mfma_f32_16x16x32_{f16,bf16}: 8 operands of the 16-bit type IN per lane in a and b
+template <int IN>
+__device__ __forceinline__ f4 mfma16(u4 a, u4 b, f4 c) {
+  if constexpr (IN == IN_BF16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
+}
 
 // Bit views of a float BY VALUE.  Never write __builtin_bit_cast(unsigned, vec[i]) on an ext_vector element: clang
 // (ROCm 7.2, clang 22) lowers that lvalue form to a load from the vector's BASE address, i.e. element 0 for every i
@@ -503,7 +522,7 @@ __device__ __forceinline__ int snake_block_id(int bid, const int nblocks) {
   return bid;
 }
 
-// b * stride_b + h * stride_h in elements, for strides the host has checked to lie in [0, 2^32) (oeh_api.hip: validate): two
+// b * stride_b + h * stride_h in elements, for strides the host has checked to lie in [0, 2^32) (oeh_desc.h: strides_in_range): two
 // 32 x 32 -> 64-bit products (s_mul_i32 + s_mul_hi_u32 each) instead of two 64 x 64-bit ones with their sign handling - six of
 // these sit in front of a kernel's first load.
 __device__ __forceinline__ long bh_offset(const int b, const long sb, const int h, const long sh) {

@@ -25,6 +25,20 @@ inline auto dispatch_in(const int in, F&& f) {
   }
 }
 
+// The callers pass a descriptor's OEH_* storage type as `in`: the ABI's values and the kernels' template arguments are the same numbers
+static_assert(IN_F16 == OEH_F16 && IN_BF16 == OEH_BF16 && IN_F32 == OEH_F32, "dispatch_in[16] take an oeh_attn_desc.dtype");
+
+// The 16-bit sibling, for kernels without an fp32-storage form (training, decode: dispatch_in would instantiate one): IN_BF16 or (anything
+// else) IN_F16.  With `flag`: a second compile-time switch, f(std::integral_constant<int, IN>{}, std::bool_constant<FLAG>{})
+template <class F>
+inline auto dispatch_in16(const int in, F&& f) {
+  return in == IN_BF16 ? f(std::integral_constant<int, IN_BF16>{}) : f(std::integral_constant<int, IN_F16>{});
+}
+template <class F>
+inline auto dispatch_in16(const int in, const bool flag, F&& f) {
+  return dispatch_in16(in, [&](auto t) { return flag ? f(t, std::true_type{}) : f(t, std::false_type{}); });
+}
+
 // oeh_attn_mfma_d*.hip, oeh_attn_fast_d*.hip, oeh_attn_flash_d*.hip
 int launch_attn_mfma_d32(const AttnParams& P, int in, bool fq, hipStream_t st);
 int launch_attn_mfma_d64(const AttnParams& P, int in, bool fq, hipStream_t st);

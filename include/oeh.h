@@ -514,6 +514,41 @@ size_t oeh_quant_mse_work_bytes(int64_t n, int32_t K);
 int oeh_quant_mse(const void* x, int64_t n, int32_t dtype, const float* cand, int32_t K, double* loss, int32_t accumulate, void* work,
                   void* stream);
 
+/* The tail of a quantised transformer block (oeh_ln.hip): residual add -> sum quantiser -> LayerNorm -> output quantiser on the rows
+ * of a (rows, cols) array in ONE pass - dense -> dropout -> + input -> res_act_quantizer -> LayerNorm of QuantizedBertSelfOutput /
+ * QuantizedBertOutput (quantized_bert.py:541-606), residual + x -> *_res_act_quantizer -> *_layer_norm of QuantizedOPTDecoderLayer
+ * (quantized_opt.py:277-384), with QuantLayerNorm = F.layer_norm on fake-quantised gamma -> activation quantiser
+ * (autoquant_utils.py:64-72, hijacker.py:78-134).  Inference only.
+ * x, r, sum_out and y have `dtype` and contiguous columns; element (i, j) of each sits at base[i * stride + j].  gamma, beta: cols fp32
+ * values, fake-quantised by the caller where weight quantisation is on.  Per row, every operation rounded on its own, in this order:
+ *   s = RN_dtype(x + r)              one fp32 add rounded once to the storage type; s = x without r
+ *   fq_sum enabled: s = RN_dtype(scale * (clamp(rint(s / scale) + zero_point, 0, qmax) - zero_point))   oeh_fake_quant's arithmetic
+ *   sum_out (if given) <- s;  the LayerNorm reads this stored, rounded s - the call equals the composition of the separate ops bit for bit
+ *   mean = sum(s) / cols;  var = sum((s - mean)^2) / cols (biased), fp32, two passes over the row in registers, a fixed summation order
+ *   rstd = 1 / sqrt(var + eps)       correctly rounded square root and division
+ *   y = ((s - mean) * rstd) * gamma + beta;  fq_out enabled: the same fake-quant;  y <- RN_dtype(.)
+ * Bitwise reproducible.  qmax up to 65535 (the 16-bit final LayerNorm of quantized_opt.py:740-741).  The dump_idx fields of the two oeh_fq
+ * are ignored: sum_idx / y_idx (tests; dense (rows, cols) uint8) receive the indices of the sum / output quantiser.
+ * Aliasing: sum_out may be r or x, and y may be x, with the same row stride; anything else must not overlap.
+ * Launch forms (oeh_resid_ln_variant: "ln/wave/CH4/f32", "ln/block/CH8/f16", "ln/scalar/CH1/bf16"; host only, NULL if refused, the
+ * string lives in thread-local storage until the next call on this thread; it assumes 16-byte aligned pointers): one wave per row, four
+ * rows per workgroup, for cols <= 1024; one workgroup per row up to cols <= 8192 - both with 16-byte accesses, which need every base
+ * pointer (gamma and beta included) 16-byte aligned and cols and every given tensor's stride a multiple of 4 (fp32) / 8 (16-bit)
+ * elements; otherwise element accesses, one workgroup per row.
+ * Refusals, before any launch: OEH_EINVAL - desc, x, gamma or y NULL, cols < 1, rows < 0, a dtype other than OEH_F16 / OEH_BF16 /
+ * OEH_F32, eps < 0 or NaN, reserved != 0, a negative stride, a stride of sum_out or y below cols with rows > 1, an enabled quantiser that
+ * is no grid (scale <= 0, qmax < 1, zero point outside [0, qmax]), an index dump of a disabled quantiser; OEH_ENOTSUP - cols > 8192,
+ * rows >= 2^31, an index dump of a grid with qmax > 255.  rows == 0: OEH_OK without a launch. */
+typedef struct oeh_ln_desc {
+  int64_t rows; int32_t cols; int32_t dtype;             /* OEH_F16 | OEH_BF16 | OEH_F32: x, r, sum_out and y share it */
+  int64_t x_stride, r_stride, sum_stride, y_stride;      /* elements between rows; columns are contiguous */
+  float eps; int32_t reserved;
+  oeh_fq fq_sum, fq_out;                                 /* either may be disabled */
+} oeh_ln_desc;
+int oeh_resid_ln_quant(const oeh_ln_desc* d, const void* x, const void* r /* may be NULL */, const float* gamma, const float* beta /* may be NULL */,
+                       void* sum_out /* may be NULL */, void* y, uint8_t* sum_idx /* tests */, uint8_t* y_idx /* tests */, void* stream);
+const char* oeh_resid_ln_variant(const oeh_ln_desc* d);  /* which launch form, or NULL if refused; host only */
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -78,6 +78,13 @@ class oeh_proj_seg(C.Structure):
                 ("y_stride_row", C.c_int64), ("transpose", C.c_int32), ("acc_add", C.c_void_p)]
 
 
+class oeh_ln_desc(C.Structure):
+    """include/oeh.h: the rows of oeh_resid_ln_quant (residual + sum quantiser + LayerNorm + output quantiser)."""
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int32), ("dtype", C.c_int32),
+                ("x_stride", C.c_int64), ("r_stride", C.c_int64), ("sum_stride", C.c_int64), ("y_stride", C.c_int64),
+                ("eps", C.c_float), ("reserved", C.c_int32), ("fq_sum", oeh_fq), ("fq_out", oeh_fq)]
+
+
 # every symbol include/oeh.h declares (tests/test_abi.py checks the .so exports exactly these)
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
@@ -88,6 +95,7 @@ EXPORTS = (
     "oeh_attn_decode_work_bytes", "oeh_attn_decode", "oeh_attn_decode_variant", "oeh_attn_decode_fq", "oeh_attn_decode_fq_variant",
     "oeh_outlier_stats_work_bytes", "oeh_outlier_stats",
     "oeh_quant_mse_work_bytes", "oeh_quant_mse",
+    "oeh_resid_ln_quant", "oeh_resid_ln_variant",
 )
 
 _lib = None
@@ -177,6 +185,10 @@ def load() -> C.CDLL:
     lib.oeh_quant_mse_work_bytes.restype = C.c_size_t
     lib.oeh_quant_mse.argtypes = [vp, i64, i32, vp, i32, vp, i32, vp, vp]
     lib.oeh_quant_mse.restype = C.c_int
+    lib.oeh_resid_ln_quant.argtypes = [C.POINTER(oeh_ln_desc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_resid_ln_quant.restype = C.c_int
+    lib.oeh_resid_ln_variant.argtypes = [C.POINTER(oeh_ln_desc)]
+    lib.oeh_resid_ln_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -471,6 +471,49 @@ int oeh_fake_quant(const void* x, void* y, uint8_t* idx, int64_t n, int32_t dtyp
   return oeh::launch_fake_quant(x, y, idx, n, dtype, make_fq(&f), reinterpret_cast<hipStream_t>(stream));
 }
 
+// oeh_resid_ln_quant / oeh_resid_ln_variant: the descriptor's own refusals (no pointers), then the launch form for `vec16`
+static int ln_check(const oeh_ln_desc* d, bool with_sum, bool with_sum_idx, bool with_y_idx) {
+  if (d == nullptr || d->cols < 1 || d->rows < 0 || !dtype_ok(d->dtype) || !(d->eps >= 0.0f) || d->reserved != 0) return OEH_EINVAL;
+  if (d->x_stride < 0 || d->r_stride < 0 || d->sum_stride < 0 || d->y_stride < 0) return OEH_EINVAL;
+  if (d->rows > 1 && (d->y_stride < d->cols || (with_sum && d->sum_stride < d->cols))) return OEH_EINVAL;
+  if (d->fq_sum.enable && !oeh::fq_grid_ok(d->fq_sum, false)) return OEH_EINVAL;
+  if (d->fq_out.enable && !oeh::fq_grid_ok(d->fq_out, false)) return OEH_EINVAL;
+  if ((with_sum_idx && !d->fq_sum.enable) || (with_y_idx && !d->fq_out.enable)) return OEH_EINVAL;
+  if (d->cols > oeh::kLnMaxCols || d->rows >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
+  if ((with_sum_idx && d->fq_sum.qmax > 255.0f) || (with_y_idx && d->fq_out.qmax > 255.0f)) return OEH_ENOTSUP;
+  return OEH_OK;
+}
+static bool ln_strides_vec16(const oeh_ln_desc* d, bool with_r, bool with_sum) {
+  const int nv = d->dtype == OEH_F32 ? 4 : 8;
+  return d->cols % nv == 0 && d->x_stride % nv == 0 && d->y_stride % nv == 0 && (!with_r || d->r_stride % nv == 0) &&
+         (!with_sum || d->sum_stride % nv == 0);
+}
+
+int oeh_resid_ln_quant(const oeh_ln_desc* d, const void* x, const void* r, const float* gamma, const float* beta, void* sum_out, void* y,
+                       uint8_t* sum_idx, uint8_t* y_idx, void* stream) {
+  if (x == nullptr || gamma == nullptr || y == nullptr) return OEH_EINVAL;
+  const int rc = ln_check(d, sum_out != nullptr, sum_idx != nullptr, y_idx != nullptr);
+  if (rc != OEH_OK) return rc;
+  if (d->rows == 0) return OEH_OK;
+  const bool vec16 = ln_strides_vec16(d, r != nullptr, sum_out != nullptr) && all16(addr(x) | addr(r) | addr(gamma) | addr(beta) | addr(sum_out) | addr(y));
+  oeh::LnArgs a = {};
+  a.x = x; a.r = r; a.gamma = gamma; a.beta = beta; a.sum = sum_out; a.y = y; a.sum_idx = sum_idx; a.y_idx = y_idx;
+  a.rows = d->rows; a.cols = d->cols;
+  a.x_stride = d->x_stride; a.r_stride = d->r_stride; a.sum_stride = d->sum_stride; a.y_stride = d->y_stride;
+  a.eps = d->eps;
+  a.fq_sum = make_fq(&d->fq_sum); a.fq_out = make_fq(&d->fq_out);
+  return oeh::launch_resid_ln(a, d->dtype, oeh::ln_plan(d->cols, d->dtype, vec16), reinterpret_cast<hipStream_t>(stream));
+}
+
+const char* oeh_resid_ln_variant(const oeh_ln_desc* d) {
+  static thread_local char name[48];
+  if (ln_check(d, d != nullptr && d->sum_stride != 0, false, false) != OEH_OK) return nullptr;
+  const oeh::LnPlan pl = oeh::ln_plan(d->cols, d->dtype, ln_strides_vec16(d, true, true));
+  std::snprintf(name, sizeof name, "ln/%s/CH%d/%s", pl.form == oeh::LN_WAVE ? "wave" : pl.form == oeh::LN_BLOCK ? "block" : "scalar", pl.ch,
+                d->dtype == OEH_F32 ? "f32" : d->dtype == OEH_BF16 ? "bf16" : "f16");
+  return name;
+}
+
 int oeh_gate_fwd(const void* hidden, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t d, int64_t hidden_stride_b,
                  int64_t hidden_stride_t, const float* w1, const float* b1, const float* w2, const float* b2, int32_t hidden_units,
                  int32_t per_head_pool, float scaling, float* gate_out, void* stream) {

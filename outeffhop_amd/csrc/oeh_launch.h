@@ -59,6 +59,38 @@ int launch_fake_quant(const void* x, void* y, unsigned char* idx, long n, int in
 int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_b, long hs_t, const float* w1, const float* b1,
                 const float* w2, const float* b2, int m_units, int pool, float scaling, float* out, hipStream_t st);
 int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st);
+// oeh_ln.hip: residual + sum quantiser + LayerNorm + output quantiser on rows (include/oeh.h: oeh_resid_ln_quant).  The kernel's argument
+// block; which of the three launch forms a problem takes and with how many accesses per thread (CH) is decided HERE, for the launch and for
+// oeh_resid_ln_variant alike.
+struct LnArgs {
+  const void *x, *r;              // r may be null
+  const float *gamma, *beta;      // beta may be null
+  void *sum, *y;                  // sum may be null
+  unsigned char *sum_idx, *y_idx; // tests; may be null
+  long rows;
+  int cols;
+  long x_stride, r_stride, sum_stride, y_stride;
+  float eps;
+  FqP fq_sum, fq_out;
+};
+enum { LN_WAVE = 0, LN_BLOCK = 1, LN_SCALAR = 2 };
+constexpr int kLnWaveCols = 1024, kLnMaxCols = 8192;
+struct LnPlan {
+  int form, ch;
+};
+// vec16: every base pointer is 16-byte aligned and cols and every row stride are multiples of the 16-byte vector (4 fp32 / 8 16-bit elements)
+inline LnPlan ln_plan(const int cols, const int in, const bool vec16) {
+  const int nv = in == IN_F32 ? 4 : 8;
+  auto pow2_at_least = [](int need, int lo) { while (lo < need) lo *= 2; return lo; };
+  if (!vec16) {
+    const int need = (cols + 255) / 256;
+    return LnPlan{LN_SCALAR, need <= 1 ? 1 : need <= 4 ? 4 : need <= 16 ? 16 : 32};
+  }
+  const int chunks = cols / nv;
+  if (cols <= kLnWaveCols) return LnPlan{LN_WAVE, pow2_at_least((chunks + 63) / 64, 1)};
+  return LnPlan{LN_BLOCK, pow2_at_least((chunks + 255) / 256, 1)};
+}
+int launch_resid_ln(const LnArgs& a, int in, LnPlan pl, hipStream_t st);
 // oeh_stats.hip, oeh_qmse.hip
 long stats_chunks(long cols);
 int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,

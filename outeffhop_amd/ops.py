@@ -854,6 +854,94 @@ def fake_quant(x: torch.Tensor, spec: FakeQuantSpec, want_idx: bool = False):
     return (y, idx) if want_idx else y
 
 
+# ---- the quantised block tail (include/oeh.h: oeh_resid_ln_quant): residual + sum quantiser + LayerNorm + output quantiser in one pass
+LN_MAX_COLS = 8192  # rows longer than this are refused (OEH_ENOTSUP)
+
+
+def _rows_view(t: torch.Tensor, cols: int):
+    """`t` (..., cols) as rows: (a tensor that shares t's memory where a 2-D view exists - else a contiguous copy -, its row stride)."""
+    if t.dim() == 0 or t.shape[-1] != cols:
+        raise ValueError(f"expected a last dimension of {cols}, got shape {tuple(t.shape)}")
+    if cols > 1 and t.stride(-1) != 1:
+        t = t.contiguous()
+    try:
+        v = t.view(-1, cols)
+    except RuntimeError:
+        t = t.contiguous()
+        v = t.view(-1, cols)
+    return v, (v.stride(0) if v.shape[0] > 1 else cols)
+
+
+def _ln_desc(rows: int, cols: int, dtype, strides, eps: float, fq_sum: Optional[FakeQuantSpec], fq_out: Optional[FakeQuantSpec]) -> _lib.oeh_ln_desc:
+    d = _lib.oeh_ln_desc()
+    d.rows, d.cols, d.dtype = rows, cols, _DT[dtype]
+    d.x_stride, d.r_stride, d.sum_stride, d.y_stride = strides
+    d.eps = float(eps)
+    for dst, spec in ((d.fq_sum, fq_sum), (d.fq_out, fq_out)):
+        _fill_fq(dst, None if spec is None else FakeQuantSpec(spec.scale, spec.zero_point, spec.qmax))  # (the dumps are arguments of the call)
+    return d
+
+
+def resid_ln_quant(x: torch.Tensor, residual: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                   eps: float = 1e-5, *, fq_sum: Optional[FakeQuantSpec] = None, fq_out: Optional[FakeQuantSpec] = None, want_sum: bool = False,
+                   want_idx: bool = False, out: Optional[torch.Tensor] = None, sum_out: Optional[torch.Tensor] = None):
+    """fq_out(LayerNorm(fq_sum(x + residual))) over the last dimension in ONE kernel (`include/oeh.h: oeh_resid_ln_quant`): the tail of a
+    quantised BERT / OPT block.  x, residual (..., N) fp16 / bf16 / fp32 with a contiguous last dimension, read in place where their
+    leading dimensions collapse to one row stride; weight (N) - required - and bias (N): the LayerNorm's gamma and beta, taken as fp32 (already
+    fake-quantised where weight quantisation is on).  Either quantiser may be None.  Returns y, or (sum, y) with want_sum - sum = fq_sum(x +
+    residual), what the next residual connection reads -, or (sum, y, sum_idx, y_idx) with want_idx (uint8 indices, None for an absent
+    quantiser; tests).  out / sum_out: where to write (x's shape and dtype); sum_out may be `residual` or `x`, and out may be `x`."""
+    if weight is None:
+        raise ValueError("resid_ln_quant needs the LayerNorm's weight")
+    dev = _need_gpu(x, residual, weight, bias, out, sum_out)
+    _need_dtype(x)
+    cols = x.shape[-1] if x.dim() else 0
+    if cols < 1:
+        raise ValueError("resid_ln_quant needs a last dimension of at least 1")
+    for t_, what in ((residual, "residual"), (out, "out"), (sum_out, "sum_out")):
+        if t_ is not None and (t_.shape != x.shape or t_.dtype != x.dtype):
+            raise ValueError(f"{what} must have x's shape and dtype")
+    if weight.numel() != cols or (bias is not None and bias.numel() != cols):
+        raise ValueError("weight / bias must hold one value per column")
+    want_sum = want_sum or want_idx or sum_out is not None
+    xv, xs = _rows_view(x.detach(), cols)
+    rv, rs = _rows_view(residual.detach(), cols) if residual is not None else (None, 0)
+    y = out if out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    s = (sum_out if sum_out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)) if want_sum else None
+    outs = []
+    for t_ in (s, y):  # an output must BE the memory it was given as: no copy may stand in for it
+        if t_ is None:
+            outs.append((None, 0))
+            continue
+        v_, st_ = _rows_view(t_, cols)
+        if v_.data_ptr() != t_.data_ptr() or (v_.shape[0] > 1 and st_ < cols):
+            raise ValueError("out / sum_out need a contiguous last dimension and leading dimensions that collapse to one row stride")
+        outs.append((v_, st_))
+    (sv, ss), (yv, ys) = outs
+    rows = xv.shape[0]
+    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+    g, b = f32(weight), f32(bias)
+    sidx = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_idx and fq_sum is not None else None
+    yidx = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_idx and fq_out is not None else None
+    d = _ln_desc(rows, cols, x.dtype, (xs, rs, ss, ys), eps, fq_sum, fq_out)
+    if rows:  # (an empty tensor has no address to hand over)
+        with _on_device(dev):
+            rc = _lib.load().oeh_resid_ln_quant(C.byref(d), _ptr(xv), _ptr(rv), _ptr(g), _ptr(b), _ptr(sv), _ptr(yv), _ptr(sidx), _ptr(yidx), _stream())
+        _lib.check(rc, "oeh_resid_ln_quant")
+    if want_idx:
+        return s, y, sidx, yidx
+    return (s, y) if want_sum else y
+
+
+def resid_ln_variant(rows: int, cols: int, dtype=torch.float32, *, row_stride: Optional[int] = None, eps: float = 1e-5) -> Optional[str]:
+    """Name of the launch form `resid_ln_quant` takes for (rows, cols) tensors of `dtype` whose rows are `row_stride` (default: cols)
+    elements apart and 16-byte aligned ("ln/wave/CH4/f32", "ln/block/CH8/f16", "ln/scalar/CH1/bf16"), or None if refused.  Host only."""
+    st = cols if row_stride is None else int(row_stride)
+    d = _ln_desc(int(rows), int(cols), dtype, (st, st, st, st), eps, None, None)
+    r = _lib.load().oeh_resid_ln_variant(C.byref(d))
+    return None if r is None else r.decode()
+
+
 _calib_work = {}  # (device index, stream handle) -> the 36-KB histograms of that stream's on-device percentile selection
 
 

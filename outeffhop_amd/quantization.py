@@ -10,6 +10,9 @@ Host-side mirror of the part of the reference's `quantization/` package that the
   QuantizedModule / QuantizedActivation                     quantization/base_quantized_classes.py:38-199
   QuantLinear (weight + output-activation quant)            quantization/hijacker.py:27-134, autoquant_utils.py:18-20
   Quantized{Bert,OPT}...AttentionWithExtras                 models/quantized_bert.py:221-440, quantized_opt.py:54-274
+  QuantLayerNorm                                            quantization/autoquant_utils.py:64-72
+  QuantizedBertSelfOutput / QuantizedBertOutput             models/quantized_bert.py:541-606
+  QuantizedOPTDecoderLayer                                  models/quantized_opt.py:277-384
 
 Same class / attribute / buffer names (`activation_quantizer.quantizer._delta`, `_zero_float`, ...) so calibrated
 state dicts are interchangeable.  Activation fake-quant runs on the GPU: fused into the attention kernel once the
@@ -46,6 +49,14 @@ class Qstates(BaseEnumOptions):
     fix_ranges = 2
     learn_ranges = 4
     estimate_ranges_train = 8
+
+
+def _adopt_unset_buffers(mod: nn.Module, state_dict, prefix: str) -> None:
+    """A calibrated checkpoint carries range buffers that a fresh module still holds as None (`_delta`, `current_xmin` ...): give such a
+    buffer the checkpoint's tensor before the loader looks, or a strict load reports the key as unexpected."""
+    for name, buf in mod._buffers.items():
+        if buf is None and prefix + name in state_dict and name not in mod._non_persistent_buffers_set:
+            mod._buffers[name] = state_dict[prefix + name].detach().clone()
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -150,6 +161,10 @@ class AsymmetricUniformQuantizer(nn.Module):
         self._delta = None
         self._zero_float = None
 
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        _adopt_unset_buffers(self, state_dict, prefix)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
     def extra_repr(self):
         return f"n_bits={self.n_bits}, per_channel={self.per_channel}, is_initalized={self.is_initialized}"
 
@@ -253,6 +268,14 @@ class RangeEstimatorBase(nn.Module):
         self.current_xmin = None
         self.current_xmax = None
         self.device_state = None
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        _adopt_unset_buffers(self, state_dict, prefix)
+        seen = len(unexpected_keys)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        # the reference's estimator holds its quantiser as a submodule: a checkpoint of it repeats the manager's `quantizer.*` keys under
+        # `range_estimator.quantizer.*` - the same object here, loaded once through the manager
+        unexpected_keys[seen:] = [k for k in unexpected_keys[seen:] if not k.startswith(prefix + "quantizer.")]
 
     def _percentile_on_device(self, x, q_lo, q_hi, momentum):
         """(np.percentile(x, q_lo), np.percentile(x, q_hi)) [+ running average] without leaving the GPU: no topk, no host sync."""
@@ -914,16 +937,102 @@ class QuantLinear(QuantizedModule, nn.Linear):
         return res
 
 
+class QuantLayerNorm(QuantizedModule, nn.LayerNorm):
+    """nn.LayerNorm with fake-quantised gamma (cached in eval) and fake-quantised output activations (autoquant_utils.py:64-72,
+    hijacker.py:78-134).  On the GPU, without autograd and with an output quantiser the kernel can apply (`fusable_out`), the forward is ONE
+    launch of `ops.resid_ln_quant`; otherwise the torch ops the reference runs - F.layer_norm, then the manager (range estimation included)."""
+
+    def __init__(self, *args, activation=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.activation_function = copy.deepcopy(activation) if activation else None
+        self.activation_quantizer = QuantizationManager(qmethod=self.act_method, init=self.act_range_method, qparams=self.act_qparams,
+                                                        init_params=self.act_range_options)
+        w_init = dict(percentile=self.percentile) if self.weight_range_method is CurrentMinMaxEstimator else self.weight_range_options
+        self.weight_quantizer = QuantizationManager(qmethod=self.method, init=self.weight_range_method,
+                                                    per_channel=self.per_channel_weights, qparams=self.weight_qparams, init_params=w_init)
+        self._fused_ln_calls = 0  # launches of the fused kernel from this module's own forward (tests)
+
+    get_params = QuantLinear.get_params  # the same rule: quantise the weight when asked to, keep the pair in eval
+
+    @property
+    def fusable_out(self) -> bool:
+        """The output quantiser is inactive, or frozen and asymmetric: what the kernel's epilogue takes."""
+        aq = self.activation_quantizer
+        return (not self._qa) or (aq.is_fixed and type(aq.quantizer) is AsymmetricUniformQuantizer)
+
+    def out_spec(self) -> Optional[FakeQuantSpec]:
+        return self.activation_quantizer.quantizer.spec() if self._qa else None
+
+    def kernel_ok(self, x, weight, bias) -> bool:
+        """`ops.resid_ln_quant` computes this module's forward on `x` (the callers that fuse a residual in front add their own conditions)."""
+        return (FUSED_LN and x.is_cuda and x.dtype in ops._DT and weight is not None and self.activation_function is None
+                and len(self.normalized_shape) == 1 and 1 <= self.normalized_shape[0] <= ops.LN_MAX_COLS and x.dim() >= 1
+                and x.shape[-1] == self.normalized_shape[0] and self.fusable_out and not ops.grad_recording(x, weight, bias))
+
+    def kernel_params(self, weight, bias):
+        """(gamma, beta) as the kernel reads them - fp32, dense - for the pair `get_params` returned, under one watch over that pair: an
+        fp32 module's cached pair is passed through as it is, a 16-bit module's is converted once."""
+        src = self.__dict__.setdefault("_ln_src", {})
+        src["weight"], src["bias"] = weight, bias
+        f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+        return cached(self.__dict__, "_ln_cache", (), lambda: [(src, "weight"), (src, "bias")], lambda: (f32(weight), f32(bias)))
+
+    def forward(self, x, offsets=None):
+        weight, bias = self.get_params()
+        if self.kernel_ok(x, weight, bias):
+            _count(self, "_fused_ln_calls")
+            g, b = self.kernel_params(weight, bias)
+            return ops.resid_ln_quant(x, None, g, b, self.eps, fq_out=self.out_spec())
+        res = nn.functional.layer_norm(x.contiguous(), self.normalized_shape, None if weight is None else weight.contiguous(),
+                                       None if bias is None else bias.contiguous(), self.eps)
+        if self.activation_function is not None:
+            res = self.activation_function(res)
+        if self._qa:
+            res = self.activation_quantizer(res)
+        return res
+
+
+def resid_ln_tail(owner: nn.Module, x, residual, res_quantizer: Optional["QuantizedActivation"], ln: nn.Module, want_sum: bool = False):
+    """ln(res_quantizer(x + residual)) - the tail of a quantised block (quantized_bert.py:565-571, quantized_opt.py:341-349,365-374) - as ONE
+    launch where the kernel applies: both quantisers inactive or frozen and asymmetric, inference on the GPU, no forward hooks on the two
+    members (a hook must see its module's own output).  `owner`._fused_ln_calls counts those launches.  residual / res_quantizer may be None.
+    Returns y, or (the quantised sum, y) with want_sum."""
+    if isinstance(ln, QuantLayerNorm) and not owner.training and (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype)):
+        rq_ok = res_quantizer is None or (res_quantizer.fusable and (not res_quantizer._qa or type(res_quantizer.activation_quantizer.quantizer) is AsymmetricUniformQuantizer))
+        mods = (ln,) if res_quantizer is None else (ln, res_quantizer)
+        if rq_ok and not has_hooks(*mods):
+            weight, bias = ln.get_params()
+            if ln.kernel_ok(x, weight, bias) and not ops.grad_recording(residual):
+                _count(owner, "_fused_ln_calls")
+                g, b = ln.kernel_params(weight, bias)
+                return ops.resid_ln_quant(x, residual, g, b, ln.eps, fq_sum=None if res_quantizer is None else res_quantizer.fixed_spec(),
+                                          fq_out=ln.out_spec(), want_sum=want_sum)
+    s = x if residual is None else x + residual
+    if res_quantizer is not None:
+        s = res_quantizer(s)
+    y = ln(s)
+    return (s, y) if want_sum else y
+
+
 def quantize_model(model: nn.Module, **quant_params) -> nn.Module:
-    """The nn.Linear case of the reference's recursive rewriter (autoquant_utils.py:236-270): the only one the attention
-    classes need (query/key/value, q_proj/k_proj/v_proj/out_proj)."""
+    """The cases of the reference's recursive rewriter (autoquant_utils.py:236-270) that the attention classes and the block tails need:
+    nn.Linear (query/key/value, q_proj/k_proj/v_proj/out_proj, dense, fc2), nn.LayerNorm, and Sequential(Linear, ReLU) - OPT's fc1 with
+    its activation folded into the QuantLinear (quantized_opt.py:292-294)."""
+    def copy_params(q, src, clone):
+        q.weight.data = src.weight.data.clone() if clone else src.weight.data
+        if getattr(src, "bias", None) is not None:
+            q.bias.data = src.bias.data.clone() if clone else src.bias.data
+        return q.to(src.weight.device)
+
     if type(model) is nn.Linear:
-        q = QuantLinear(model.in_features, model.out_features, bias=model.bias is not None, **quant_params)
-        q.weight.data = model.weight.data
-        if model.bias is not None:
-            q.bias.data = model.bias.data
-        return q.to(model.weight.device)
-    raise NotImplementedError(f"quantize_model: {type(model).__name__} is outside the attention path")
+        return copy_params(QuantLinear(model.in_features, model.out_features, bias=model.bias is not None, **quant_params), model, False)
+    if type(model) is nn.LayerNorm and model.elementwise_affine:
+        return copy_params(QuantLayerNorm(model.normalized_shape, eps=model.eps, **quant_params), model, False)
+    if type(model) is nn.Sequential and len(model) == 2 and type(model[0]) is nn.Linear and isinstance(model[1], nn.ReLU):
+        lin = model[0]
+        q = QuantLinear(lin.in_features, lin.out_features, bias=lin.bias is not None, activation=model[1], **quant_params)
+        return nn.Sequential(copy_params(q, lin, True))
+    raise NotImplementedError(f"quantize_model: {type(model).__name__} is outside the attention path and the block tails")
 
 
 class QuantizedModel(nn.Module):
@@ -1512,6 +1621,99 @@ class QuantizedOPTAttentionWithExtras(_QuantAttnBase):
         return self.out_proj(merged), weights, new_past
 
 
+# ------------------------------------------------------------------------------------------------------------
+# the block tails: what follows the attention module's out_proj in a quantised layer
+# ------------------------------------------------------------------------------------------------------------
+_LN_DECOMPOSED_KEYS = {"QuantizedBertSelfOutput": "layer_norm_res_self_output", "QuantizedBertOutput": "layer_norm_res_output"}
+
+
+class _QuantizedBertTail(QuantizedModel):
+    """dense -> dropout -> + input -> res_act_quantizer -> LayerNorm (quantized_bert.py:541-606).  Dropout is the identity in eval; in
+    training the torch ops run.  The decomposed integer LayerNorm (quantized_bert.py:78-143) and the logarithmic sum quantiser are refused."""
+
+    def __init__(self, org_model, **quant_params):
+        super().__init__()
+        self.quant_dict = DotDict(quant_params.get("quant_dict") or {})
+        key = _LN_DECOMPOSED_KEYS[type(self).__name__]
+        if self.quant_dict.get(key, False):
+            raise NotImplementedError(f"quant_dict['{key}']: the decomposed LayerNorm is not implemented (only the fake-quantised nn.LayerNorm is)")
+        if self.quant_dict.get("y", None) == "log":
+            raise NotImplementedError("quant_dict['y'] == 'log': the logarithmic residual quantiser is not implemented")
+        self.dense = quantize_model(org_model.dense, **quant_params)
+        self.dropout = org_model.dropout
+        self.res_act_quantizer = QuantizedActivation(**quant_params)
+        self.LayerNorm = quantize_model(org_model.LayerNorm, **quant_params)
+        self._fused_ln_calls = 0
+
+    def forward(self, hidden_states, input_tensor):
+        hidden_states = self.dense(hidden_states)
+        hidden_states = self.dropout(hidden_states)
+        return resid_ln_tail(self, hidden_states, input_tensor, self.res_act_quantizer, self.LayerNorm)
+
+
+class QuantizedBertSelfOutput(_QuantizedBertTail):
+    """quantized_bert.py:541-571."""
+
+
+class QuantizedBertOutput(_QuantizedBertTail):
+    """quantized_bert.py:574-606."""
+
+
+class QuantizedOPTDecoderLayer(QuantizedModel):
+    """quantized_opt.py:277-384.  In eval with frozen ranges the residual sums, their quantisers and the LayerNorms are three launches:
+    pre-LN (do_layer_norm_before) - the first LayerNorm alone, the attention residual with final_layer_norm (its quantised sum is the
+    FFN's residual), and the FFN residual's quantiser on the torch add (its LayerNorm belongs to the next layer); post-LN - each
+    residual with the LayerNorm that follows it, and nothing else."""
+
+    def __init__(self, org_model, **quant_params):
+        super().__init__()
+        self.embed_dim = org_model.embed_dim
+        self.do_layer_norm_before = org_model.do_layer_norm_before
+        self.dropout = org_model.dropout
+        self.activation_fn = org_model.activation_fn
+        assert isinstance(self.activation_fn, nn.ReLU)
+        self.self_attn = QuantizedOPTAttentionWithExtras(org_model.self_attn, **quant_params)
+        self.self_attn_layer_norm = quantize_model(org_model.self_attn_layer_norm, **quant_params)
+        self.fc1_act = quantize_model(nn.Sequential(org_model.fc1, org_model.activation_fn), **quant_params)[0]
+        self.fc2 = quantize_model(org_model.fc2, **quant_params)
+        self.final_layer_norm = quantize_model(org_model.final_layer_norm, **quant_params)
+        self.self_attn_res_act_quantizer = QuantizedActivation(**quant_params)
+        self.ffn_res_act_quantizer = QuantizedActivation(**quant_params)
+        self._fused_ln_calls = 0
+
+    def tail(self, attn_output, residual):
+        """Everything after the attention module: (B, S, E) attention output and the layer's input -> the layer's output."""
+        hidden_states = nn.functional.dropout(attn_output, p=self.dropout, training=self.training)
+        shape = hidden_states.shape
+        if self.do_layer_norm_before:
+            residual, hidden_states = resid_ln_tail(self, hidden_states, residual, self.self_attn_res_act_quantizer, self.final_layer_norm, want_sum=True)
+        else:
+            hidden_states = residual = resid_ln_tail(self, hidden_states, residual, self.self_attn_res_act_quantizer, self.self_attn_layer_norm)
+        residual = residual.reshape(-1, shape[-1])
+        hidden_states = self.fc2(self.fc1_act(hidden_states.reshape(-1, shape[-1])))
+        hidden_states = nn.functional.dropout(hidden_states, p=self.dropout, training=self.training)
+        if self.do_layer_norm_before:
+            return self.ffn_res_act_quantizer(residual + hidden_states).view(shape)
+        return resid_ln_tail(self, hidden_states, residual, self.ffn_res_act_quantizer, self.final_layer_norm).view(shape)
+
+    def forward(self, hidden_states, attention_mask=None, layer_head_mask=None, output_attentions=False, use_cache=False, past_key_value=None):
+        residual = hidden_states
+        if self.do_layer_norm_before:
+            hidden_states = resid_ln_tail(self, hidden_states, None, None, self.self_attn_layer_norm)
+        hidden_states, self_attn_weights, present_key_value = self.self_attn(hidden_states=hidden_states, past_key_value=past_key_value,
+                                                                             attention_mask=attention_mask, layer_head_mask=layer_head_mask,
+                                                                             output_attentions=output_attentions)
+        outputs = (self.tail(hidden_states, residual),)
+        if output_attentions:
+            outputs += (self_attn_weights,)
+        if use_cache:
+            outputs += (present_key_value,)
+        return outputs
+
+
+# The block tails (QuantLayerNorm, QuantizedBert[Self]Output, QuantizedOPTDecoderLayer) as ONE launch of ops.resid_ln_quant where it
+# applies; False: the separate ops (torch add, ops.fake_quant, F.layer_norm, ops.fake_quant) - tests compare the two.
+FUSED_LN = True
 # estimate_ranges state: the score and probability quantisers' percentile ranges from `ops.attn_calibrate` (the (B,H,Sq,Sk)
 # tensors are recomputed tile by tile inside the kernel, never stored); False: the observable path materialises them.
 FUSED_CALIBRATION = True

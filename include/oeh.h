@@ -549,6 +549,67 @@ int oeh_resid_ln_quant(const oeh_ln_desc* d, const void* x, const void* r /* may
                        void* sum_out /* may be NULL */, void* y, uint8_t* sum_idx /* tests */, uint8_t* y_idx /* tests */, void* stream);
 const char* oeh_resid_ln_variant(const oeh_ln_desc* d);  /* which launch form, or NULL if refused; host only */
 
+/* The front of a quantised model (oeh_embed.hip): 1 <= n_tab <= 3 embedding lookups -> their sums, each behind its activation quantiser ->
+ * LayerNorm -> output quantiser, ONE output row per (b, s) of a (B, S) id grid in ONE pass - QuantizedBertEmbeddings (quantized_bert.py:
+ * 146-218: word + token type -> sum_input_token_type_embd_act_quantizer, += position -> sum_pos_embd_act_quantizer, LayerNorm) and the OPT
+ * decoder front (quantized_opt.py:27-51, 549-569: embed_tokens + embed_positions -> embed_sum_act_quantizer, no LayerNorm), on tables the
+ * reference fake-quantises as whole tensors (QuantEmbedding, autoquant_utils.py:75-95).  Inference only.
+ * Lookup t reads row ids[b * id_stride_b + s * id_stride_s] (int32 or int64 elements; a stride may be 0: a (1, S) id tensor broadcast over
+ * the batch) of its table, n_rows rows of `cols` contiguous elements row_stride elements apart.  ids == NULL, lookup 0 only: row b * S + s
+ * ("dense rows": inputs_embeds).  A table row e_t arrives in one of three forms; with RN = rounding to `dtype`, every operation rounded on
+ * its own, in this order:
+ *   OEH_TAB_PLAIN  `dtype` elements taken as they are
+ *   OEH_TAB_GRID   `dtype` elements w, the per-tensor symmetric weight grid applied to the gathered row with the rounding points of
+ *                  SymmetricUniformQuantizer.forward's torch ops on a `dtype` tensor (uniform_quantizers.py:150-186): sc = RN(scale);
+ *                  q = RN(w / sc) (a true division); i = clamp(rint(q), int_min, int_max) + 0; e = RN(sc * i)
+ *   OEH_TAB_I8     int8 elements i, the grid's integers: sc = RN(scale); e = RN(sc * i).  The same bits as OEH_TAB_GRID on the table the
+ *                  integers were taken from (+ 0 above: an integer is never -0, where torch's scale * round(-0.3) is) at a quarter of an
+ *                  fp32 table's memory and gather traffic.
+ * Then per row:  s = e_0;  for t = 1 .. n_tab - 1:  s = RN(s + e_t);  fq_sum[t] enabled: s = RN(scale * (clamp(rint(s / scale) + zero_point,
+ * 0, qmax) - zero_point)), oeh_fake_quant's arithmetic.  sum_out (if given) <- the final s.  gamma == NULL: y <- the final s.  Otherwise the
+ * LayerNorm of that s and fq_out exactly as oeh_resid_ln_quant defines them (moments, summation order per launch form, qmax up to 65535):
+ * in the same launch form the two entry points give the same bits for the same s.  Bitwise reproducible.  The dump_idx fields are ignored:
+ * sum_idx / y_idx (tests; dense (B * S, cols) uint8) receive the indices of fq_sum[n_tab - 1] / fq_out.
+ * Ids are data: a row with an id outside [0, n_rows) reads nothing from any table, its y (and sum_out) row is written as NaN, its index dumps
+ * are not written, and *bad_rows (if given; a device int32 the caller zeroes) is incremented by one.  Nothing synchronises.
+ * Launch forms (oeh_embed_sum_variant: "embed/wave/CH4/T3/f32", "embed/block/CH4/T2/f16", "embed/scalar/CH1/T1/bf16" - form, accesses per
+ * thread, lookups, storage type; host only, NULL if refused, thread-local storage): those of oeh_resid_ln_quant.  The 16-byte forms need every
+ * `dtype` base pointer (tables, gamma, beta, sum_out, y) 16-byte aligned and cols, every table's row stride and the output strides multiples
+ * of 4 (fp32) / 8 (16-bit) elements - an int8 table: base and row stride multiples of that many BYTES; otherwise element accesses.
+ * Refusals, before any launch, in this order: OEH_EINVAL - d, y or a table NULL, n_tab outside 1..3, lookup t >= 1 without ids, cols < 1,
+ * B or S < 0, a negative n_rows or stride, a stride of sum_out or y below cols with more than one row, a dtype, id_dtype or form code that
+ * is none, a grid table with scale <= 0 (or not finite) or int_min >= int_max, an enabled quantiser that is no grid, an enabled fq_sum[0] or
+ * fq_sum[t >= n_tab], fq_out, beta or y_idx without gamma, an index dump of a disabled quantiser, reserved != 0, eps < 0 or NaN with gamma
+ * given; OEH_ENOTSUP - cols > 8192, B * S >= 2^31, an int8 table with int_min < -128 or int_max > 127, an index dump of a grid with
+ * qmax > 255; OEH_EALIGN - ids off their element size, an int8 table off 4 bytes, a `dtype` pointer off its element size (gamma, beta: 4).
+ * B * S == 0: OEH_OK without a launch. */
+#define OEH_TAB_PLAIN 0
+#define OEH_TAB_GRID 1
+#define OEH_TAB_I8 2
+#define OEH_ID_I32 0
+#define OEH_ID_I64 1
+typedef struct oeh_embed_lookup {
+  const void* table;                    /* n_rows x cols, `dtype` (OEH_TAB_PLAIN, OEH_TAB_GRID) or int8 (OEH_TAB_I8) */
+  const void* ids;                      /* NULL (lookup 0 only): dense rows */
+  int64_t n_rows, row_stride;           /* row_stride in elements of the table */
+  int64_t id_stride_b, id_stride_s;     /* in id elements; 0 broadcasts */
+  int32_t id_dtype, form;               /* OEH_ID_*, OEH_TAB_* */
+  float scale, int_min, int_max;        /* the weight grid of OEH_TAB_GRID / OEH_TAB_I8 */
+  int32_t reserved;
+} oeh_embed_lookup;
+typedef struct oeh_embed_desc {
+  int32_t B, S, cols, dtype;            /* OEH_F16 | OEH_BF16 | OEH_F32: the float tables, sum_out and y share it */
+  int32_t n_tab, reserved;
+  int64_t sum_stride, y_stride;         /* elements between rows */
+  float eps; int32_t reserved2;
+  oeh_embed_lookup tab[3];
+  oeh_fq fq_sum[3];                     /* [t]: behind the add of lookup t; [0] stays disabled */
+  oeh_fq fq_out;
+} oeh_embed_desc;
+int oeh_embed_sum_quant(const oeh_embed_desc* d, const float* gamma /* may be NULL */, const float* beta /* may be NULL */, void* sum_out /* may be NULL */,
+                        void* y, uint8_t* sum_idx /* tests */, uint8_t* y_idx /* tests */, int32_t* bad_rows /* may be NULL */, void* stream);
+const char* oeh_embed_sum_variant(const oeh_embed_desc* d);  /* which launch form for d's pointers and strides, or NULL if refused; host only */
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

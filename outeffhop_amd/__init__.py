@@ -3,7 +3,7 @@
 Python host surface mirroring the reference's plugin interface:
     SOFTMAX_MAPPING, AttentionGateType, BertSelfAttentionWithExtras, OPTAttentionWithExtras,
     ViTSelfAttentionWithExtras, Association / Hopfield / HopfieldPooling, QuantizedActivation,
-    Quantized{Bert,OPT}...AttentionWithExtras, kurtosis / inf_norm / OutlierMeter (the reference's result metrics)
+    Quantized{Bert,OPT}...AttentionWithExtras, QuantEmbedding / QuantizedBertEmbeddings / opt_embed_front, kurtosis / inf_norm / OutlierMeter (the reference's result metrics)
 over the C-ABI library `lib/liboeh_hip.so` (include/oeh.h).  There is no CPU implementation in this package:
 every op raises if the HIP library is missing or a tensor is not on a GPU.
 """
@@ -21,13 +21,17 @@ from .quantization import (  # noqa: F401
     OptMethod,
     QMethods,
     QuantizationManager,
+    QuantEmbedding,
     QuantizedActivation,
+    QuantizedBertEmbeddings,
     QuantizedBertSelfAttentionWithExtras,
     QuantizedOPTAttentionWithExtras,
+    QuantizedOPTLearnedPositionalEmbedding,
     QuantLinear,
     RangeEstimators,
     RunningMinMaxEstimator,
     get_quant_config,
+    opt_embed_front,
     val_qparams,
 )
 from .softmax import (SOFTMAX_MAPPING, ClipSoftmax, ClipSoftmax_1, Softmax_1, clipped_softmax, clipped_softmax1, clipped_softmax_1,  # noqa: F401

@@ -85,6 +85,24 @@ class oeh_ln_desc(C.Structure):
                 ("eps", C.c_float), ("reserved", C.c_int32), ("fq_sum", oeh_fq), ("fq_out", oeh_fq)]
 
 
+OEH_TAB_PLAIN, OEH_TAB_GRID, OEH_TAB_I8 = 0, 1, 2  # include/oeh.h: the forms of an embedding table
+OEH_ID_I32, OEH_ID_I64 = 0, 1
+
+
+class oeh_embed_lookup(C.Structure):
+    """include/oeh.h: one lookup of oeh_embed_sum_quant (table, ids, strides, the table's form and weight grid)."""
+    _fields_ = [("table", C.c_void_p), ("ids", C.c_void_p), ("n_rows", C.c_int64), ("row_stride", C.c_int64),
+                ("id_stride_b", C.c_int64), ("id_stride_s", C.c_int64), ("id_dtype", C.c_int32), ("form", C.c_int32),
+                ("scale", C.c_float), ("int_min", C.c_float), ("int_max", C.c_float), ("reserved", C.c_int32)]
+
+
+class oeh_embed_desc(C.Structure):
+    """include/oeh.h: the rows of oeh_embed_sum_quant (lookups + sum quantisers + LayerNorm + output quantiser)."""
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("cols", C.c_int32), ("dtype", C.c_int32), ("n_tab", C.c_int32), ("reserved", C.c_int32),
+                ("sum_stride", C.c_int64), ("y_stride", C.c_int64), ("eps", C.c_float), ("reserved2", C.c_int32),
+                ("tab", oeh_embed_lookup * 3), ("fq_sum", oeh_fq * 3), ("fq_out", oeh_fq)]
+
+
 # every symbol include/oeh.h declares (tests/test_abi.py checks the .so exports exactly these)
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
@@ -96,6 +114,7 @@ EXPORTS = (
     "oeh_outlier_stats_work_bytes", "oeh_outlier_stats",
     "oeh_quant_mse_work_bytes", "oeh_quant_mse",
     "oeh_resid_ln_quant", "oeh_resid_ln_variant",
+    "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
 _lib = None
@@ -189,6 +208,10 @@ def load() -> C.CDLL:
     lib.oeh_resid_ln_quant.restype = C.c_int
     lib.oeh_resid_ln_variant.argtypes = [C.POINTER(oeh_ln_desc)]
     lib.oeh_resid_ln_variant.restype = C.c_char_p
+    lib.oeh_embed_sum_quant.argtypes = [C.POINTER(oeh_embed_desc), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_embed_sum_quant.restype = C.c_int
+    lib.oeh_embed_sum_variant.argtypes = [C.POINTER(oeh_embed_desc)]
+    lib.oeh_embed_sum_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -514,6 +514,82 @@ const char* oeh_resid_ln_variant(const oeh_ln_desc* d) {
   return name;
 }
 
+// oeh_embed_sum_quant / oeh_embed_sum_variant: every refusal in the order OEH_EINVAL -> OEH_ENOTSUP -> OEH_EALIGN, then whether the 16-byte forms apply
+static int embed_check(const oeh_embed_desc* d, const float* gamma, const float* beta, const void* sum_out, const void* y, bool with_sum_idx,
+                       bool with_y_idx, bool* vec16) {
+  if (d == nullptr || y == nullptr || d->n_tab < 1 || d->n_tab > 3 || d->cols < 1 || d->B < 0 || d->S < 0 || !dtype_ok(d->dtype)) return OEH_EINVAL;
+  if (d->reserved != 0 || d->reserved2 != 0 || d->sum_stride < 0 || d->y_stride < 0) return OEH_EINVAL;
+  const int64_t rows = (int64_t)d->B * d->S;
+  if (rows > 1 && (d->y_stride < d->cols || (sum_out != nullptr && d->sum_stride < d->cols))) return OEH_EINVAL;
+  for (int t = 0; t < d->n_tab; ++t) {
+    const oeh_embed_lookup& l = d->tab[t];
+    if (l.table == nullptr || (t >= 1 && l.ids == nullptr) || l.reserved != 0) return OEH_EINVAL;
+    if (l.ids == nullptr && l.n_rows < rows) return OEH_EINVAL;  // dense rows: one per (b, s)
+    if (l.n_rows < 0 || l.row_stride < 0 || l.id_stride_b < 0 || l.id_stride_s < 0) return OEH_EINVAL;
+    if ((l.id_dtype != OEH_ID_I32 && l.id_dtype != OEH_ID_I64) || l.form < OEH_TAB_PLAIN || l.form > OEH_TAB_I8) return OEH_EINVAL;
+    if (l.form != OEH_TAB_PLAIN && (!(l.scale > 0.0f) || !std::isfinite(l.scale) || !(l.int_min < l.int_max))) return OEH_EINVAL;
+  }
+  for (int t = 0; t < 3; ++t) {
+    if (d->fq_sum[t].enable && (t == 0 || t >= d->n_tab || !oeh::fq_grid_ok(d->fq_sum[t], false))) return OEH_EINVAL;
+  }
+  if (d->fq_out.enable && !oeh::fq_grid_ok(d->fq_out, false)) return OEH_EINVAL;
+  if (gamma == nullptr && (beta != nullptr || d->fq_out.enable || with_y_idx)) return OEH_EINVAL;
+  if ((with_sum_idx && !d->fq_sum[d->n_tab - 1].enable) || (with_y_idx && !d->fq_out.enable)) return OEH_EINVAL;
+  if (gamma != nullptr && !(d->eps >= 0.0f)) return OEH_EINVAL;
+  if (d->cols > oeh::kLnMaxCols || rows >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
+  for (int t = 0; t < d->n_tab; ++t) {
+    if (d->tab[t].form == OEH_TAB_I8 && (d->tab[t].int_min < -128.0f || d->tab[t].int_max > 127.0f)) return OEH_ENOTSUP;
+  }
+  if ((with_sum_idx && d->fq_sum[d->n_tab - 1].qmax > 255.0f) || (with_y_idx && d->fq_out.qmax > 255.0f)) return OEH_ENOTSUP;
+  const int eb = elem_bytes(d->dtype), nv = d->dtype == OEH_F32 ? 4 : 8;
+  bool v16 = d->cols % nv == 0 && d->y_stride % nv == 0 && (sum_out == nullptr || d->sum_stride % nv == 0) &&
+             all16(addr(gamma) | addr(beta) | addr(sum_out) | addr(y));
+  for (int t = 0; t < d->n_tab; ++t) {
+    const oeh_embed_lookup& l = d->tab[t];
+    if (l.ids != nullptr && addr(l.ids) % (l.id_dtype == OEH_ID_I64 ? 8 : 4) != 0) return OEH_EALIGN;
+    if (addr(l.table) % (l.form == OEH_TAB_I8 ? 4 : eb) != 0) return OEH_EALIGN;
+    // (an int8 row is read nv BYTES at a time; a float row nv elements = 16 bytes)
+    v16 = v16 && l.row_stride % nv == 0 && (l.form == OEH_TAB_I8 ? addr(l.table) % nv == 0 : all16(addr(l.table)));
+  }
+  if (addr(y) % eb != 0 || addr(sum_out) % eb != 0 || addr(gamma) % 4 != 0 || addr(beta) % 4 != 0) return OEH_EALIGN;
+  *vec16 = v16;
+  return OEH_OK;
+}
+
+int oeh_embed_sum_quant(const oeh_embed_desc* d, const float* gamma, const float* beta, void* sum_out, void* y, uint8_t* sum_idx, uint8_t* y_idx,
+                        int32_t* bad_rows, void* stream) {
+  bool vec16 = false;
+  const int rc = embed_check(d, gamma, beta, sum_out, y, sum_idx != nullptr, y_idx != nullptr, &vec16);
+  if (rc != OEH_OK) return rc;
+  if (addr(bad_rows) % 4 != 0) return OEH_EALIGN;
+  if ((int64_t)d->B * d->S == 0) return OEH_OK;
+  oeh::EmbedArgs a = {};
+  for (int t = 0; t < d->n_tab; ++t) {
+    const oeh_embed_lookup& l = d->tab[t];
+    a.tab[t] = oeh::EmbedTab{l.table, l.ids, l.n_rows, l.row_stride, l.id_stride_b, l.id_stride_s, l.form, l.id_dtype == OEH_ID_I64, l.scale, l.int_min, l.int_max};
+    a.fq_sum[t] = make_fq(&d->fq_sum[t]);
+  }
+  a.gamma = gamma; a.beta = beta; a.sum = sum_out; a.y = y; a.sum_idx = sum_idx; a.y_idx = y_idx; a.bad_rows = bad_rows;
+  a.rows = (long)d->B * d->S; a.S = d->S; a.cols = d->cols;
+  a.sum_stride = d->sum_stride; a.y_stride = d->y_stride;
+  a.eps = d->eps;
+  a.fq_out = make_fq(&d->fq_out);
+  return oeh::launch_embed(a, d->dtype, d->n_tab, oeh::ln_plan(d->cols, d->dtype, vec16), reinterpret_cast<hipStream_t>(stream));
+}
+
+const char* oeh_embed_sum_variant(const oeh_embed_desc* d) {
+  static thread_local char name[48];
+  bool vec16 = false;
+  // (the outputs and gamma / beta are taken as given with every part and 16-byte aligned, as oeh_resid_ln_variant does)
+  const void* const aligned = reinterpret_cast<const void*>((uintptr_t)4096);
+  if (embed_check(d, static_cast<const float*>(aligned), nullptr, d != nullptr && d->sum_stride != 0 ? aligned : nullptr, aligned, false, false, &vec16) != OEH_OK)
+    return nullptr;
+  const oeh::LnPlan pl = oeh::ln_plan(d->cols, d->dtype, vec16);
+  std::snprintf(name, sizeof name, "embed/%s/CH%d/T%d/%s", pl.form == oeh::LN_WAVE ? "wave" : pl.form == oeh::LN_BLOCK ? "block" : "scalar", pl.ch,
+                d->n_tab, d->dtype == OEH_F32 ? "f32" : d->dtype == OEH_BF16 ? "bf16" : "f16");
+  return name;
+}
+
 int oeh_gate_fwd(const void* hidden, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t d, int64_t hidden_stride_b,
                  int64_t hidden_stride_t, const float* w1, const float* b1, const float* w2, const float* b2, int32_t hidden_units,
                  int32_t per_head_pool, float scaling, float* gate_out, void* stream) {

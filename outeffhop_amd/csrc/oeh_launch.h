@@ -91,6 +91,30 @@ inline LnPlan ln_plan(const int cols, const int in, const bool vec16) {
   return LnPlan{LN_BLOCK, pow2_at_least((chunks + 255) / 256, 1)};
 }
 int launch_resid_ln(const LnArgs& a, int in, LnPlan pl, hipStream_t st);
+// oeh_embed.hip: up to three gathered table rows -> sums with their quantisers -> (LayerNorm -> output quantiser) per (b, s) of an id grid
+// (include/oeh.h: oeh_embed_sum_quant).  The launch forms are ln_plan's; vec16 there also covers every table's base and row stride.
+enum { TAB_PLAIN = 0, TAB_GRID = 1, TAB_I8 = 2 };
+struct EmbedTab {
+  const void* w;       // the table: storage type (TAB_PLAIN, TAB_GRID) or int8 indices (TAB_I8)
+  const void* ids;     // null: lookup 0 reads row (b * S + s) of w ("dense rows")
+  long n_rows, row_stride, id_sb, id_ss;
+  int form, id64;
+  float scale, lo, hi;  // the weight grid of TAB_GRID / TAB_I8: fp32 scale (rounded to the storage type in the kernel), int_min, int_max
+};
+struct EmbedArgs {
+  EmbedTab tab[3];
+  FqP fq_sum[3];                  // [t]: behind the add of lookup t (t >= 1); [0] is never enabled
+  const float *gamma, *beta;      // gamma null: no LayerNorm, y is the final sum
+  void *sum, *y;                  // sum may be null
+  unsigned char *sum_idx, *y_idx; // tests; may be null
+  int* bad_rows;                  // may be null
+  long rows;
+  int S, cols;
+  long sum_stride, y_stride;
+  float eps;
+  FqP fq_out;
+};
+int launch_embed(const EmbedArgs& a, int in, int n_tab, LnPlan pl, hipStream_t st);
 // oeh_stats.hip, oeh_qmse.hip
 long stats_chunks(long cols);
 int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,

@@ -942,6 +942,154 @@ def resid_ln_variant(rows: int, cols: int, dtype=torch.float32, *, row_stride: O
     return None if r is None else r.decode()
 
 
+# ---- the quantised model front (include/oeh.h: oeh_embed_sum_quant): embedding lookups + sums + their quantisers + LayerNorm in one pass
+@dataclass
+class EmbedLookup:
+    """One lookup of `embed_sum_quant`.  table (n_rows, cols): the storage dtype, or int8 (the weight grid's integers, with `scale`); ids:
+    int32 / int64, broadcastable to the call's (B, S) - None (the first lookup only): `table` is (B, S, cols), one dense row per position.
+    scale (with int_min, int_max) on a float table: the per-tensor symmetric weight grid, applied to the gathered rows on the fly."""
+
+    table: torch.Tensor
+    ids: Optional[torch.Tensor] = None
+    scale: Optional[float] = None
+    int_min: float = -128.0
+    int_max: float = 127.0
+
+
+def _embed_desc(B: int, S: int, cols: int, dtype, lookups, views, strides, eps: float, fq_sums, fq_out: Optional[FakeQuantSpec]) -> _lib.oeh_embed_desc:
+    d = _lib.oeh_embed_desc()
+    d.B, d.S, d.cols, d.dtype, d.n_tab = B, S, cols, _DT[dtype], len(lookups)
+    d.sum_stride, d.y_stride = strides
+    d.eps = float(eps)
+    for t, (lk, ((tv, ts), iv)) in enumerate(zip(lookups, views)):
+        l = d.tab[t]
+        l.table, l.row_stride, l.n_rows = tv.data_ptr(), ts, (B * S if iv is None else lk.table.shape[0])
+        if iv is not None:
+            l.ids, l.id_stride_b, l.id_stride_s = iv.data_ptr(), iv.stride(0), iv.stride(1)
+            l.id_dtype = _lib.OEH_ID_I64 if iv.dtype == torch.int64 else _lib.OEH_ID_I32
+        l.form = _lib.OEH_TAB_I8 if lk.table.dtype == torch.int8 else _lib.OEH_TAB_GRID if lk.scale is not None else _lib.OEH_TAB_PLAIN
+        if lk.scale is not None:
+            l.scale, l.int_min, l.int_max = float(lk.scale), float(lk.int_min), float(lk.int_max)
+    for t, spec in enumerate(fq_sums):
+        _fill_fq(d.fq_sum[t + 1], None if spec is None else FakeQuantSpec(spec.scale, spec.zero_point, spec.qmax))  # (the dumps are arguments of the call)
+    _fill_fq(d.fq_out, None if fq_out is None else FakeQuantSpec(fq_out.scale, fq_out.zero_point, fq_out.qmax))
+    return d
+
+
+def _embed_geometry(lookups, dtype):
+    """(B, S, cols, dtype) of a call and, per lookup, ((table rows view, row stride), ids expanded to (B, S) or None)."""
+    if not 1 <= len(lookups) <= 3:
+        raise ValueError("embed_sum_quant takes one to three lookups")
+    shapes = []
+    for t, lk in enumerate(lookups):
+        if lk.ids is None:
+            if t != 0 or lk.table.dim() != 3:
+                raise ValueError("only the first lookup may come without ids, as dense (B, S, cols) rows")
+            shapes.append(tuple(lk.table.shape[:2]))
+        else:
+            if lk.ids.dtype not in (torch.int32, torch.int64) or lk.ids.dim() != 2 or lk.table.dim() != 2:
+                raise ValueError("ids must be 2-D int32 / int64 tensors and their tables 2-D")
+            shapes.append(tuple(lk.ids.shape))
+        if lk.table.dtype == torch.int8:
+            if lk.scale is None:
+                raise ValueError("an int8 table needs its scale")
+        elif dtype is None:
+            dtype = lk.table.dtype
+        elif lk.table.dtype != dtype:
+            raise ValueError(f"tables must share one storage dtype, got {dtype} and {lk.table.dtype}")
+    if dtype not in _DT:
+        raise ValueError(f"unsupported dtype {dtype}" if dtype is not None else "int8 tables alone do not say the storage dtype: pass dtype=")
+    B, S = torch.broadcast_shapes(*shapes)
+    cols = lookups[0].table.shape[-1]
+    views = []
+    for lk in lookups:
+        if lk.table.shape[-1] != cols:
+            raise ValueError("tables must share their row length")
+        if lk.ids is None:
+            if tuple(lk.table.shape[:2]) != (B, S):
+                raise ValueError("dense rows must cover the whole (B, S) grid")
+            views.append((_rows_view(lk.table.detach(), cols), None))
+        else:
+            tb = lk.table.detach()
+            if cols > 1 and tb.stride(1) != 1:
+                tb = tb.contiguous()
+            views.append(((tb, tb.stride(0) if tb.shape[0] > 1 else cols), lk.ids.detach().expand(B, S)))
+    return B, S, cols, dtype, views
+
+
+def embed_sum_quant(lookups, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, eps: float = 1e-5, *, fq_sums=(),
+                    fq_out: Optional[FakeQuantSpec] = None, dtype=None, want_sum: bool = False, want_idx: bool = False, out: Optional[torch.Tensor] = None,
+                    sum_out: Optional[torch.Tensor] = None, check_ids: bool = False):
+    """The front of a quantised model in ONE kernel (`include/oeh.h: oeh_embed_sum_quant`): s = row of lookups[0]; for each further lookup t
+    s = fq_sums[t - 1](s + its row); y = fq_out(LayerNorm(s)) with the LayerNorm's `weight` (and `bias`), or y = s without them.  lookups:
+    one to three `EmbedLookup`; fq_sums: one entry (a FakeQuantSpec or None) per lookup after the first, missing ones are None.  Returns y
+    (B, S, cols), or (sum, y) with want_sum, or (sum, y, sum_idx, y_idx) with want_idx (uint8 indices of the LAST sum quantiser and of
+    fq_out, None for an absent one; tests).  out / sum_out: where to write.  A row with an id outside its table is NaN (nothing is read for
+    it); check_ids=True also returns the number of such rows as the last element, at the price of one synchronisation."""
+    lookups = list(lookups)
+    dev = _need_gpu(weight, bias, out, sum_out, *[lk.table for lk in lookups], *[lk.ids for lk in lookups])
+    B, S, cols, dtype, views = _embed_geometry(lookups, dtype)
+    fq_sums = list(fq_sums) + [None] * (len(lookups) - 1 - len(fq_sums))
+    if len(fq_sums) != len(lookups) - 1:
+        raise ValueError("fq_sums has one entry per lookup after the first")
+    if weight is None and (bias is not None or fq_out is not None):
+        raise ValueError("bias and fq_out belong to the LayerNorm: pass its weight")
+    if weight is not None and (weight.numel() != cols or (bias is not None and bias.numel() != cols)):
+        raise ValueError("weight / bias must hold one value per column")
+    shape = (B, S, cols)
+    for t_, what in ((out, "out"), (sum_out, "sum_out")):
+        if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != dtype):
+            raise ValueError(f"{what} must be (B, S, cols) of the tables' dtype")
+    want_sum = want_sum or want_idx or sum_out is not None
+    device = lookups[0].table.device
+    y = out if out is not None else torch.empty(shape, dtype=dtype, device=device)
+    s = (sum_out if sum_out is not None else torch.empty(shape, dtype=dtype, device=device)) if want_sum else None
+    outs = []
+    for t_ in (s, y):  # an output must BE the memory it was given as: no copy may stand in for it
+        if t_ is None:
+            outs.append((None, 0))
+            continue
+        v_, st_ = _rows_view(t_, cols)
+        if v_.data_ptr() != t_.data_ptr() or (v_.shape[0] > 1 and st_ < cols):
+            raise ValueError("out / sum_out need a contiguous last dimension and leading dimensions that collapse to one row stride")
+        outs.append((v_, st_))
+    (sv, ss), (yv, ys) = outs
+    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+    g, b = f32(weight), f32(bias)
+    last = fq_sums[-1] if fq_sums else None
+    sidx = torch.empty(shape, dtype=torch.uint8, device=device) if want_idx and last is not None else None
+    yidx = torch.empty(shape, dtype=torch.uint8, device=device) if want_idx and fq_out is not None else None
+    bad = torch.zeros(1, dtype=torch.int32, device=device) if check_ids else None
+    d = _embed_desc(B, S, cols, dtype, lookups, views, (ss, ys), eps, fq_sums, fq_out)
+    if B * S:  # (an empty tensor has no address to hand over)
+        with _on_device(dev):
+            rc = _lib.load().oeh_embed_sum_quant(C.byref(d), _ptr(g), _ptr(b), _ptr(sv), _ptr(yv), _ptr(sidx), _ptr(yidx), _ptr(bad), _stream())
+        _lib.check(rc, "oeh_embed_sum_quant")
+    res = (s, y, sidx, yidx) if want_idx else (s, y) if want_sum else y
+    if check_ids:
+        n_bad = int(bad.item())
+        return (*res, n_bad) if isinstance(res, tuple) else (res, n_bad)
+    return res
+
+
+def embed_sum_variant(B: int, S: int, cols: int, dtype=torch.float32, *, n_tab: int = 3, int8: bool = False, row_stride: Optional[int] = None,
+                      table_offset: int = 0) -> Optional[str]:
+    """Name of the launch form `embed_sum_quant` takes for `n_tab` lookups of `cols`-element rows `row_stride` (default: cols) elements
+    apart into (B, S, cols) outputs of `dtype` - float tables, or int8 ones - whose tables start `table_offset` bytes behind a 16-byte
+    boundary ("embed/wave/CH4/T3/f32", "embed/block/CH4/T2/f16", "embed/scalar/CH1/T1/bf16"), or None if refused.  Host only."""
+    st = cols if row_stride is None else int(row_stride)
+    d = _lib.oeh_embed_desc()
+    d.B, d.S, d.cols, d.dtype, d.n_tab = int(B), int(S), int(cols), _DT[dtype], int(n_tab)
+    d.sum_stride = d.y_stride = cols
+    for t in range(max(0, min(int(n_tab), 3))):
+        l = d.tab[t]
+        l.table, l.ids, l.n_rows, l.row_stride, l.id_stride_b, l.id_stride_s = 4096 + int(table_offset), 4096, 1, st, int(S), 1
+        if int8:
+            l.form, l.scale, l.int_min, l.int_max = _lib.OEH_TAB_I8, 1.0, -128.0, 127.0
+    r = _lib.load().oeh_embed_sum_variant(C.byref(d))
+    return None if r is None else r.decode()
+
+
 _calib_work = {}  # (device index, stream handle) -> the 36-KB histograms of that stream's on-device percentile selection
 
 

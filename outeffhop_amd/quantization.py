@@ -796,7 +796,7 @@ class QuantLinear(QuantizedModule, nn.Linear):
     def get_params(self):
         if not self.training and self.cached_params:
             return self.cached_params
-        weight, bias = self.weight, self.bias
+        weight, bias = self.weight, getattr(self, "bias", None)
         if self._qw:
             weight = self.weight_quantizer(weight)
         if self._caching and not self.training and self.cached_params is None:
@@ -1014,10 +1014,128 @@ def resid_ln_tail(owner: nn.Module, x, residual, res_quantizer: Optional["Quanti
     return (s, y) if want_sum else y
 
 
+class FP32Acts(nn.Module):
+    """The reference's pass-through in the place of an activation quantiser (base_quantized_classes.py:202-207): no ranges, no state."""
+
+    def forward(self, x):
+        return x
+
+    def reset_ranges(self):
+        pass
+
+
+class QuantEmbedding(QuantizedModule, nn.Embedding):
+    """nn.Embedding with a fake-quantised table (autoquant_utils.py:75-95).  Its output is NOT quantised again - a looked-up row of a quantised
+    table is already on the grid - so the activation quantiser is the pass-through.  forward: F.embedding on the (in eval: cached)
+    fake-quantised table.  The fused front (`embed_front`) does not read that fp32 copy: `kernel_table` hands the kernel the int8 indices of
+    the frozen grid, or the raw table with the grid to apply on the fly."""
+
+    def __init__(self, *args, activation=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.max_norm is not None:
+            raise NotImplementedError("QuantEmbedding: max_norm renormalises the table in place during the forward; not implemented")
+        self.activation_function = None
+        w_init = dict(percentile=self.percentile) if self.weight_range_method is CurrentMinMaxEstimator else self.weight_range_options
+        self.weight_quantizer = QuantizationManager(qmethod=self.method, init=self.weight_range_method,
+                                                    per_channel=self.per_channel_weights, qparams=self.weight_qparams, init_params=w_init)
+        self.activation_quantizer = FP32Acts()
+
+    get_params = QuantLinear.get_params  # the same rule: quantise the table when asked to, keep it in eval (there is no bias)
+
+    def _index_table(self):
+        """(int8 indices of the table or None where the grid's integers do not fit a signed byte, fp32 scale, int_min, int_max) of the weight
+        quantiser's current grid, built once per (table, range) under one watch - the table, the quantiser's buffers, the quantiser, its bits."""
+        qz = self.weight_quantizer.quantizer
+
+        def build():
+            with torch.no_grad():
+                lo, hi = float(qz.int_min), float(qz.int_max)
+                fits = lo >= -128.0 and hi <= 127.0
+                idx = qz.to_integer_forward(self.weight.detach()).to(torch.int8).contiguous() if fits else None
+                return idx, float(np.float32(float(qz.scale))), lo, hi
+        return cached(self.__dict__, "_i8_table", (qz, getattr(qz, "n_bits", None)),
+                      lambda: [(self._parameters, "weight")] + [(qz._buffers, n_) for n_ in qz._buffers], build)
+
+    def kernel_table(self):
+        """This table as `ops.embed_sum_quant` gathers from it: (tensor, scale or None, int_min, int_max).  Full-precision weights: the table as
+        it is.  Quantised weights on a frozen per-tensor symmetric grid: its int8 indices with the scale - or, where the integers do not fit a
+        signed byte, the raw table with the grid to apply to the gathered rows.  Anything else (a range still being estimated, another weight
+        quantiser): the fake-quantised table of `get_params`, range estimation included, as it is."""
+        if not self._qw:
+            return self.weight.detach(), None, 0.0, 0.0
+        mgr = self.weight_quantizer
+        if mgr.is_fixed and type(mgr.quantizer) is SymmetricUniformQuantizer and mgr.quantizer.is_initialized:
+            idx, scale, lo, hi = self._index_table()
+            return (idx if idx is not None else self.weight.detach()), scale, lo, hi
+        return self.get_params()[0].detach(), None, 0.0, 0.0
+
+    def forward(self, x, offsets=None):
+        weight, _ = self.get_params()
+        res = nn.functional.embedding(x.contiguous(), weight.contiguous(), self.padding_idx, None, self.norm_type, self.scale_grad_by_freq, self.sparse)
+        if self._qa:
+            res = self.activation_quantizer(res)
+        return res
+
+
+def _sum_quantizer_ok(q: "QuantizedActivation") -> bool:
+    return q.fusable and (not q._qa or type(q.activation_quantizer.quantizer) is AsymmetricUniformQuantizer)
+
+
+def embed_front(owner: nn.Module, lookups, sum_quantizers, ln: Optional[nn.Module] = None):
+    """ln(q_k(... q_1(E_0[ids_0] + E_1[ids_1]) ... + E_k[ids_k])) - the front of a quantised model - as ONE launch of `ops.embed_sum_quant`
+    where the kernel applies, else None (the caller then runs the torch ops the reference runs).  lookups: (QuantEmbedding, ids) pairs, the
+    first possibly (None, inputs_embeds); sum_quantizers: one QuantizedActivation per lookup after the first; ln: a QuantLayerNorm or None.
+    The kernel applies to GPU tensors of a supported dtype, outside training, with no autograd recording on the tables or inputs_embeds, every
+    active sum / output quantiser frozen and asymmetric, no forward hooks on the members, rows of at most 8192 elements.
+    `owner`._fused_embed_calls counts the launches."""
+    if not FUSED_EMBED or owner.training:
+        return None
+    mods = [m for m, _ in lookups if m is not None] + list(sum_quantizers) + ([ln] if ln is not None else [])
+    if has_hooks(*mods) or not all(_sum_quantizer_ok(q) for q in sum_quantizers):
+        return None
+    if any(m is not None and (not isinstance(m, QuantEmbedding) or m.training) for m, _ in lookups):
+        return None
+    if ln is not None and not (isinstance(ln, QuantLayerNorm) and ln.activation_function is None and len(ln.normalized_shape) == 1 and ln.fusable_out
+                               and ln.weight is not None):
+        return None
+    first = lookups[0][1] if lookups[0][0] is None else lookups[0][0].weight
+    dtype, cols = first.dtype, first.shape[-1]
+    if dtype not in ops._DT or not 1 <= cols <= ops.LN_MAX_COLS or (ln is not None and ln.normalized_shape[0] != cols):
+        return None
+    args, watched = [], []
+    for m, ids in lookups:
+        if m is None:
+            if not ids.is_cuda or ids.dim() != 3:
+                return None
+            watched.append(ids)
+            continue
+        if not (m.weight.is_cuda and ids.is_cuda and ids.dim() == 2 and ids.dtype in (torch.int32, torch.int64) and m.weight.dtype == dtype
+                and m.weight.shape[-1] == cols):
+            return None
+        watched.append(m.weight)
+    gamma = beta = None
+    if ln is not None:
+        weight, bias = ln.get_params()
+        if not weight.is_cuda or ops.grad_recording(weight, bias):
+            return None
+        gamma, beta = ln.kernel_params(weight, bias)
+    if ops.grad_recording(*watched):
+        return None
+    for m, ids in lookups:
+        if m is None:
+            args.append(ops.EmbedLookup(ids))
+        else:
+            table, scale, lo, hi = m.kernel_table()
+            args.append(ops.EmbedLookup(table, ids, scale, lo, hi))
+    _count(owner, "_fused_embed_calls")
+    return ops.embed_sum_quant(args, gamma, beta, ln.eps if ln is not None else 0.0, fq_sums=[q.fixed_spec() for q in sum_quantizers],
+                               fq_out=ln.out_spec() if ln is not None else None, dtype=dtype)
+
+
 def quantize_model(model: nn.Module, **quant_params) -> nn.Module:
     """The cases of the reference's recursive rewriter (autoquant_utils.py:236-270) that the attention classes and the block tails need:
-    nn.Linear (query/key/value, q_proj/k_proj/v_proj/out_proj, dense, fc2), nn.LayerNorm, and Sequential(Linear, ReLU) - OPT's fc1 with
-    its activation folded into the QuantLinear (quantized_opt.py:292-294)."""
+    nn.Linear (query/key/value, q_proj/k_proj/v_proj/out_proj, dense, fc2), nn.LayerNorm, nn.Embedding (the model fronts), and
+    Sequential(Linear, ReLU) - OPT's fc1 with its activation folded into the QuantLinear (quantized_opt.py:292-294)."""
     def copy_params(q, src, clone):
         q.weight.data = src.weight.data.clone() if clone else src.weight.data
         if getattr(src, "bias", None) is not None:
@@ -1026,13 +1144,17 @@ def quantize_model(model: nn.Module, **quant_params) -> nn.Module:
 
     if type(model) is nn.Linear:
         return copy_params(QuantLinear(model.in_features, model.out_features, bias=model.bias is not None, **quant_params), model, False)
+    if type(model) is nn.Embedding:
+        q = QuantEmbedding(model.num_embeddings, model.embedding_dim, padding_idx=model.padding_idx, max_norm=model.max_norm, norm_type=model.norm_type,
+                           scale_grad_by_freq=model.scale_grad_by_freq, sparse=model.sparse, **quant_params)
+        return copy_params(q, model, False)
     if type(model) is nn.LayerNorm and model.elementwise_affine:
         return copy_params(QuantLayerNorm(model.normalized_shape, eps=model.eps, **quant_params), model, False)
     if type(model) is nn.Sequential and len(model) == 2 and type(model[0]) is nn.Linear and isinstance(model[1], nn.ReLU):
         lin = model[0]
         q = QuantLinear(lin.in_features, lin.out_features, bias=lin.bias is not None, activation=model[1], **quant_params)
         return nn.Sequential(copy_params(q, lin, True))
-    raise NotImplementedError(f"quantize_model: {type(model).__name__} is outside the attention path and the block tails")
+    raise NotImplementedError(f"quantize_model: {type(model).__name__} is outside the attention path, the block tails and the embeddings")
 
 
 class QuantizedModel(nn.Module):
@@ -1711,6 +1833,120 @@ class QuantizedOPTDecoderLayer(QuantizedModel):
         return outputs
 
 
+# ------------------------------------------------------------------------------------------------------------
+# the model fronts: embeddings -> sums -> (LayerNorm)
+# ------------------------------------------------------------------------------------------------------------
+class QuantizedBertEmbeddings(QuantizedModel):
+    """quantized_bert.py:146-218: word + token type -> sum_input_token_type_embd_act_quantizer, += position ->
+    sum_pos_embd_act_quantizer, LayerNorm, dropout.  In eval with frozen ranges on the GPU: one launch (`embed_front`).  quant_dict["Et"]
+    selects the MSE golden-section range for the word table; the decomposed integer LayerNorm (quant_dict["layer_norm_embd"]) is refused."""
+
+    def __init__(self, org_model, **quant_params):
+        super().__init__()
+        self.quant_dict = DotDict(quant_params.get("quant_dict") or {})
+        if self.quant_dict.get("layer_norm_embd", False):
+            raise NotImplementedError("quant_dict['layer_norm_embd']: the decomposed LayerNorm is not implemented (only the fake-quantised nn.LayerNorm is)")
+        quant_params_ = dict(quant_params)
+        if "Et" in self.quant_dict:
+            quant_params_["weight_range_method"] = MSE_Estimator
+            quant_params_["weight_range_options"] = dict(opt_method=OptMethod.golden_section)
+        self.word_embeddings = quantize_model(org_model.word_embeddings, **quant_params_)
+        self.position_embeddings = quantize_model(org_model.position_embeddings, **quant_params)
+        self.token_type_embeddings = quantize_model(org_model.token_type_embeddings, **quant_params)
+        self.dropout = org_model.dropout
+        position_ids = org_model.position_ids
+        if position_ids is not None:
+            self.register_buffer("position_ids", position_ids)
+        else:
+            self.position_ids = position_ids
+        self.position_embedding_type = getattr(org_model, "position_embedding_type", "absolute")
+        self.sum_input_token_type_embd_act_quantizer = QuantizedActivation(**quant_params)
+        self.sum_pos_embd_act_quantizer = QuantizedActivation(**quant_params)
+        self.LayerNorm = quantize_model(org_model.LayerNorm, **quant_params)
+        self._fused_embed_calls = 0
+
+    def forward(self, input_ids=None, token_type_ids=None, position_ids=None, inputs_embeds=None):
+        input_shape = input_ids.size() if input_ids is not None else inputs_embeds.size()[:-1]
+        seq_length = input_shape[1]
+        if position_ids is None:
+            position_ids = self.position_ids[:, :seq_length]
+        if token_type_ids is None:
+            token_type_ids = torch.zeros(input_shape, dtype=torch.long, device=self.position_ids.device)
+        absolute = self.position_embedding_type == "absolute"
+        lookups = [(self.word_embeddings, input_ids) if inputs_embeds is None else (None, inputs_embeds), (self.token_type_embeddings, token_type_ids)]
+        quantizers = [self.sum_input_token_type_embd_act_quantizer]
+        if absolute:
+            lookups.append((self.position_embeddings, position_ids))
+            quantizers.append(self.sum_pos_embd_act_quantizer)
+        fused = embed_front(self, lookups, quantizers, self.LayerNorm)
+        if fused is not None:
+            return self.dropout(fused)
+        if inputs_embeds is None:
+            inputs_embeds = self.word_embeddings(input_ids)
+        embeddings = inputs_embeds + self.token_type_embeddings(token_type_ids)
+        embeddings = self.sum_input_token_type_embd_act_quantizer(embeddings)
+        if absolute:
+            embeddings = embeddings + self.position_embeddings(position_ids)
+            embeddings = self.sum_pos_embd_act_quantizer(embeddings)
+        embeddings = self.LayerNorm(embeddings)
+        return self.dropout(embeddings)
+
+
+class QuantizedOPTLearnedPositionalEmbedding(QuantizedModel):
+    """quantized_opt.py:27-51: the position table behind `offset`, positions counted along the attention mask."""
+
+    def __init__(self, org_model, **quant_params):
+        super().__init__()
+        self.offset = org_model.offset
+        self.quant_embedding = QuantEmbedding(org_model.num_embeddings, org_model.embedding_dim, padding_idx=org_model.padding_idx,
+                                              max_norm=org_model.max_norm, norm_type=org_model.norm_type,
+                                              scale_grad_by_freq=org_model.scale_grad_by_freq, sparse=org_model.sparse, **quant_params)
+        self.quant_embedding.weight.data = org_model.weight.data.clone()
+        self.quant_embedding.to(org_model.weight.device)
+        self._fused_embed_calls = 0
+
+    def position_ids(self, attention_mask, past_key_values_length: int = 0):
+        """The table rows of a (B, S_total) mask: cumsum(mask) * mask - 1 cut to the new tokens, + offset (a padded position reads row offset - 1)."""
+        attention_mask = attention_mask.long()
+        positions = (torch.cumsum(attention_mask, dim=1).type_as(attention_mask) * attention_mask).long() - 1
+        return positions[:, past_key_values_length:] + self.offset
+
+    def forward(self, attention_mask, past_key_values_length: int = 0):
+        return self.quant_embedding(self.position_ids(attention_mask, past_key_values_length))
+
+
+def opt_embed_front(embed_tokens, embed_positions, embed_sum_act_quantizer, input_ids, attention_mask, past_key_values_length=0, inputs_embeds=None,
+                    project_in=None):
+    """quantized_opt.py:549-569: embed_sum_act_quantizer(embed_tokens(input_ids) + embed_positions(attention_mask, past_key_values_length)),
+    the decoder's hidden states in front of its first layer.  One launch where `embed_front` applies (`embed_positions`._fused_embed_calls
+    counts them); the position ids come from the reference's cumsum rule in torch - the id tensor is tiny.  attention_mask None: all ones.
+    project_in (OPT-350m) sits between the lookup and the sum: the torch ops run."""
+    if inputs_embeds is None:
+        shape = input_ids.shape
+        input_ids = input_ids.view(-1, shape[-1])
+        B, S, dev = input_ids.shape[0], input_ids.shape[1], input_ids.device
+    else:
+        B, S, dev = inputs_embeds.shape[0], inputs_embeds.shape[1], inputs_embeds.device
+    if attention_mask is None:
+        attention_mask = torch.ones((B, S + past_key_values_length), dtype=torch.bool, device=dev)
+    if project_in is None:
+        pos = embed_positions.position_ids(attention_mask, past_key_values_length)
+        first = (embed_tokens, input_ids) if inputs_embeds is None else (None, inputs_embeds)
+        if not embed_positions.training and not has_hooks(embed_positions):
+            fused = embed_front(embed_positions, [first, (embed_positions.quant_embedding, pos)], [embed_sum_act_quantizer], None)
+            if fused is not None:
+                return fused
+    if inputs_embeds is None:
+        inputs_embeds = embed_tokens(input_ids)
+    pos_embeds = embed_positions(attention_mask, past_key_values_length)
+    if project_in is not None:
+        inputs_embeds = project_in(inputs_embeds)
+    return embed_sum_act_quantizer(inputs_embeds + pos_embeds)
+
+
+# The model fronts (QuantizedBertEmbeddings, opt_embed_front) as ONE launch of ops.embed_sum_quant where it applies; False: the separate ops
+# (F.embedding on the fake-quantised tables, torch add, ops.fake_quant, the LayerNorm) - tests compare the two.
+FUSED_EMBED = True
 # The block tails (QuantLayerNorm, QuantizedBert[Self]Output, QuantizedOPTDecoderLayer) as ONE launch of ops.resid_ln_quant where it
 # applies; False: the separate ops (torch add, ops.fake_quant, F.layer_norm, ops.fake_quant) - tests compare the two.
 FUSED_LN = True

@@ -248,6 +248,9 @@ int flash_mq(const oeh_attn_desc* d, bool pv2) {
   return (d->Sq > 64 && wg2 >= 416) ? 2 : 1;  // (H=12 S=512 causal: B=8 - 384 workgroups - 10.8 vs 12.4 us with one block per wave, B=9 - 432 - 13.3 vs 12.8, B=10 14.5 vs 12.7, B=12 16.2 vs 13.5)
 }
 
+// The any-shape kernel (oeh_attn_generic.hip): the query row and the score row in LDS as fp32
+bool generic_can(const oeh_attn_desc* d) { return (size_t)(d->D + d->Sk) * 4 <= 64 * 1024; }
+
 Variant pick_variant(const oeh_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const oeh_fq_desc* fq, bool out32) {
   if (d->dtype == OEH_I8) return i8_eligible(d, q, k, v, o, fq) ? V_I8 : V_NONE;
   const int eb = elem_bytes(d->dtype);
@@ -268,8 +271,8 @@ Variant pick_variant(const oeh_attn_desc* d, const void* q, const void* k, const
   // fp32 storage on the full-row kernel: clipped softmax, the INT8 chain, vanilla softmax with key padding (the in-kernel gate predictor: on
   // operand pairs here - fast_can refuses it together with fake-quant)
   if (shape_ok && p_exact && al && fast_can(d, fq, f32) && !prefer_general_d128(d, fq) && !(off & ((1 << V_FAST) | (f32 ? HOOK_NO_FAST_F32 : 0)))) return V_FAST;
-  if (shape_ok && p_exact && al) return V_MFMA;
-  if ((size_t)(d->D + d->Sk) * 4 <= 64 * 1024) return V_GENERIC;
+  if (shape_ok && p_exact && al && !(off & (1 << V_MFMA))) return V_MFMA;
+  if (generic_can(d) && !(off & (1 << V_GENERIC))) return V_GENERIC;
   return V_NONE;
 }
 
@@ -348,7 +351,7 @@ AttnPlan plan_attn(const oeh_attn_desc* d, const oeh_attn_opts* opts, const void
   // the any-shape kernel (fp32 FMA); the one-pass and full-row kernels run their PV2 forms, the small-shape kernel is fp32-exact as it is.
   pl.out32 = (d->dtype == OEH_F16 || d->dtype == OEH_BF16) && d->o_dtype == OEH_F32;
   pl.var = pick_variant(d, q, k, v, o, fq, pl.out32);
-  if (pl.pv2 && pl.var == V_MFMA) pl.var = (size_t)(d->D + d->Sk) * 4 <= 64 * 1024 ? V_GENERIC : V_NONE;
+  if (pl.pv2 && pl.var == V_MFMA) pl.var = (generic_can(d) && !(g_hooks.off & (1 << V_GENERIC))) ? V_GENERIC : V_NONE;
   if (pl.var == V_NONE) { pl.rc = OEH_ENOTSUP; return pl; }
   const bool matrix16 = pl.var == V_FLASH || pl.var == V_FAST;
   pl.src32 = (d->dtype == OEH_F32 && matrix16) ? (pl.pv2 ? 2 : 1) : 0;

@@ -56,10 +56,11 @@ def causal_mask(Sq: int, Sk: int, mask_min: float):
 
 
 def attn64(q, k, v=None, *, scale=1.0, scale_div=0.0, scores_range=None, probs_range=None, n_bits=8, eps=1e-8, pad=None, full=None,
-           causal=False, clamp_min=False, mask_min=FMIN32, base=1, clip=None):
+           causal=False, clamp_min=False, mask_min=FMIN32, base=1, clip=None, scores_grid=None, probs_grid=None):
     """The contract's chain in float64, in its order: q k^T; / scale_div or else * scale; [score fake-quant]; + pad; + full; + causal
     (Sk - Sq offset); [max(., mask_min)]; softmax (base 0 / 1); [clamp(p (eta - gamma) + gamma, 0, 1)]; [probability fake-quant]; P V.
     Scalars the kernel receives as float32 (scale, scale_div, mask_min, gamma, eta - gamma) enter as those float32 values.
+    scores_grid / probs_grid: a quantiser given as its grid (scale, zero_point, qmax) instead of a range (tests/_attn_ref.py).
     Returns a dict: "scores" (scaled, before quantiser and masks - what CALIB_SCORES measures), "probs" (after the clip, before the
     probability quantiser - what CALIB_PROBS measures), "probs_q" (what multiplies V) and "ctx" (None without v)."""
     q, k = np.asarray(q, dtype=np.float64), np.asarray(k, dtype=np.float64)
@@ -70,7 +71,11 @@ def attn64(q, k, v=None, *, scale=1.0, scale_div=0.0, scores_range=None, probs_r
     elif scale != 1.0:
         s = s * float(np.float32(scale))
     out = {"scores": s}
-    x = s if scores_range is None else fake_quant64(s, *grid_from_range(scores_range[0], scores_range[1], n_bits, eps))
+    if scores_grid is None and scores_range is not None:
+        scores_grid = grid_from_range(scores_range[0], scores_range[1], n_bits, eps)
+    if probs_grid is None and probs_range is not None:
+        probs_grid = grid_from_range(probs_range[0], probs_range[1], n_bits, eps)
+    x = s if scores_grid is None else fake_quant64(s, *scores_grid)
     mmin = float(np.float32(mask_min))
     if pad is not None:
         x = x + np.asarray(pad, dtype=np.float64)[:, None, None, :]
@@ -91,7 +96,7 @@ def attn64(q, k, v=None, *, scale=1.0, scale_div=0.0, scores_range=None, probs_r
         gamma, eta = clip
         p = np.clip(p * float(np.float32(float(eta) - float(gamma))) + float(np.float32(gamma)), 0.0, 1.0)
     out["probs"] = p
-    pq = p if probs_range is None else fake_quant64(p, *grid_from_range(probs_range[0], probs_range[1], n_bits, eps))
+    pq = p if probs_grid is None else fake_quant64(p, *probs_grid)
     out["probs_q"] = pq
     out["ctx"] = None if v is None else np.matmul(pq, np.asarray(v, dtype=np.float64))
     return out

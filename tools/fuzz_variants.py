@@ -4,7 +4,8 @@ fused INT8 chain - through `ops.attn_fwd` as the library picks the kernel, again
 row, fp32 FMAs; forced through include/oeh_debug.h) on the same inputs.  Prints every disagreement with the parameters that
 reproduce it and a summary per variant.  (Known harmless report: the INT8 chain on rows WITHOUT a visible key under the vanilla softmax
 when 255 / Sk is a half-integer - Sk = 170: the uniform probability sits exactly on a rounding boundary of its quantiser and the two
-kernels' arithmetic legitimately lands on different sides for every such row.)   usage: python tools/fuzz_variants.py [seconds=120] [seed=0]"""
+kernels' arithmetic legitimately lands on different sides for every such row.)  GENERIC_ONLY's bit 3 (the general kernel off) is read by
+the library since the fallback-kernel tests: before, shapes of up to 512 keys were compared with the general kernel.   usage: python tools/fuzz_variants.py [seconds=120] [seed=0]"""
 import collections
 import ctypes as C
 import os

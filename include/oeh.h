@@ -610,6 +610,54 @@ int oeh_embed_sum_quant(const oeh_embed_desc* d, const float* gamma /* may be NU
                         void* y, uint8_t* sum_idx /* tests */, uint8_t* y_idx /* tests */, int32_t* bad_rows /* may be NULL */, void* stream);
 const char* oeh_embed_sum_variant(const oeh_embed_desc* d);  /* which launch form for d's pointers and strides, or NULL if refused; host only */
 
+/* Cross-entropy over a vocabulary (oeh_xent.hip): the loss both language models end in - CrossEntropyLoss on the shifted logits
+ * (quantized_opt.py:868-877), on -100 labels (quantized_bert.py:910-915), exp(mean of the batch losses) as perplexity (validate_clm.py:
+ * 556-594), label_smoothing (run_vit.py) - with every logit read ONCE forward, and read once and written once backward.
+ * logits: a (B, S, V) view, element (b, s, j) at logits[b * x_stride[0] + s * x_stride[1] + j]; labels: a (B, S) view of int32 or int64
+ * with label_stride.  The reference's shift is logits as they are with S - 1 rows per batch and labels + 1: no copy.  A row may start at
+ * any element; it is read with 16-byte loads on its own 16-byte boundaries, and nothing outside [row, row + V) is read except inside the
+ * 16-byte slots that hold the row's first and last element.
+ * Forward, per row with label y (fp32 arithmetic, bitwise reproducible, a fixed order of every sum):
+ *   lse = M + log(L),  M = max_j x_j,  L = sum_j exp(x_j - M) by an online (max, sum) per thread, merged over the workgroup
+ *   row_loss = lse - x_y                                              one fp32 subtraction
+ *   label_smoothing = e > 0:  row_loss = (1 - e) * (lse - x_y) + e * (lse - sum_j x_j / V)       torch's definition
+ *   y == ignore_index: no logit is read, lse = row_loss = 0, the row is not counted
+ *   y outside [0, V) otherwise (found before any address is formed): lse = row_loss = NaN, the row IS counted
+ * then ONE more launch of one workgroup: out2[0] = the float64 sum of the counted rows' fp32 losses, out2[1] = their number,
+ * *mean = fp32(out2[0] / out2[1]) (NaN without a counted row, as torch), meter (if given; a device double[2] the caller zeroes once):
+ * meter[0] += out2[0] / out2[1]; meter[1] += 1 - what validate_clm.py:561-591 accumulates on the host, so that a validation run needs
+ * one device-to-host copy at its end; *bad_rows (if given; a device int32 the caller zeroes) += the number of rows with a label that
+ * is none.  lse and row_loss: B * S fp32 values, row b * S + s.  row_loss may be NULL without label smoothing: the reduce launch then
+ * forms lse - x_y itself (the same bits).  No atomics, no allocation, no host synchronisation.  B * S == 0: the reduce launch alone
+ * (sum 0, count 0, mean NaN).
+ * Backward, per element:  dlogits[j] = RN_dtype((exp(x_j - lse) - (1 - e) * [j == y] - e / V) * g), each operation rounded on its own,
+ * the third term only with smoothing; g = grad[row * grad_stride] (fp32, read on the device; grad_stride == 0 broadcasts one scalar),
+ * with mean_reduction != 0 g = fp32(g / out2[1]).  lse and out2 are the forward's.  An ignored row is written as zeros without reading
+ * its logits, a row with a label that is none as NaN.  dlogits has the logits' dtype and dx_stride; it may BE logits (the same pointer and
+ * strides: every thread reads its elements before it writes them), otherwise the two must not overlap.  Stores are 16 bytes wide when
+ * every dlogits row sits as far from a 16-byte boundary as its logits row, else per element (variant name ends in "/el").
+ * oeh_xent_variant: "xent/block/CH4/f16", "xent/block/CH4/f32/ls", "xent/block/CH4/bf16/ls/el" - one 256-thread workgroup per row, CH
+ * (= OEH_XENT_SLOTS) 16-byte slots per thread and loop step, i.e. 256 * CH * (4 fp32 | 8 16-bit) elements per step; "/el" only with
+ * dlogits given.  Host only, NULL if refused, thread-local storage.
+ * Refusals, before any launch, in this order: OEH_EINVAL - d, logits, labels, lse or out2 NULL (backward: grad or dlogits too), row_loss
+ * NULL with label smoothing, V < 1, B or S < 0, a dtype other than OEH_F16 / OEH_BF16 / OEH_F32, a label_dtype that is none, a negative
+ * stride, a dx_stride below V with more than one row along it (backward), label_smoothing outside [0, 1) or NaN, reserved != 0;
+ * OEH_ENOTSUP - B * S >= 2^31; OEH_EALIGN - logits or dlogits off their element size, labels off theirs, lse / row_loss / mean / grad /
+ * bad_rows off 4 bytes, out2 / meter off 8 bytes. */
+#define OEH_XENT_SLOTS 4
+typedef struct oeh_xent_desc {
+  int32_t B, S, V, dtype;              /* OEH_F16 | OEH_BF16 | OEH_F32: logits and dlogits */
+  int32_t label_dtype, mean_reduction; /* OEH_ID_I32 | OEH_ID_I64;  backward: divide grad by out2[1] */
+  int64_t x_stride[2], label_stride[2], dx_stride[2];   /* elements: batch, row */
+  int64_t ignore_index;
+  float label_smoothing; int32_t reserved;
+} oeh_xent_desc;
+int oeh_xent_fwd(const oeh_xent_desc* d, const void* logits, const void* labels, float* lse, float* row_loss /* may be NULL */,
+                 double* out2, float* mean /* may be NULL */, double* meter /* may be NULL */, int32_t* bad_rows /* may be NULL */, void* stream);
+int oeh_xent_bwd(const oeh_xent_desc* d, const void* logits, const void* labels, const float* lse, const double* out2,
+                 const float* grad, int64_t grad_stride, void* dlogits, void* stream);
+const char* oeh_xent_variant(const oeh_xent_desc* d, const void* logits, const void* dlogits /* may be NULL */);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -103,6 +103,16 @@ class oeh_embed_desc(C.Structure):
                 ("tab", oeh_embed_lookup * 3), ("fq_sum", oeh_fq * 3), ("fq_out", oeh_fq)]
 
 
+XENT_SLOTS = 4  # include/oeh.h: OEH_XENT_SLOTS
+
+
+class oeh_xent_desc(C.Structure):
+    """include/oeh.h: the rows of oeh_xent_fwd / oeh_xent_bwd (cross-entropy over (B, S, V) logits and (B, S) labels, both by strides)."""
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("label_dtype", C.c_int32), ("mean_reduction", C.c_int32),
+                ("x_stride", C.c_int64 * 2), ("label_stride", C.c_int64 * 2), ("dx_stride", C.c_int64 * 2), ("ignore_index", C.c_int64),
+                ("label_smoothing", C.c_float), ("reserved", C.c_int32)]
+
+
 # every symbol include/oeh.h declares (tests/test_abi.py checks the .so exports exactly these)
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
@@ -114,6 +124,7 @@ EXPORTS = (
     "oeh_outlier_stats_work_bytes", "oeh_outlier_stats",
     "oeh_quant_mse_work_bytes", "oeh_quant_mse",
     "oeh_resid_ln_quant", "oeh_resid_ln_variant",
+    "oeh_xent_fwd", "oeh_xent_bwd", "oeh_xent_variant",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
@@ -212,6 +223,12 @@ def load() -> C.CDLL:
     lib.oeh_embed_sum_quant.restype = C.c_int
     lib.oeh_embed_sum_variant.argtypes = [C.POINTER(oeh_embed_desc)]
     lib.oeh_embed_sum_variant.restype = C.c_char_p
+    lib.oeh_xent_fwd.argtypes = [C.POINTER(oeh_xent_desc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_xent_fwd.restype = C.c_int
+    lib.oeh_xent_bwd.argtypes = [C.POINTER(oeh_xent_desc), vp, vp, vp, vp, vp, i64, vp, vp]
+    lib.oeh_xent_bwd.restype = C.c_int
+    lib.oeh_xent_variant.argtypes = [C.POINTER(oeh_xent_desc), vp, vp]
+    lib.oeh_xent_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -593,6 +593,71 @@ const char* oeh_embed_sum_variant(const oeh_embed_desc* d) {
   return name;
 }
 
+// oeh_xent_fwd / oeh_xent_bwd / oeh_xent_variant: every refusal in the order OEH_EINVAL -> OEH_ENOTSUP -> OEH_EALIGN.  bwd: dx_stride is looked at.
+static int xent_check(const oeh_xent_desc* d, const void* logits, const void* labels, bool bwd) {
+  if (d == nullptr || logits == nullptr || labels == nullptr || d->V < 1 || d->B < 0 || d->S < 0 || !dtype_ok(d->dtype)) return OEH_EINVAL;
+  if (d->label_dtype != OEH_ID_I32 && d->label_dtype != OEH_ID_I64) return OEH_EINVAL;
+  for (int i = 0; i < 2; ++i) {
+    if (d->x_stride[i] < 0 || d->label_stride[i] < 0 || (bwd && d->dx_stride[i] < 0)) return OEH_EINVAL;
+  }
+  if (bwd && ((d->S > 1 && d->dx_stride[1] < d->V) || (d->B > 1 && d->dx_stride[0] < d->V))) return OEH_EINVAL;
+  if (!(d->label_smoothing >= 0.0f && d->label_smoothing < 1.0f) || d->reserved != 0) return OEH_EINVAL;
+  if ((int64_t)d->B * d->S >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
+  if (addr(logits) % elem_bytes(d->dtype) != 0 || addr(labels) % (d->label_dtype == OEH_ID_I64 ? 8 : 4) != 0) return OEH_EALIGN;
+  return OEH_OK;
+}
+static oeh::XentArgs xent_args(const oeh_xent_desc* d, const void* logits, const void* labels) {
+  oeh::XentArgs a = {};
+  a.x = logits; a.labels = labels;
+  a.x_sb = d->x_stride[0]; a.x_ss = d->x_stride[1]; a.l_sb = d->label_stride[0]; a.l_ss = d->label_stride[1];
+  a.dx_sb = d->dx_stride[0]; a.dx_ss = d->dx_stride[1];
+  a.ignore_index = d->ignore_index; a.rows = (long)d->B * d->S;
+  a.S = d->S; a.V = d->V; a.in = d->dtype; a.label64 = d->label_dtype == OEH_ID_I64; a.mean_reduction = d->mean_reduction != 0;
+  a.eps_ls = d->label_smoothing;
+  return a;
+}
+// whether the gradient rows take element stores: a dlogits row that is not as far from a 16-byte boundary as its logits row
+static bool xent_el(const oeh_xent_desc* d, const void* logits, const void* dlogits) {
+  const int64_t eb = elem_bytes(d->dtype);
+  bool same = (addr(logits) - addr(dlogits)) % 16 == 0;
+  if (d->B > 1) same = same && ((d->x_stride[0] - d->dx_stride[0]) * eb) % 16 == 0;
+  if (d->S > 1) same = same && ((d->x_stride[1] - d->dx_stride[1]) * eb) % 16 == 0;
+  return !same;
+}
+
+int oeh_xent_fwd(const oeh_xent_desc* d, const void* logits, const void* labels, float* lse, float* row_loss, double* out2, float* mean,
+                 double* meter, int32_t* bad_rows, void* stream) {
+  if (lse == nullptr || out2 == nullptr) return OEH_EINVAL;
+  if (d != nullptr && row_loss == nullptr && d->label_smoothing > 0.0f) return OEH_EINVAL;
+  const int rc = xent_check(d, logits, labels, false);
+  if (rc != OEH_OK) return rc;
+  if ((addr(lse) | addr(row_loss) | addr(mean) | addr(bad_rows)) % 4 != 0 || (addr(out2) | addr(meter)) % 8 != 0) return OEH_EALIGN;
+  oeh::XentArgs a = xent_args(d, logits, labels);
+  a.lse = lse; a.row_loss = row_loss; a.out2 = out2; a.mean = mean; a.meter = meter; a.bad_rows = bad_rows;
+  return oeh::launch_xent_fwd(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_xent_bwd(const oeh_xent_desc* d, const void* logits, const void* labels, const float* lse, const double* out2, const float* grad,
+                 int64_t grad_stride, void* dlogits, void* stream) {
+  if (lse == nullptr || out2 == nullptr || grad == nullptr || dlogits == nullptr || grad_stride < 0) return OEH_EINVAL;
+  const int rc = xent_check(d, logits, labels, true);
+  if (rc != OEH_OK) return rc;
+  if ((addr(lse) | addr(grad)) % 4 != 0 || addr(out2) % 8 != 0 || addr(dlogits) % elem_bytes(d->dtype) != 0) return OEH_EALIGN;
+  oeh::XentArgs a = xent_args(d, logits, labels);
+  a.lse = const_cast<float*>(lse); a.out2 = const_cast<double*>(out2); a.grad = grad; a.grad_stride = grad_stride; a.dx = dlogits;
+  return oeh::launch_xent_bwd(a, xent_el(d, logits, dlogits), reinterpret_cast<hipStream_t>(stream));
+}
+
+const char* oeh_xent_variant(const oeh_xent_desc* d, const void* logits, const void* dlogits) {
+  static thread_local char name[48];
+  const void* const aligned = reinterpret_cast<const void*>((uintptr_t)4096);  // (the labels are taken as given and aligned)
+  if (xent_check(d, logits, aligned, dlogits != nullptr) != OEH_OK) return nullptr;
+  if (dlogits != nullptr && addr(dlogits) % elem_bytes(d->dtype) != 0) return nullptr;
+  std::snprintf(name, sizeof name, "xent/block/CH%d/%s%s%s", OEH_XENT_SLOTS, d->dtype == OEH_F32 ? "f32" : d->dtype == OEH_BF16 ? "bf16" : "f16",
+                d->label_smoothing > 0.0f ? "/ls" : "", dlogits != nullptr && xent_el(d, logits, dlogits) ? "/el" : "");
+  return name;
+}
+
 int oeh_gate_fwd(const void* hidden, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t d, int64_t hidden_stride_b,
                  int64_t hidden_stride_t, const float* w1, const float* b1, const float* w2, const float* b2, int32_t hidden_units,
                  int32_t per_head_pool, float scaling, float* gate_out, void* stream) {

@@ -115,6 +115,23 @@ struct EmbedArgs {
   FqP fq_out;
 };
 int launch_embed(const EmbedArgs& a, int in, int n_tab, LnPlan pl, hipStream_t st);
+// oeh_xent.hip: cross-entropy rows over (B, S, V) logits - forward + reduce, backward (include/oeh.h: oeh_xent_fwd, oeh_xent_bwd)
+struct XentArgs {
+  const void *x, *labels;
+  float *lse, *row_loss;  // row_loss may be null (without label smoothing)
+  double* out2;           // {sum, count}: written by the reduce launch, read by the backward with mean_reduction
+  float* mean;            // may be null
+  double* meter;          // may be null
+  int* bad_rows;          // may be null
+  const float* grad;      // backward only
+  void* dx;               // backward only
+  long x_sb, x_ss, l_sb, l_ss, dx_sb, dx_ss, grad_stride;  // elements
+  long ignore_index, rows;
+  int S, V, in, label64, mean_reduction;
+  float eps_ls;           // label smoothing
+};
+int launch_xent_fwd(const XentArgs& a, hipStream_t st);
+int launch_xent_bwd(const XentArgs& a, bool el, hipStream_t st);
 // oeh_stats.hip, oeh_qmse.hip
 long stats_chunks(long cols);
 int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,

@@ -1090,6 +1090,135 @@ def embed_sum_variant(B: int, S: int, cols: int, dtype=torch.float32, *, n_tab: 
     return None if r is None else r.decode()
 
 
+# ---- cross-entropy over a vocabulary (include/oeh.h: oeh_xent_fwd / oeh_xent_bwd): loss and logit gradient from one pass each
+
+XENT_SLOTS = _lib.XENT_SLOTS  # 16-byte slots per thread and loop step: a step covers 256 * XENT_SLOTS * (4 fp32 | 8 16-bit) elements
+XENT_CALLS = 0  # launches of `xent_fwd` (losses.FUSED_XENT)
+_ID_DT = {torch.int32: _lib.OEH_ID_I32, torch.int64: _lib.OEH_ID_I64}
+
+
+def _xent_views(logits: torch.Tensor, labels: torch.Tensor):
+    """(B, S, V) logits and (B, S) labels as the kernel addresses them: 1-d logits are one row, 2-d ones (1, N, V), more than three
+    dimensions fold their leading ones into B.  A view is passed as it is, by its strides (the last dimension contiguous); what has no
+    such strides is copied."""
+    _need_dtype(logits)
+    if labels.dtype not in _ID_DT:
+        raise ValueError(f"labels must be int32 or int64, got {labels.dtype}")
+    if logits.dim() < 1 or tuple(labels.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"labels {tuple(labels.shape)} must have the logits' leading dimensions {tuple(logits.shape[:-1])}")
+    V = logits.shape[-1]
+    x = logits.detach()
+    y = labels.detach()
+    if x.dim() == 1:
+        x, y = x[None, None], y[None, None]
+    elif x.dim() == 2:
+        x, y = x[None], y[None]
+    elif x.dim() > 3:
+        x, y = x.reshape(-1, x.shape[-2], V), y.reshape(-1, y.shape[-1])
+    if V > 1 and x.stride(2) != 1:
+        x = x.contiguous()
+    return x, y
+
+
+def _xent_desc(x: torch.Tensor, y: torch.Tensor, dx: Optional[torch.Tensor], ignore_index: int, label_smoothing: float, mean_reduction: bool = False):
+    d = _lib.oeh_xent_desc()
+    d.B, d.S, d.V, d.dtype = x.shape[0], x.shape[1], x.shape[2], _DT[x.dtype]
+    d.label_dtype, d.mean_reduction = _ID_DT[y.dtype], int(bool(mean_reduction))
+    d.x_stride[0], d.x_stride[1] = x.stride(0), x.stride(1)
+    d.label_stride[0], d.label_stride[1] = y.stride(0), y.stride(1)
+    if dx is not None:
+        d.dx_stride[0], d.dx_stride[1] = dx.stride(0), dx.stride(1)
+    d.ignore_index, d.label_smoothing = int(ignore_index), float(label_smoothing)
+    return d
+
+
+def xent_fwd(logits: torch.Tensor, labels: torch.Tensor, *, ignore_index: int = -100, label_smoothing: float = 0.0, want_rows: bool = False,
+             meter: Optional[torch.Tensor] = None, bad_rows: Optional[torch.Tensor] = None):
+    """Cross-entropy of `logits` (..., V) against integer `labels` (...) in one pass over the logits, which may be any view with a
+    contiguous last dimension (`include/oeh.h: oeh_xent_fwd`).  Returns (mean, out2, lse, row_loss | None): the fp32 mean over the rows
+    whose label is not `ignore_index` (NaN without one), a float64 {sum, count}, the rows' fp32 logsumexp and (want_rows, or with label
+    smoothing) their fp32 losses, both flat.  meter: float64[2] on the same GPU, {sum of the means, calls}; bad_rows: int32[1] that counts
+    the rows whose label is neither a class nor ignore_index (their loss is NaN).  Nothing synchronises."""
+    global XENT_CALLS
+    dev = _need_gpu(logits, labels, meter, bad_rows)
+    x, y = _xent_views(logits, labels)
+    rows = x.shape[0] * x.shape[1]
+    if meter is not None:
+        _need_f64(meter, 2, "meter must be a contiguous float64 tensor of 2 elements")
+    if bad_rows is not None and (bad_rows.dtype != torch.int32 or bad_rows.numel() != 1):
+        raise ValueError("bad_rows must be one int32")
+    lse = torch.empty(rows, dtype=torch.float32, device=x.device)
+    row_loss = torch.empty(rows, dtype=torch.float32, device=x.device) if want_rows or label_smoothing > 0.0 else None
+    out2 = torch.empty(2, dtype=torch.float64, device=x.device)
+    mean = torch.empty((), dtype=torch.float32, device=x.device)
+    d = _xent_desc(x, y, None, ignore_index, label_smoothing)
+    one = C.c_void_p(x.element_size() * 8)  # (an empty tensor has no address to hand over; nothing is read through this one)
+    with _on_device(dev):
+        rc = _lib.load().oeh_xent_fwd(C.byref(d), _ptr(x) if rows else one, _ptr(y) if rows else one, _ptr(lse) if rows else one,
+                                      _ptr(row_loss) if rows or row_loss is None else one, _ptr(out2), _ptr(mean), _ptr(meter), _ptr(bad_rows), _stream())
+    _lib.check(rc, "oeh_xent_fwd")
+    XENT_CALLS += 1
+    return mean, out2, lse, row_loss
+
+
+def xent_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, out2: torch.Tensor, grad: torch.Tensor, *, ignore_index: int = -100,
+             label_smoothing: float = 0.0, mean_reduction: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The logit gradient of `xent_fwd` in one read and one write (`include/oeh.h: oeh_xent_bwd`): (softmax - smoothed one-hot) * g per
+    row, g = `grad` - one fp32 value on the device, or one per row - divided by the forward's count with mean_reduction.  lse, out2: the
+    forward's.  out: where to write, a tensor of the logits' shape and dtype with a contiguous last dimension; it may be `logits` itself."""
+    dev = _need_gpu(logits, labels, lse, out2, grad, out)
+    x, y = _xent_views(logits, labels)
+    rows = x.shape[0] * x.shape[1]
+    _need_f64(out2, 2, "out2 must be the forward's float64 {sum, count}")
+    if lse.dtype != torch.float32 or lse.numel() != rows or not lse.is_contiguous():
+        raise ValueError("lse must be the forward's: one contiguous fp32 value per row")
+    g = grad.detach()
+    if g.dtype != torch.float32 or g.numel() not in (1, rows) or not g.is_contiguous():
+        raise ValueError("grad must be a contiguous fp32 tensor of one element, or of one per row")
+    if out is None:
+        out = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+    elif tuple(out.shape) != tuple(logits.shape) or out.dtype != logits.dtype:
+        raise ValueError("out must have the logits' shape and dtype")
+    dx = out.detach()
+    dx = dx[None, None] if dx.dim() == 1 else dx[None] if dx.dim() == 2 else dx
+    if dx.dim() > 3:
+        try:
+            dx = dx.view(-1, dx.shape[-2], dx.shape[-1])  # (a view or nothing: the result must land in `out`)
+        except RuntimeError:
+            raise ValueError("out of more than three dimensions needs leading dimensions that fold into one") from None
+    if tuple(dx.shape) != tuple(x.shape) or (x.shape[2] > 1 and dx.stride(2) != 1):
+        raise ValueError("out needs a contiguous last dimension")
+    if rows:
+        d = _xent_desc(x, y, dx, ignore_index, label_smoothing, mean_reduction)
+        with _on_device(dev):
+            rc = _lib.load().oeh_xent_bwd(C.byref(d), _ptr(x), _ptr(y), _ptr(lse), _ptr(out2), _ptr(g), 0 if g.numel() == 1 else 1, _ptr(dx), _stream())
+        _lib.check(rc, "oeh_xent_bwd")
+    return out
+
+
+def xent_variant(B: int, S: int, V: int, dtype=torch.float16, *, label_smoothing: float = 0.0, row_stride: Optional[int] = None, offset: int = 0,
+                 dx_row_stride: Optional[int] = None, dx_offset: Optional[int] = None) -> Optional[str]:
+    """Name of the launch form for (B, S, V) logits of `dtype` whose rows are `row_stride` (default V) elements apart and start `offset`
+    elements behind a 16-byte boundary ("xent/block/CH4/f16", ".../ls" with smoothing), or None if refused.  With dx_offset (and
+    dx_row_stride) the backward's form for a gradient tensor placed like that: ".../el" when its rows take element stores.  Host only."""
+    if dtype not in _DT:
+        return None
+    eb = 4 if dtype == torch.float32 else 2
+    st = V if row_stride is None else int(row_stride)
+    d = _lib.oeh_xent_desc()
+    d.B, d.S, d.V, d.dtype, d.label_dtype = int(B), int(S), int(V), _DT[dtype], _lib.OEH_ID_I64
+    d.x_stride[0], d.x_stride[1] = st * int(S), st
+    d.label_stride[0], d.label_stride[1] = int(S), 1
+    d.label_smoothing = float(label_smoothing)
+    dxp = None
+    if dx_offset is not None:
+        dst = V if dx_row_stride is None else int(dx_row_stride)
+        d.dx_stride[0], d.dx_stride[1] = dst * int(S), dst
+        dxp = C.c_void_p((1 << 20) + int(dx_offset) * eb)
+    r = _lib.load().oeh_xent_variant(C.byref(d), C.c_void_p(4096 + int(offset) * eb), dxp)
+    return None if r is None else r.decode()
+
+
 _calib_work = {}  # (device index, stream handle) -> the 36-KB histograms of that stream's on-device percentile selection
 
 

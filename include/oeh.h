@@ -658,6 +658,60 @@ int oeh_xent_bwd(const oeh_xent_desc* d, const void* logits, const void* labels,
                  const float* grad, int64_t grad_stride, void* dlogits, void* stream);
 const char* oeh_xent_variant(const oeh_xent_desc* d, const void* logits, const void* dlogits /* may be NULL */);
 
+/* The tail of a transformer block in training (oeh_ln_train.hip): dropout -> residual add -> LayerNorm on the rows of a (rows, cols)
+ * array, forward in ONE pass and backward in one pass plus a column reduction - dense -> dropout -> + input -> LayerNorm of BertSelfOutput
+ * / BertOutput (the fp32 shape of quantized_bert.py:541-606) and residual + dropout(h) in front of the next LayerNorm of the OPT decoder
+ * layer (quantized_opt.py:277-384), whose residual stream is sum_out.
+ * Every row tensor has `dtype` and contiguous columns; element (i, j) sits at base[i * stride + j].  The descriptor's strides belong to
+ * x, r, sum_out, y in the forward and to dx, dr, s, dy (and dsum_stride to dsum) in the backward.  gamma, beta, mean, rstd, dgamma, dbeta: fp32.
+ * Forward, per element (i, j), every operation rounded on its own, in this order:
+ *   d = keep(i, j) ? fp32(x) * inv : 0        inv = 1 / (1 - p), formed once in fp32; p == 0: d = fp32(x), no generator work
+ *   s = RN_dtype(d + fp32(r))                 one rounding to the storage type; r == NULL: s = RN_dtype(d)
+ *   sum_out <- s                              required: the backward reads it, and pre-LN blocks carry it on as the residual stream
+ *   y = ((s - mean) * rstd) * gamma + beta from the stored s exactly as oeh_resid_ln_quant defines it without quantisers (its fp32 moments,
+ *   the same summation order per launch form: with p == 0 the two entry points give the same bits)
+ *   mean[i], rstd[i] <- the row's mean and 1 / sqrt(var + eps) formed in float64 and rounded to fp32 once: what the backward reads
+ * Keep bit: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32), counter (j >> 2, i & 0xffffffff, i >> 32, 1), output word j & 3:
+ * kept iff word >= floor(p * 2^32).  The fourth counter word is 1 where attention dropout's is 0 (oeh_dropout): one seed serves both
+ * without a shared stream.  The mask depends on (seed, i, j) only - not on the launch form, not on strides.
+ * oeh_drop_resid_ln_mask: the dense (rows, cols) keep mask (1 kept, 0 dropped) of d's rows, cols and drop from the same generator.
+ * Backward, from the forward's s, mean, rstd and drop, per row in fp32:
+ *   xhat = (s - mean) * rstd;  g = dy * gamma;  c1 = sum(g) / cols;  c2 = sum(g * xhat) / cols
+ *   ds = rstd * ((g - c1) - xhat * c2);  dsum given (the gradient that arrived on sum_out): ds = ds + fp32(dsum)
+ *   dr (if given) <- RN_dtype(ds);  dx <- RN_dtype(keep(i, j) ? ds * inv : 0)
+ *   dgamma[j] = sum_i dy * xhat;  dbeta[j] (if given) = sum_i dy        both summed in float64 and rounded once to fp32, with xhat for
+ *   THESE sums from a mean and rstd = 1 / sqrt(var + eps) the kernel forms again from s in float64 (eps: the forward's): an entry that one
+ *   row dominates would otherwise carry the rounding of that row's fp32 rstd
+ * Two kernels, no atomics, bitwise reproducible: the row kernel runs at most OEH_LN_TRAIN_MAX_GROUPS workgroups (two per CU), each of which -
+ * in the one-wave-per-row form each of its four waves - walks a contiguous slab of rows with its columns' two sums in registers and leaves
+ * one (2, cols) float64 partial in `work`; the column kernel adds the partials in a fixed order.  work: oeh_drop_resid_ln_bwd_work_bytes(d)
+ * bytes (a multiple of 16; 0 for a refused descriptor), 8-byte aligned, the caller's, not shared between streams.
+ * Aliasing: sum_out may be r, y may be x, dx may be dy, dr may be dsum - each pair with equal row strides; anything else must not overlap.
+ * Launch forms: those of oeh_resid_ln_quant, with its alignment rule over every given row tensor, gamma, beta (and the backward's work).
+ * oeh_drop_resid_ln_variant: "ln_train/fwd/wave/CH2/f16/drop", "ln_train/bwd/block/CH8/f32/G512x2" (backward: workgroups x rows per
+ * slab); host only, NULL if refused, thread-local storage; it takes every optional tensor as given and 16-byte aligned.
+ * Refusals, before any launch: OEH_EINVAL - p outside [0, 1) or NaN or drop.reserved != 0 (checked first), then d or a required pointer
+ * NULL (forward: x, gamma, sum_out, y, mean, rstd; backward: dy, s, gamma, mean, rstd, dx, dgamma, work), cols < 1, rows < 0, a dtype other
+ * than OEH_F16 / OEH_BF16 / OEH_F32, eps < 0 or NaN, reserved != 0, a negative stride, a stride of an output (sum_out, y; dx, dr) below
+ * cols with rows > 1; OEH_ENOTSUP - cols > 8192, rows >= 2^31.  rows == 0: OEH_OK without a launch; the backward still zeroes dgamma and
+ * dbeta. */
+#define OEH_LN_TRAIN_MAX_GROUPS 512
+typedef struct oeh_ln_train_desc {
+  int64_t rows; int32_t cols; int32_t dtype;           /* OEH_F16 | OEH_BF16 | OEH_F32 */
+  int64_t x_stride, r_stride, sum_stride, y_stride;    /* forward: x, r, sum_out, y;  backward: dx, dr, s, dy */
+  int64_t dsum_stride;                                 /* backward only */
+  float eps; int32_t reserved;
+  oeh_dropout drop;                                    /* p == 0: no dropout */
+} oeh_ln_train_desc;
+int oeh_drop_resid_ln_fwd(const oeh_ln_train_desc* d, const void* x, const void* r /* may be NULL */, const float* gamma, const float* beta /* may be NULL */,
+                          void* sum_out, void* y, float* mean, float* rstd, void* stream);
+size_t oeh_drop_resid_ln_bwd_work_bytes(const oeh_ln_train_desc* d);
+int oeh_drop_resid_ln_bwd(const oeh_ln_train_desc* d, const void* dy, const void* dsum /* may be NULL */, const void* s, const float* gamma,
+                          const float* mean, const float* rstd, void* dx, void* dr /* may be NULL */, float* dgamma, float* dbeta /* may be NULL */,
+                          void* work, void* stream);
+int oeh_drop_resid_ln_mask(const oeh_ln_train_desc* d, uint8_t* keep /* dense (rows, cols) */, void* stream);   /* tests */
+const char* oeh_drop_resid_ln_variant(const oeh_ln_train_desc* d, int backward);   /* host only, NULL if refused */
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -4,7 +4,8 @@ Python host surface mirroring the reference's plugin interface:
     SOFTMAX_MAPPING, AttentionGateType, BertSelfAttentionWithExtras, OPTAttentionWithExtras,
     ViTSelfAttentionWithExtras, Association / Hopfield / HopfieldPooling, QuantizedActivation,
     Quantized{Bert,OPT}...AttentionWithExtras, QuantEmbedding / QuantizedBertEmbeddings / opt_embed_front, kurtosis / inf_norm / OutlierMeter (the reference's result metrics),
-    cross_entropy / FusedCrossEntropyLoss / causal_lm_loss / masked_lm_loss / PerplexityMeter (the models' loss and the perplexity)
+    cross_entropy / FusedCrossEntropyLoss / causal_lm_loss / masked_lm_loss / PerplexityMeter (the models' loss and the perplexity),
+    dropout_add_layer_norm / FusedDropoutAddLayerNorm / FusedBertSelfOutput / FusedBertOutput / fuse_block_tails (the block tail in training)
 over the C-ABI library `lib/liboeh_hip.so` (include/oeh.h).  There is no CPU implementation in this package:
 every op raises if the HIP library is missing or a tensor is not on a GPU.
 """
@@ -12,6 +13,8 @@ from . import _lib, losses, ops  # noqa: F401
 from .attention import AttentionGateType, logit, set_fused_backward, set_fused_dropout, set_split_decode  # noqa: F401
 from .autograd_attention import fused_attention  # noqa: F401
 from .bert_attention import BertSelfAttentionWithExtras  # noqa: F401
+from .layers import (FusedBertOutput, FusedBertSelfOutput, FusedDropoutAddLayerNorm, dropout_add_layer_norm, fuse_block_tails,  # noqa: F401
+                     set_fused_ln_train)
 from .losses import FusedCrossEntropyLoss, PerplexityMeter, causal_lm_loss, cross_entropy, masked_lm_loss  # noqa: F401
 from .hopfield import Association, Hopfield, HopfieldPooling  # noqa: F401
 from .opt_attention import OPTAttentionWithExtras  # noqa: F401

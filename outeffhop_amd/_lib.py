@@ -113,6 +113,16 @@ class oeh_xent_desc(C.Structure):
                 ("label_smoothing", C.c_float), ("reserved", C.c_int32)]
 
 
+LN_TRAIN_MAX_GROUPS = 512  # include/oeh.h: OEH_LN_TRAIN_MAX_GROUPS
+
+
+class oeh_ln_train_desc(C.Structure):
+    """include/oeh.h: the rows of oeh_drop_resid_ln_fwd / oeh_drop_resid_ln_bwd (dropout + residual + LayerNorm for training)."""
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int32), ("dtype", C.c_int32),
+                ("x_stride", C.c_int64), ("r_stride", C.c_int64), ("sum_stride", C.c_int64), ("y_stride", C.c_int64),
+                ("dsum_stride", C.c_int64), ("eps", C.c_float), ("reserved", C.c_int32), ("drop", oeh_dropout)]
+
+
 # every symbol include/oeh.h declares (tests/test_abi.py checks the .so exports exactly these)
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
@@ -125,6 +135,7 @@ EXPORTS = (
     "oeh_quant_mse_work_bytes", "oeh_quant_mse",
     "oeh_resid_ln_quant", "oeh_resid_ln_variant",
     "oeh_xent_fwd", "oeh_xent_bwd", "oeh_xent_variant",
+    "oeh_drop_resid_ln_fwd", "oeh_drop_resid_ln_bwd_work_bytes", "oeh_drop_resid_ln_bwd", "oeh_drop_resid_ln_mask", "oeh_drop_resid_ln_variant",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
@@ -229,6 +240,16 @@ def load() -> C.CDLL:
     lib.oeh_xent_bwd.restype = C.c_int
     lib.oeh_xent_variant.argtypes = [C.POINTER(oeh_xent_desc), vp, vp]
     lib.oeh_xent_variant.restype = C.c_char_p
+    lib.oeh_drop_resid_ln_fwd.argtypes = [C.POINTER(oeh_ln_train_desc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_drop_resid_ln_fwd.restype = C.c_int
+    lib.oeh_drop_resid_ln_bwd_work_bytes.argtypes = [C.POINTER(oeh_ln_train_desc)]
+    lib.oeh_drop_resid_ln_bwd_work_bytes.restype = C.c_size_t
+    lib.oeh_drop_resid_ln_bwd.argtypes = [C.POINTER(oeh_ln_train_desc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_drop_resid_ln_bwd.restype = C.c_int
+    lib.oeh_drop_resid_ln_mask.argtypes = [C.POINTER(oeh_ln_train_desc), vp, vp]
+    lib.oeh_drop_resid_ln_mask.restype = C.c_int
+    lib.oeh_drop_resid_ln_variant.argtypes = [C.POINTER(oeh_ln_train_desc), C.c_int]
+    lib.oeh_drop_resid_ln_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

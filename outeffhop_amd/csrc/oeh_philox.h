@@ -44,4 +44,14 @@ __host__ __device__ __forceinline__ Philox4 dropout_words(uint32_t c, uint32_t i
   return philox4x32_10(c, i, bh, 0u, k0, k1);
 }
 
+// Row dropout stream (oeh_ln_train.hip, include/oeh.h: oeh_drop_resid_ln_fwd): the same key; the counter of element (i, j) of a
+// (rows, cols) array is (j >> 2, i & 0xffffffff, i >> 32, 1) and output word j & 3 belongs to it - the fourth counter word keeps the
+// stream apart from attention dropout's under one seed.  The four words of columns 4 c .. 4 c + 3 of row i:
+__host__ __device__ __forceinline__ Philox4 row_dropout_words(uint32_t c, uint64_t i, uint32_t k0, uint32_t k1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(k0), "+s"(k1));  // (as dropout_words: the round keys are formed again per call, not kept in SGPRs across the row loop)
+#endif
+  return philox4x32_10(c, (uint32_t)(i & 0xffffffffu), (uint32_t)(i >> 32), 1u, k0, k1);
+}
+
 }  // namespace oeh

@@ -942,6 +942,139 @@ def resid_ln_variant(rows: int, cols: int, dtype=torch.float32, *, row_stride: O
     return None if r is None else r.decode()
 
 
+# ---- the block tail in training (include/oeh.h: oeh_drop_resid_ln_fwd / oeh_drop_resid_ln_bwd): dropout + residual + LayerNorm, both directions
+def _ln_train_desc(rows: int, cols: int, dtype, strides, eps: float, p: float, seed: Optional[int], dsum_stride: int = 0) -> _lib.oeh_ln_train_desc:
+    """strides: (x, r, sum, y) forward, (dx, dr, s, dy) backward.  The library validates p; the seed is a uint64 and has to be given with p != 0."""
+    d = _lib.oeh_ln_train_desc()
+    d.rows, d.cols, d.dtype = rows, cols, _DT[dtype]
+    d.x_stride, d.r_stride, d.sum_stride, d.y_stride = strides
+    d.dsum_stride = dsum_stride
+    d.eps = float(eps)
+    drop = _dropout(p, seed)
+    d.drop.p, d.drop.seed = (0.0, 0) if drop is None else (drop.p, drop.seed)
+    return d
+
+
+def _own_rows(t: torch.Tensor, cols: int, what: str):
+    """An output as rows: it must BE the memory it was given as - no copy may stand in for it."""
+    v, st = _rows_view(t, cols)
+    if v.data_ptr() != t.data_ptr() or (v.shape[0] > 1 and st < cols):
+        raise ValueError(f"{what} needs a contiguous last dimension and leading dimensions that collapse to one row stride")
+    return v, st
+
+
+def drop_resid_ln_fwd(x: torch.Tensor, residual: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                      *, p: float = 0.0, seed: Optional[int] = None, out: Optional[torch.Tensor] = None, sum_out: Optional[torch.Tensor] = None):
+    """(sum, y, mean, rstd) of LayerNorm(dropout(x) + residual) over the last dimension in ONE kernel (`include/oeh.h: oeh_drop_resid_ln_fwd`):
+    sum = dropout(x) + residual in x's dtype - what the backward reads and what a pre-LN block carries on -, y its LayerNorm, mean / rstd the
+    row statistics (x.shape[:-1]; formed in float64, stored as fp32).  x, residual (..., N) fp16 / bf16 / fp32; weight (N) and bias (N) are taken as fp32.  p > 0 needs the
+    uint64 `seed` of the keep mask (`drop_resid_ln_mask`).  No autograd here (see `layers.dropout_add_layer_norm`).  sum_out may be `residual`,
+    out may be `x`."""
+    dev = _need_gpu(x, residual, weight, bias, out, sum_out, allow_grad=True)
+    _need_dtype(x)
+    cols = x.shape[-1] if x.dim() else 0
+    if cols < 1:
+        raise ValueError("drop_resid_ln_fwd needs a last dimension of at least 1")
+    for t_, what in ((residual, "residual"), (out, "out"), (sum_out, "sum_out")):
+        if t_ is not None and (t_.shape != x.shape or t_.dtype != x.dtype):
+            raise ValueError(f"{what} must have x's shape and dtype")
+    if weight.numel() != cols or (bias is not None and bias.numel() != cols):
+        raise ValueError("weight / bias must hold one value per column")
+    xv, xs = _rows_view(x.detach(), cols)
+    rv, rs = _rows_view(residual.detach(), cols) if residual is not None else (None, 0)
+    y = out if out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    s = sum_out if sum_out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    (sv, ss), (yv, ys) = _own_rows(s, cols, "sum_out"), _own_rows(y, cols, "out")
+    rows = xv.shape[0]
+    mean = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    rstd = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+    g, b = f32(weight), f32(bias)
+    d = _ln_train_desc(rows, cols, x.dtype, (xs, rs, ss, ys), eps, p, seed)
+    if rows:  # (an empty tensor has no address to hand over)
+        with _on_device(dev):
+            rc = _lib.load().oeh_drop_resid_ln_fwd(C.byref(d), _ptr(xv), _ptr(rv), _ptr(g), _ptr(b), _ptr(sv), _ptr(yv), _ptr(mean), _ptr(rstd), _stream())
+        _lib.check(rc, "oeh_drop_resid_ln_fwd")
+    return s, y, mean, rstd
+
+
+_ln_train_work = {}  # (device index, stream handle) -> the per-workgroup column partials of that stream's backward
+
+
+def drop_resid_ln_bwd(dy: torch.Tensor, s: torch.Tensor, weight: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, eps: float = 1e-5, *,
+                      dsum: Optional[torch.Tensor] = None,
+                      p: float = 0.0, seed: Optional[int] = None, want_dr: bool = True, want_dbeta: bool = True, dx: Optional[torch.Tensor] = None,
+                      dr: Optional[torch.Tensor] = None):
+    """(dx, dr, dgamma, dbeta) of `drop_resid_ln_fwd` from its sum `s`, mean, rstd and (p, seed), the output gradient dy and - where the sum was
+    an output with a gradient of its own - dsum (`include/oeh.h: oeh_drop_resid_ln_bwd`).  dx, dr: s's shape and dtype (dr None without
+    want_dr); dgamma, dbeta: fp32 (N) (dbeta None without want_dbeta), summed in float64 from the row statistics the kernel forms again in
+    float64 - which is what `eps`, the forward's, is for - and rounded once.  Two HIP kernels, no atomics: the same bits on every call.  dx may be
+    `dy`, dr may be `dsum`."""
+    dev = _need_gpu(dy, s, weight, mean, rstd, dsum, dx, dr, allow_grad=True)
+    _need_dtype(s)
+    cols = s.shape[-1] if s.dim() else 0
+    if cols < 1:
+        raise ValueError("drop_resid_ln_bwd needs a last dimension of at least 1")
+    for t_, what in ((dy, "dy"), (dsum, "dsum"), (dx, "dx"), (dr, "dr")):
+        if t_ is not None and (t_.shape != s.shape or t_.dtype != s.dtype):
+            raise ValueError(f"{what} must have s's shape and dtype")
+    if weight.numel() != cols:
+        raise ValueError("weight must hold one value per column")
+    sv, ss = _rows_view(s.detach(), cols)
+    rows = sv.shape[0]
+    for t_, what in ((mean, "mean"), (rstd, "rstd")):
+        if t_.dtype != torch.float32 or t_.numel() != rows or not t_.is_contiguous():
+            raise ValueError(f"{what} must be the contiguous fp32 row statistic of drop_resid_ln_fwd")
+    dyv, dys = _rows_view(dy.detach(), cols)
+    dsv, dss = _rows_view(dsum.detach(), cols) if dsum is not None else (None, 0)
+    dx = dx if dx is not None else torch.empty(s.shape, dtype=s.dtype, device=s.device)
+    dxv, dxs = _own_rows(dx, cols, "dx")
+    if dr is None and want_dr:
+        dr = torch.empty(s.shape, dtype=s.dtype, device=s.device)
+    drv, drs = _own_rows(dr, cols, "dr") if dr is not None else (None, 0)
+    dgamma = torch.empty(cols, dtype=torch.float32, device=s.device)
+    dbeta = torch.empty(cols, dtype=torch.float32, device=s.device) if want_dbeta else None
+    g = weight.detach().reshape(-1).to(torch.float32).contiguous()
+    d = _ln_train_desc(rows, cols, s.dtype, (dxs, drs, ss, dys), eps, p, seed, dss)
+    lib = _lib.load()
+    if rows:
+        work = _scratch(_ln_train_work, dev, max(int(lib.oeh_drop_resid_ln_bwd_work_bytes(C.byref(d))), 8))
+        with _on_device(dev):
+            rc = lib.oeh_drop_resid_ln_bwd(C.byref(d), _ptr(dyv), _ptr(dsv), _ptr(sv), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(dxv), _ptr(drv), _ptr(dgamma),
+                                           _ptr(dbeta), _ptr(work), _stream())
+        _lib.check(rc, "oeh_drop_resid_ln_bwd")
+    else:  # (an empty tensor has no address to hand over: sums over no row)
+        dgamma.zero_()
+        if dbeta is not None:
+            dbeta.zero_()
+    return dx, dr, dgamma, dbeta
+
+
+def drop_resid_ln_mask(rows: int, cols: int, p: float, seed: int, device) -> torch.Tensor:
+    """The keep mask `drop_resid_ln_fwd` / `drop_resid_ln_bwd` apply for (p, seed): a (rows, cols) bool tensor on `device`, True where an
+    element of x is kept (and scaled by 1 / (1 - p)).  include/oeh.h: oeh_drop_resid_ln_mask; p == 0 keeps everything."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    d = _ln_train_desc(int(rows), int(cols), torch.float32, (cols, cols, cols, cols), 0.0, p, seed)
+    keep = torch.empty((rows, cols), dtype=torch.uint8, device=device)
+    if rows:
+        with _on_device(device):
+            rc = _lib.load().oeh_drop_resid_ln_mask(C.byref(d), _ptr(keep), _stream())
+        _lib.check(rc, "oeh_drop_resid_ln_mask")
+    return keep.view(torch.bool)
+
+
+def drop_resid_ln_variant(rows: int, cols: int, dtype=torch.float32, *, backward: bool = False, p: float = 0.0, row_stride: Optional[int] = None) -> Optional[str]:
+    """Name of the launch form the training block tail takes for (rows, cols) tensors of `dtype` whose rows are `row_stride` (default: cols)
+    elements apart and 16-byte aligned: "ln_train/fwd/wave/CH2/f16/drop", "ln_train/bwd/block/CH8/f32/G512x2" (backward: workgroups of the
+    row kernel x rows of a slab), or None if refused.  Host only."""
+    st = cols if row_stride is None else int(row_stride)
+    d = _ln_train_desc(int(rows), int(cols), dtype, (st, st, st, st), 1e-5, p, 0, st)
+    r = _lib.load().oeh_drop_resid_ln_variant(C.byref(d), int(bool(backward)))
+    return None if r is None else r.decode()
+
+
 # ---- the quantised model front (include/oeh.h: oeh_embed_sum_quant): embedding lookups + sums + their quantisers + LayerNorm in one pass
 @dataclass
 class EmbedLookup:

@@ -712,6 +712,69 @@ int oeh_drop_resid_ln_bwd(const oeh_ln_train_desc* d, const void* dy, const void
 int oeh_drop_resid_ln_mask(const oeh_ln_train_desc* d, uint8_t* keep /* dense (rows, cols) */, void* stream);   /* tests */
 const char* oeh_drop_resid_ln_variant(const oeh_ln_train_desc* d, int backward);   /* host only, NULL if refused */
 
+/* The optimizer phase of a training step (oeh_optim.hip): the global gradient norm with its clip coefficient, and a decoupled-weight-decay
+ * Adam step over ALL parameter tensors of a model in one launch - what the reference's loops do after backward()
+ * (run_clm.py:440-462 torch.optim.AdamW over a decay and a no-decay group, :589-601 accelerator.clip_grad_norm_ then optimizer.step()).
+ * A call works on a PLAN: a table the host builds once from the tensor list, copies to the device and reuses while the pointers stay the same.
+ *   oeh_mt_plan(t, n_tensors, plan_host, n_chunks): host only.  Writes oeh_mt_plan_bytes(t, n_tensors) bytes into plan_host (8-byte
+ *   aligned; NULL: only *n_chunks is formed): first one 16-byte chunk entry per workgroup {int32 tensor, int32 count, int64 offset} - tensor
+ *   i's elements [offset, offset + count), count <= OEH_MT_CHUNK, the tensors in the order given and a tensor's chunks ascending - then one
+ *   56-byte record per tensor {p, g, m, v, int64 n, int32 g_dtype, int32 group, int32 vec16, int32 0}.  A tensor with n == 0 has a record and
+ *   no chunk.  Offsets are 64-bit throughout.
+ *   p, m, v: fp32.  g: g_dtype (OEH_F16 | OEH_BF16 | OEH_F32).  group: which column of oeh_adamw_desc the tensor is stepped with.
+ *   A tensor takes the 16-byte form ("vec16") when p, m and v are 16-byte aligned and g is aligned to four of its elements (16 bytes fp32,
+ *   8 bytes 16-bit): thread t of a chunk owns the elements [4 (k * 256 + t), + 4), k = 0..3, as one access per tensor.  The ragged end of a
+ *   vec16 tensor's last chunk is done by the same kernel element by element.  Any other tensor takes the element form ("elem"): one element
+ *   per access.  Both forms compute the same bits.  oeh_mt_variant: which one, NULL for a refused tensor; host only.
+ *   Refusals: OEH_EINVAL - t NULL with n_tensors > 0, n_tensors < 0, n_chunks NULL, n < 0, a NULL p / g / m / v, group outside
+ *   [0, OEH_MT_MAX_GROUPS), a g_dtype that is none of the three; OEH_EALIGN - p, m or v off 4 bytes, g off its element size; OEH_ENOTSUP -
+ *   2^31 or more chunks.  oeh_mt_plan_bytes: -1 for a refused list.
+ * oeh_grad_norm: two launches.  One workgroup per chunk writes the float64 partial sum of (double)g * (double)g (every product exact) into
+ *   work (oeh_grad_norm_work_bytes(n_chunks) bytes, 8-byte aligned); one workgroup of 1024 threads then adds the partials - thread t the
+ *   partials t, t + 1024, ... ascending, the wave butterflies, the 16 waves as a pairwise tree - and writes
+ *     out4 = {sumsq, norm = sqrt(sumsq), coef, 0},  coef = min(1, max_norm / (norm + 1e-6)) in float64 (torch's clip_grad_norm_)
+ *   max_norm <= 0, NaN or +inf: coef = 1.  A non-finite gradient gives a non-finite sumsq and the coef that formula then gives (NaN for NaN):
+ *   torch's error_if_nonfinite=False.  No atomics: the same bits on every call.  n_chunks == 0: the second launch alone, sumsq = 0.
+ * oeh_grad_scale: g <- RN_dtype(fp32(g) * c) in place, c = clip4[2] rounded to fp32 once; clip4 is device memory (an out4).
+ * oeh_adamw_step: one launch over the chunks.  c = clip4[2] rounded to fp32 once (clip4 NULL: c = 1, nothing read).  Per element in fp32,
+ *   every operation rounded on its own, `/` and sqrt correctly rounded, denormals kept; RN32: a constant the host forms in double from the
+ *   descriptor's fp32 fields and rounds to fp32 once; t = step[group], the step number AFTER the increment (torch's), the powers by pow():
+ *     g' = fp32(g) * c
+ *     p1 = p * RN32(1 - lr * wd)
+ *     m' = m + (g' - m) * RN32(1 - beta1)
+ *     v' = v * beta2 + (g' * g') * RN32(1 - beta2)
+ *     den = sqrt(v') / RN32(sqrt(1 - beta2^t)) + eps
+ *     p' = p1 - RN32(lr / (1 - beta1^t)) * (m' / den)
+ *   p, m, v are written; g is NOT (the clip is folded in: the difference from torch's clip_grad_norm_ + step pair).  A thread reads its
+ *   elements of a chunk before it writes them.  Tensors of a plan must not overlap each other.
+ *   Refusals: OEH_EINVAL - d NULL, n_groups outside [1, OEH_MT_MAX_GROUPS], reserved != 0, and for a group below n_groups: step < 1, lr, eps
+ *   or weight_decay negative or NaN, a beta outside [0, 1); n_chunks < 0; plan_dev NULL with n_chunks > 0 (all three entry points; oeh_grad_norm:
+ *   out4 NULL, work NULL with n_chunks > 0; oeh_grad_scale: clip4 NULL); OEH_EALIGN - work, out4 or clip4 off 8 bytes; OEH_ENOTSUP - n_chunks >= 2^31.
+ *   n_chunks == 0: OEH_OK without a launch (oeh_adamw_step, oeh_grad_scale).  The plan lives on the device and is not looked at by the host: a
+ *   tensor whose group is not below n_groups is no refusal - the kernel leaves its p, m and v untouched.
+ *   oeh_grad_norm and oeh_grad_scale read and write g alone.  A caller who plans for them only still has to name p, m and v (NULL is
+ *   refused): any 4-byte aligned addresses serve, 16-byte aligned ones leave the access form to g; such a plan must not be stepped. */
+#define OEH_MT_CHUNK 4096        /* elements of one tensor covered by one workgroup */
+#define OEH_MT_MAX_GROUPS 8
+#define OEH_MT_ENTRY_BYTES 16
+#define OEH_MT_RECORD_BYTES 56
+typedef struct oeh_mt_tensor {
+  void* p; const void* g; void* m; void* v;
+  int64_t n; int32_t g_dtype; int32_t group;
+} oeh_mt_tensor;
+typedef struct oeh_adamw_desc {
+  float lr[8], beta1[8], beta2[8], eps[8], weight_decay[8];
+  int64_t step[8];
+  int32_t n_groups, reserved;
+} oeh_adamw_desc;
+int64_t oeh_mt_plan_bytes(const oeh_mt_tensor* t, int32_t n_tensors);                                        /* host only */
+int oeh_mt_plan(const oeh_mt_tensor* t, int32_t n_tensors, void* plan_host /* may be NULL */, int64_t* n_chunks);   /* host only */
+const char* oeh_mt_variant(const oeh_mt_tensor* t);                                                          /* host only */
+int64_t oeh_grad_norm_work_bytes(int64_t n_chunks);
+int oeh_grad_norm(const void* plan_dev, int64_t n_chunks, double max_norm, void* work, double* out4, void* stream);
+int oeh_grad_scale(const void* plan_dev, int64_t n_chunks, const double* clip4, void* stream);
+int oeh_adamw_step(const void* plan_dev, int64_t n_chunks, const oeh_adamw_desc* d, const double* clip4 /* may be NULL */, void* stream);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -123,6 +123,20 @@ class oeh_ln_train_desc(C.Structure):
                 ("dsum_stride", C.c_int64), ("eps", C.c_float), ("reserved", C.c_int32), ("drop", oeh_dropout)]
 
 
+MT_CHUNK, MT_MAX_GROUPS, MT_ENTRY_BYTES, MT_RECORD_BYTES = 4096, 8, 16, 56  # include/oeh.h: OEH_MT_CHUNK, OEH_MT_MAX_GROUPS, OEH_MT_ENTRY_BYTES, OEH_MT_RECORD_BYTES
+
+
+class oeh_mt_tensor(C.Structure):
+    """include/oeh.h: one parameter tensor of a multi-tensor plan (fp32 p, m, v; g in g_dtype; the hyper-parameter group it is stepped with)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("g_dtype", C.c_int32), ("group", C.c_int32)]
+
+
+class oeh_adamw_desc(C.Structure):
+    """include/oeh.h: the hyper-parameters and step numbers of oeh_adamw_step, one column per group."""
+    _fields_ = [("lr", C.c_float * 8), ("beta1", C.c_float * 8), ("beta2", C.c_float * 8), ("eps", C.c_float * 8), ("weight_decay", C.c_float * 8),
+                ("step", C.c_int64 * 8), ("n_groups", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/oeh.h declares (tests/test_abi.py checks the .so exports exactly these)
 EXPORTS = (
     "oeh_attn_fwd", "oeh_softmax_rows", "oeh_fake_quant", "oeh_gate_fwd", "oeh_minmax", "oeh_percentile_ema", "oeh_fake_quant_range", "oeh_attn_calibrate", "oeh_quantize_heads_i8", "oeh_split_pairs", "oeh_split_triples", "oeh_proj_quant_i8",
@@ -136,6 +150,7 @@ EXPORTS = (
     "oeh_resid_ln_quant", "oeh_resid_ln_variant",
     "oeh_xent_fwd", "oeh_xent_bwd", "oeh_xent_variant",
     "oeh_drop_resid_ln_fwd", "oeh_drop_resid_ln_bwd_work_bytes", "oeh_drop_resid_ln_bwd", "oeh_drop_resid_ln_mask", "oeh_drop_resid_ln_variant",
+    "oeh_mt_plan_bytes", "oeh_mt_plan", "oeh_mt_variant", "oeh_grad_norm_work_bytes", "oeh_grad_norm", "oeh_grad_scale", "oeh_adamw_step",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
@@ -250,6 +265,20 @@ def load() -> C.CDLL:
     lib.oeh_drop_resid_ln_mask.restype = C.c_int
     lib.oeh_drop_resid_ln_variant.argtypes = [C.POINTER(oeh_ln_train_desc), C.c_int]
     lib.oeh_drop_resid_ln_variant.restype = C.c_char_p
+    lib.oeh_mt_plan_bytes.argtypes = [C.POINTER(oeh_mt_tensor), i32]
+    lib.oeh_mt_plan_bytes.restype = C.c_int64
+    lib.oeh_mt_plan.argtypes = [C.POINTER(oeh_mt_tensor), i32, vp, C.POINTER(i64)]
+    lib.oeh_mt_plan.restype = C.c_int
+    lib.oeh_mt_variant.argtypes = [C.POINTER(oeh_mt_tensor)]
+    lib.oeh_mt_variant.restype = C.c_char_p
+    lib.oeh_grad_norm_work_bytes.argtypes = [i64]
+    lib.oeh_grad_norm_work_bytes.restype = C.c_int64
+    lib.oeh_grad_norm.argtypes = [vp, i64, f64, vp, vp, vp]
+    lib.oeh_grad_norm.restype = C.c_int
+    lib.oeh_grad_scale.argtypes = [vp, i64, vp, vp]
+    lib.oeh_grad_scale.restype = C.c_int
+    lib.oeh_adamw_step.argtypes = [vp, i64, C.POINTER(oeh_adamw_desc), vp, vp]
+    lib.oeh_adamw_step.restype = C.c_int
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -1352,6 +1352,160 @@ def xent_variant(B: int, S: int, V: int, dtype=torch.float16, *, label_smoothing
     return None if r is None else r.decode()
 
 
+# ---- the optimizer phase (include/oeh.h: oeh_mt_plan, oeh_grad_norm, oeh_grad_scale, oeh_adamw_step): one plan over all parameter tensors
+MT_CHUNK = _lib.MT_CHUNK            # elements of one tensor that one workgroup covers
+MT_MAX_GROUPS = _lib.MT_MAX_GROUPS  # hyper-parameter groups of one step
+_grad_norm_work = {}  # (device index, stream handle) -> the per-chunk float64 partials of that stream's norm
+
+
+@dataclass(frozen=True)
+class AdamWGroup:
+    """The hyper-parameters one kernel group is stepped with; `step` is the step number AFTER the increment (torch's)."""
+    lr: float
+    beta1: float
+    beta2: float
+    eps: float
+    weight_decay: float
+    step: int
+
+
+class MtPlan:
+    """The device table of a tensor list (`mt_plan`): the chunk entries and tensor records the multi-tensor kernels read, the number of
+    chunks, and the tensors themselves - the table holds their addresses, so the plan keeps them alive (`hold_grads=False`: all but the
+    gradients, whose addresses the caller then checks before every use).  `staging` is the pinned host copy the table was sent from."""
+
+    def __init__(self, table, n_chunks, tensors, device, groups, numel, norm_only, records, staging):
+        self.table, self.n_chunks, self.tensors, self.device = table, n_chunks, tensors, device
+        self.groups, self.numel, self.norm_only, self._records, self.staging = groups, numel, norm_only, records, staging
+        self.stream = None  # the raw handle of the stream the table was copied on
+
+    @property
+    def variants(self):
+        """The access form of every non-empty tensor, in order: "vec16" or "elem" (include/oeh.h: oeh_mt_variant)."""
+        lib = _lib.load()
+        return [lib.oeh_mt_variant(C.byref(a)).decode() for a in self._records]
+
+
+def mt_plan(params, grads, exp_avgs=None, exp_avg_sqs=None, groups=None, *, hold_grads: bool = True, replace: Optional[MtPlan] = None) -> MtPlan:
+    """Plan the multi-tensor kernels over parallel lists: fp32 contiguous `params`, `exp_avgs`, `exp_avg_sqs`, and `grads` in fp32, fp16
+    or bf16, all of a tensor's four with the same number of elements and everything on one GPU; groups[i] in [0, MT_MAX_GROUPS) says which
+    `AdamWGroup` of `adamw_step` tensor i is stepped with (default 0).  With exp_avgs and exp_avg_sqs None the plan serves `grad_norm` and
+    `grad_scale_` only (`params` may then be None as well).  hold_grads=False: the plan does not keep the gradients alive - for a caller who
+    caches the plan across `zero_grad(set_to_none=True)` and compares every `data_ptr` before using it again (`optim.FusedAdamW`); a plan
+    whose gradients were freed must not be launched.  replace: a plan of the caller's that is given up for this one - its device table is
+    written over in place where it has the size (on the stream it was made on), so that planning again allocates nothing on the device
+    and the allocator's picture stays as the training loop left it.  Host work and one small copy to the device, from pinned memory and in stream order:
+    nothing waits for the device.  Reuse the plan while no tensor moves."""
+    grads = list(grads)
+    n = len(grads)
+    norm_only = exp_avgs is None and exp_avg_sqs is None
+    if norm_only:
+        params = exp_avgs = exp_avg_sqs = [None] * n
+    elif params is None or exp_avgs is None or exp_avg_sqs is None:
+        raise ValueError("mt_plan needs params, exp_avgs and exp_avg_sqs together")
+    params, exp_avgs, exp_avg_sqs = list(params), list(exp_avgs), list(exp_avg_sqs)
+    groups = [0] * n if groups is None else [int(g) for g in groups]
+    if not (len(params) == len(exp_avgs) == len(exp_avg_sqs) == len(groups) == n):
+        raise ValueError("mt_plan needs lists of one length")
+    dev = _need_gpu(*grads, *params, *exp_avgs, *exp_avg_sqs, allow_grad=True)
+    keep, rows = [], []
+    for p, g, m, v, grp in zip(params, grads, exp_avgs, exp_avg_sqs, groups):
+        g = g.detach()
+        if g.dtype not in _DT or g.is_sparse or not g.is_contiguous():
+            raise ValueError("gradients must be dense contiguous fp32, fp16 or bf16 tensors")
+        if not 0 <= grp < MT_MAX_GROUPS:
+            raise ValueError(f"group {grp} outside [0, {MT_MAX_GROUPS})")
+        if norm_only:
+            p = m = v = None
+        else:
+            p, m, v = p.detach(), m.detach(), v.detach()
+            for t_, what in ((p, "parameters"), (m, "exp_avgs"), (v, "exp_avg_sqs")):
+                if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.numel() != g.numel():
+                    raise ValueError(f"{what} must be contiguous fp32 tensors with as many elements as their gradients")
+        keep.append((p, g if hold_grads else None, m, v))
+        if g.numel():  # (an empty tensor has no address and no chunk)
+            # a norm-only plan names no p, m, v: the 16-byte boundary below g stands in, so that g alone decides the access form
+            rows.append(tuple(g.data_ptr() & ~15 if t_ is None else t_.data_ptr() for t_ in (p, m, v)) + (g.data_ptr(), g.numel(), _DT[g.dtype], grp))
+    arr = (_lib.oeh_mt_tensor * max(len(rows), 1))()
+    for a, (pp, mp, vp, gp, cnt, dt, grp) in zip(arr, rows):
+        a.p, a.g, a.m, a.v, a.n, a.g_dtype, a.group = pp, gp, mp, vp, cnt, dt, grp
+    lib = _lib.load()
+    nbytes = int(lib.oeh_mt_plan_bytes(arr, len(rows)))
+    if nbytes < 0:
+        _lib.check(lib.oeh_mt_plan(arr, len(rows), None, C.byref(C.c_int64())), "oeh_mt_plan")
+    # (pinned, so that the copy below is an asynchronous one in stream order: a pageable source makes torch wait for the stream, i.e. for
+    # the whole backward in front of an optimizer step.  torch's pinned-memory cache hands the block out again only after that copy has run.)
+    host = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, pin_memory=dev is not None)
+    n_chunks = C.c_int64()
+    _lib.check(lib.oeh_mt_plan(arr, len(rows), C.c_void_p(host.data_ptr()), C.byref(n_chunks)), "oeh_mt_plan")
+    table, stream = None, None
+    if dev is not None:
+        with _on_device(dev):
+            stream = _stream().value
+            if replace is not None and replace.table is not None and replace.device == dev and replace.stream == stream and replace.table.numel() == host.numel():
+                table = replace.table  # (stream order: every launch that read the old contents is in front of this copy)
+                table.copy_(host, non_blocking=True)
+            else:
+                table = host.to(dev, non_blocking=True)
+    plan = MtPlan(table, int(n_chunks.value), keep, dev, groups, sum(r[4] for r in rows), norm_only, arr[:len(rows)], host)
+    plan.stream = stream
+    return plan
+
+
+def grad_norm(plan: MtPlan, max_norm: Optional[float] = None, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(4,) float64 on the plan's GPU: {sum of squares, 2-norm, clip coefficient, 0} over every gradient of the plan, the squares exact and
+    summed in float64 in a fixed order (`include/oeh.h: oeh_grad_norm`); coefficient = min(1, max_norm / (norm + 1e-6)), 1 for max_norm None,
+    <= 0 or inf.  out: a (4,) float64 tensor on that GPU to write into instead of a new one.  Two launches, nothing synchronises."""
+    if plan.device is None:
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    lib = _lib.load()
+    if out is not None:
+        _need_gpu(out, plan.table)
+        _need_f64(out, 4, "out must be a contiguous float64 tensor of 4 elements")
+    out4 = out if out is not None else torch.empty(4, dtype=torch.float64, device=plan.device)
+    work = _scratch(_grad_norm_work, plan.device, max(int(lib.oeh_grad_norm_work_bytes(plan.n_chunks)), 8))
+    with _on_device(plan.device):
+        rc = lib.oeh_grad_norm(_ptr(plan.table), plan.n_chunks, 0.0 if max_norm is None else float(max_norm), _ptr(work), _ptr(out4), _stream())
+    _lib.check(rc, "oeh_grad_norm")
+    return out4
+
+
+def grad_scale_(plan: MtPlan, clip: torch.Tensor) -> None:
+    """Every gradient of the plan times clip[2] in place, rounded to fp32 once and then to the gradient's storage type (`clip`: a `grad_norm` result)."""
+    if plan.device is None:
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    _need_gpu(clip, plan.table)
+    _need_f64(clip, 4, "clip must be the (4,) float64 result of grad_norm")
+    with _on_device(plan.device):
+        rc = _lib.load().oeh_grad_scale(_ptr(plan.table), plan.n_chunks, _ptr(clip), _stream())
+    _lib.check(rc, "oeh_grad_scale")
+
+
+def adamw_step(plan: MtPlan, groups, clip: Optional[torch.Tensor] = None) -> None:
+    """One AdamW step of every tensor of the plan in one launch (`include/oeh.h: oeh_adamw_step`): groups[i] is the `AdamWGroup` of the
+    tensors planned with group i.  clip: a `grad_norm` result whose coefficient scales the gradients as they are read - they are not
+    written.  step and lr are host values recorded with the launch: not for graph capture."""
+    if plan.device is None:
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    if plan.norm_only:
+        raise ValueError("this plan was made without exp_avgs and exp_avg_sqs: it serves grad_norm and grad_scale_ only")
+    groups = list(groups)
+    if not 1 <= len(groups) <= MT_MAX_GROUPS:
+        raise ValueError(f"adamw_step takes 1 to {MT_MAX_GROUPS} groups")
+    if plan.groups and max(plan.groups) >= len(groups):
+        raise ValueError("a tensor of the plan names a group that was not given")
+    d = _lib.oeh_adamw_desc()
+    d.n_groups = len(groups)
+    for i, g in enumerate(groups):
+        d.lr[i], d.beta1[i], d.beta2[i], d.eps[i], d.weight_decay[i], d.step[i] = g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, int(g.step)
+    if clip is not None:
+        _need_gpu(clip, plan.table)
+        _need_f64(clip, 4, "clip must be the (4,) float64 result of grad_norm")
+    with _on_device(plan.device):
+        rc = _lib.load().oeh_adamw_step(_ptr(plan.table), plan.n_chunks, C.byref(d), _ptr(clip), _stream())
+    _lib.check(rc, "oeh_adamw_step")
+
+
 _calib_work = {}  # (device index, stream handle) -> the 36-KB histograms of that stream's on-device percentile selection
 
 

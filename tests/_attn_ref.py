@@ -82,10 +82,14 @@ def _c(name, Sq, Sk, D, **kw):
     before: the context quantiser before the gate; emit: ctx_emit_index; dumps: index dumps of every quantiser that is on; layout:
     see `pose`; qmul: q is N(0,1) * qmul; shift: a constant added to every score; hook: the off_mask of include/oeh_debug.h;
     via "prepared": launched through the prebuilt-call form (ops pads no head dim there); kernel: the variant name the library must give;
-    seq_bound: see `check_exact`."""
+    seq_bound: see `check_exact`; out32: out_dtype=float32 on 16-bit storage; pv_pairs: the probability pairs (fp32 storage); pad_bool:
+    key_pad_boolean; gate_units: the in-kernel gate predictor (ops.GatePredictor) with that many hidden units, 0 the linear one;
+    mq: flash_mq_force of include/oeh_debug.h; ramp: ramp * (j - Sk) is added to the score of key j, so that the latest keys a causal row
+    sees weigh most."""
     d = dict(name=name, B=2, H=2, Sq=Sq, Sk=Sk, D=D, storage="fp32", base=1, clip=None, scale=None, scale_div=0.0, pad=None, lens=None,
              full=None, causal=False, clamp_min=False, mask_min=R.FMIN32, gate=None, gs=None, gp=None, gc=None, before=True, emit=False,
-             dumps=False, layout="contig", qmul=1.0, shift=None, hook=0, via="fwd", kernel=None, seq_bound=False)
+             dumps=False, layout="contig", qmul=1.0, shift=None, hook=0, via="fwd", kernel=None, seq_bound=False, out32=False, pv_pairs=False, pad_bool=False,
+             gate_units=None, mq=0, ramp=None)
     assert not set(kw) - set(d), set(kw) - set(d)
     d.update(kw)
     if d["scale"] is None:
@@ -246,7 +250,9 @@ def low_of(c, dtype16: bool):
 
 def inputs(c):
     """dict(q, k, v: float32 arrays of values of the storage type; pad: (B,Sk) in the dtype the library is to read; full: (B,1,Sq,Sk)
-    likewise; gate: float32, (B,H,Sq,1) or (1,H,1,1))."""
+    likewise; gate: float32, (B,H,Sq,1) or (1,H,1,1)).  With gate_units: hidden (B,Sq,H D) in the storage type, the predictor's float32 weights
+    w1, b1, w2, b2 (ops.gate_fwd's layout), gate64 - the predictor in float64, (B,H,Sq,1), without gate_scaling - and gate: gate64 times
+    gate_scaling, which the chain applies until a kernel has written its own (GatePredictor.out)."""
     B, H, Sq, Sk, D = c["B"], c["H"], c["Sq"], c["Sk"], c["D"]
     seed = R._seed("attn", c["name"])
     rs = np.random.RandomState(seed)
@@ -255,6 +261,9 @@ def inputs(c):
     if c["shift"] is not None:  # head dim 0 carries the constant: q0 * 1 * scale = shift
         eff = 1.0 / c["scale_div"] if c["scale_div"] != 0.0 else c["scale"]
         q[..., 0], k[..., 0] = c["shift"] / eff, 1.0
+    if c["ramp"] is not None:  # head dim 1 carries the ramp: 1 * k1 * scale = ramp (j - Sk)
+        eff = 1.0 / c["scale_div"] if c["scale_div"] != 0.0 else c["scale"]
+        q[..., 1], k[..., 1] = 1.0, ((np.arange(Sk) - Sk) * (c["ramp"] / eff)).astype(np.float32)[None, None, :]
     x = dict(q=R.round_storage(q, c["storage"]), k=R.round_storage(k, c["storage"]), v=R.round_storage(v, c["storage"]), pad=None, full=None, gate=None)
     if c["pad"] is not None:
         f16 = c["pad"] == "f16"
@@ -264,7 +273,34 @@ def inputs(c):
         x["full"] = R.full_matrix(seed + 2, B, Sq, Sk, low_of(c, f16)).astype(np.float16 if f16 else np.float32)
     if c["gate"] is not None:
         x["gate"] = rs.rand(*((B, H, Sq, 1) if c["gate"] == "token" else (1, H, 1, 1))).astype(np.float32)
+    if c["gate_units"] is not None:
+        m = c["gate_units"]
+        x["hidden"] = R.round_storage(rs.standard_normal((B, Sq, H * D)).astype(np.float32), c["storage"])
+        x["w1"] = (rs.standard_normal((H, m, D) if m else (H, D)) * 0.2).astype(np.float32)
+        x["b1"] = (rs.standard_normal((H, m) if m else (H,)) * 0.2).astype(np.float32)
+        x["w2"] = (rs.standard_normal((H, m)) * 0.5).astype(np.float32) if m else None
+        x["b2"] = rs.standard_normal((H,)).astype(np.float32) if m else None
+        x["gate64"] = gate64(x["hidden"], H, x["w1"], x["b1"], x["w2"], x["b2"])
+        x["gate"] = (x["gate64"] * gate_scaling(c)).astype(np.float32)
     return x
+
+
+def gate_scaling(c) -> float:
+    """gate_scaling of a case with the in-kernel predictor: 1 with the linear predictor, 2 with the hidden layer."""
+    return 2.0 if c["gate_units"] else 1.0
+
+
+def gate64(hidden, H, w1, b1, w2=None, b2=None):
+    """The per-head gate predictor in float64 (oracle/oeh_oracle.py: gate_values, "linear" / "mlp"): (B,H,T,1) probabilities."""
+    x = np.asarray(hidden, dtype=np.float64)
+    B, T, E = x.shape
+    xh = x.reshape(B, T, H, E // H).transpose(0, 2, 1, 3)
+    if w2 is None:
+        a = np.einsum("bhtd,hd->bht", xh, w1.astype(np.float64)) + b1.astype(np.float64)[None, :, None]
+    else:
+        h1 = np.maximum(np.einsum("bhtd,hmd->bhtm", xh, w1.astype(np.float64)) + b1.astype(np.float64)[None, :, None, :], 0.0)
+        a = np.einsum("bhtm,hm->bht", h1, w2.astype(np.float64)) + b2.astype(np.float64)[None, :, None]
+    return (1.0 / (1.0 + np.exp(-a)))[..., None]
 
 
 def _f32(a):
@@ -395,13 +431,50 @@ def check_exact(c, r, got, dumps=None):
     return ratio
 
 
-def contract_limit(want, storage: str):
+def contract_limit(want, storage: str, gate_scale: float = 1.0):
+    """gate_scale: gate_scaling of the in-kernel predictor, which multiplies the output - the arithmetic (absolute) term scales with it, as
+    tests/test_attn_gpu.py: test_gate_predictor_fused_in_kernel writes it."""
     a, rel = CONTRACT[storage]
-    return a + rel * np.abs(want) + (half_ulp(want, "fp16") if storage == "fp16" else 0.0)
+    return a * gate_scale + rel * np.abs(want) + (half_ulp(want, "fp16") if storage == "fp16" else 0.0)
 
 
-def check_contract(c, r, got, dumps=None):
+def limit_of(c, r):
+    """The limit on |got - want64| of a case of the matrix-core kernels: the contract - or, with the probability pairs, the bound
+    tests/test_attn_pv_pairs_gpu.py applies (4 x the fp32 oracle's own distance from float64 + 2^-20 max(1, |V|max))."""
+    if c["pv_pairs"]:
+        return np.full(r["w"]["ctx"].shape, 4.0 * r["e_out"] + 2.0 ** -20 * max(1.0, float(np.abs(r["x"]["v"]).max())))
+    return contract_limit(r["w"]["ctx"], c["storage"], gate_scaling(c) if c["gate_units"] is not None else 1.0)
+
+
+def check_contract_long(c, r, got, dumps):
+    """Quantised rows of more than 512 keys, where no kernel with fp16 operands writes dumps: `dumps` are the any-shape kernel's, held to
+    check_exact's statement; rows that hold an element inside a tie band or an index that differs from float64 are left out of the output
+    check (at most MAX_LEFT_OUT_ROWS of them), as are such elements of the context; the others meet the contract.  Returns the largest
+    |got - want64| / limit."""
+    w, (gs, gp, gc) = r["w"], r["grids"]
+    zero = np.zeros(r["rows_s"].shape, dtype=bool)
+    rows = r["rows_p"].copy()
+    out_c = r["band_c"].copy()
+    for key, g, band, up in (("scores", gs, r["band_s"], zero), ("probs", gp, r["band_p"], r["rows_s"]), ("ctx", gc, r["band_c"], r["rows_p"])):
+        if not g:
+            continue
+        _check_indices(c, key, dumps[key], w[key + "_idx"], band, up)
+        differs = dumps[key].astype(np.float64) != w[key + "_idx"]
+        if key == "ctx":
+            out_c |= differs
+        else:
+            rows |= (band | differs).any(axis=-1)
+    assert rows.mean() <= MAX_LEFT_OUT_ROWS, (c["name"], "rows left out", float(rows.mean()))
+    assert np.isfinite(got).all(), (c["name"], "non-finite output")
+    keep = ~rows[..., None] & ~out_c
+    q = np.abs(got - w["ctx"]) / limit_of(c, r)
+    assert not (q[keep] > 1.0).any(), (c["name"], "output", int((q[keep] > 1.0).sum()), float(q[keep].max()))
+    return float(q[keep].max())
+
+
+def check_contract(c, r, got, dumps=None, leave_out=None):
     """The general / one-pass kernels' acceptance (module docstring).  Quantised cases come with the dumps of a second, bitwise equal run.
+    leave_out: elements of the output that the dumps do not speak for (where the run that wrote them differs from `got`).
     Returns the largest |got - want64| / limit over the checked elements."""
     w, (gs, gp, gc) = r["w"], r["grids"]
     assert np.isfinite(got).all(), (c["name"], "non-finite output")
@@ -422,7 +495,9 @@ def check_contract(c, r, got, dumps=None):
             else:
                 rows |= (d != 0).any(axis=-1)
     keep = ~rows[..., None] & ~flip_c
-    q = np.abs(got - w["ctx"]) / contract_limit(w["ctx"], c["storage"])
+    if leave_out is not None:
+        keep = keep & ~leave_out
+    q = np.abs(got - w["ctx"]) / limit_of(c, r)
     assert not (q[keep] > 1.0).any(), (c["name"], "output", int((q[keep] > 1.0).sum()), float(q[keep].max()))
     return float(q[keep].max())
 
@@ -431,12 +506,16 @@ def check_contract(c, r, got, dumps=None):
 GUARD = 7.0
 
 
-def pose(ops, torch, c, x, with_dumps=None):
-    """Run case c on inputs x through ops.attn_fwd under its hook mask.  Returns (variant name of the real descriptor, output as a float64
-    array, dumps or None).  Layouts: "contig"; "blhe" - (B,L,H,E) tensors viewed (B,H,L,E); "longkv" - k and v are the first Sk rows of a
-    longer buffer whose other rows are NaN; "outslice" - the caller's `out` is the inside of a larger tensor that must keep its other
+def pose(ops, torch, c, x, with_dumps=None, info=None):
+    """Run case c on inputs x through ops.attn_fwd under its hook mask (and flash_mq_force).  Returns (variant name of the real descriptor,
+    output as a float64 array, dumps or None).  Layouts: "contig"; "blhe" - (B,L,H,E) tensors viewed (B,H,L,E); "longkv" - k and v are the
+    first Sk rows of a longer buffer whose other rows are NaN;
+    "outslice" - the caller's `out` is the inside of a larger tensor that must keep its other
     elements; "off4" - rows of q, k, v and out start 4 elements into rows of D + 4 (8-byte, not 16-byte aligned in 16-bit storage);
-    "fused" - q, k and v are the three slots of one (B,S,3 H D) tensor."""
+    "fused" - q, k and v are the three slots of one (B,S,3 H D) tensor; "qslice" - q is the first Sq rows of a buffer of Sk rows (NaN beyond):
+    q, k and v then have the same three strides.  info: a dict that receives desc / fqd (the real descriptors), raw (the output tensor as the
+    library wrote it, on the host), gate_out (what the in-kernel predictor wrote, (B,H,Sq)) and hot (how many launches took the hot argument
+    prefix)."""
     from outeffhop_amd import _lib
 
     DT = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
@@ -456,6 +535,10 @@ def pose(ops, torch, c, x, with_dumps=None):
             buf = torch.full((B, H, S + 5, D), float("nan"), dtype=dt, device="cuda")
             buf[:, :, :S] = dev(a, dt)
             return buf[:, :, :S]
+        if lay == "qslice" and slot == 0:
+            buf = torch.full((B, H, Sk, D), float("nan"), dtype=dt, device="cuda")
+            buf[:, :, :S] = dev(a, dt)
+            return buf[:, :, :S]
         if lay == "off4":
             buf = torch.full((B, H, S, D + 4), float("nan"), dtype=dt, device="cuda")
             buf[..., 4:] = dev(a, dt)
@@ -472,6 +555,7 @@ def pose(ops, torch, c, x, with_dumps=None):
     else:
         tq, tk, tv = heads(x["q"], 0), heads(x["k"], 1), heads(x["v"], 2)
     out, big = None, None
+    odt = torch.float32 if c["out32"] else dt
     if lay == "outslice":
         big = torch.full((B, H, Sq + 2, D + 8), GUARD, dtype=dt, device="cuda")
         out = big[:, :, 1:Sq + 1, 4:D + 4]
@@ -480,8 +564,18 @@ def pose(ops, torch, c, x, with_dumps=None):
         out = big[..., 4:]
     sm = ops.SoftmaxSpec(base=c["base"]) if c["clip"] is None else ops.SoftmaxSpec(base=c["base"], clip=True, gamma=c["clip"][0], eta=c["clip"][1])
     kw = dict(softmax=sm, scale=c["scale"], scale_div=c["scale_div"], causal=c["causal"], clamp_min=c["clamp_min"], mask_min=c["mask_min"], out=out)
+    if c["out32"]:
+        kw["out_dtype"] = torch.float32
+    if c["pv_pairs"]:
+        kw["pv_pairs"] = True
     if x["pad"] is not None:
         kw["key_pad_mask"] = dev(x["pad"])
+        kw["key_pad_boolean"] = c["pad_bool"]
+    gate_out = None
+    if c["gate_units"] is not None:
+        gate_out = torch.full((B, H, Sq), float("nan"), dtype=torch.float32, device="cuda")
+        w = {n: None if x[n] is None else dev(x[n]) for n in ("w1", "b1", "w2", "b2")}
+        kw["gate_mlp"] = ops.GatePredictor(dev(x["hidden"], dt), w["w1"], w["b1"], w["w2"], w["b2"], scaling=gate_scaling(c), out=gate_out)
     if x["full"] is not None:
         if c["full"] == "strided":  # rows of a wider allocation, read in place through the row stride
             wide = torch.full((B, 1, Sq, Sk + 8), GUARD, device="cuda")
@@ -490,7 +584,7 @@ def pose(ops, torch, c, x, with_dumps=None):
             assert not kw["full_mask"].is_contiguous()
         else:
             kw["full_mask"] = dev(x["full"])
-    if x["gate"] is not None:
+    if x["gate"] is not None and c["gate_units"] is None:
         kw["gate"] = dev(x["gate"])
     dumps = None
     if c["gs"] or c["gp"] or c["gc"]:
@@ -508,22 +602,28 @@ def pose(ops, torch, c, x, with_dumps=None):
         kw["fq"] = ops.AttnFakeQuant(scores=spec("gs", (B, H, Sq, Sk)), probs=spec("gp", (B, H, Sq, Sk)), ctx=spec("gc", (B, H, Sq, D)),
                                      ctx_before_gate=c["before"], ctx_emit_index=c["emit"])
     lib = _lib.load()
-    assert lib.oeh_debug_set_variant(c["hook"], 0) == 0
+    assert lib.oeh_debug_set_variant(c["hook"], c["mq"]) == 0
     try:
         box = []
         res = ops.attn_fwd(tq, tk, tv, _prepared=box, **kw)  # (builds the descriptor, launches nothing)
         fn, args, keep = box
         d, fqd = keep[0], keep[1]
-        name = lib.oeh_attn_variant(ctypes.byref(d), None if fqd is None else ctypes.byref(fqd))
+        if c["pv_pairs"]:
+            name = lib.oeh_attn_variant_ex(ctypes.byref(d), ctypes.byref(_lib.oeh_attn_opts(pv_pairs=1)), None if fqd is None else ctypes.byref(fqd))
+        else:
+            name = lib.oeh_attn_variant(ctypes.byref(d), None if fqd is None else ctypes.byref(fqd))
         name = None if name is None else name.decode()
+        lib.oeh_debug_hot_launches.restype = ctypes.c_long
+        hot0 = lib.oeh_debug_hot_launches()
         if c["via"] == "prepared":
             _lib.check(fn(*args, ops._stream()), "oeh_attn_fwd")
         else:
             res = ops.attn_fwd(tq, tk, tv, **kw)
         torch.cuda.synchronize()
+        hot = lib.oeh_debug_hot_launches() - hot0
     finally:
         lib.oeh_debug_set_variant(0, 0)
-    assert res.shape == (B, H, Sq, D) and res.dtype == dt
+    assert res.shape == (B, H, Sq, D) and res.dtype == odt
     if big is not None:  # nothing around the caller's view was written
         inside = torch.zeros(big.shape, dtype=torch.bool, device="cuda")
         if lay == "outslice":
@@ -532,6 +632,8 @@ def pose(ops, torch, c, x, with_dumps=None):
             inside[..., 4:] = True
         assert bool((big[~inside] == GUARD).all()), (c["name"], "the kernel wrote outside the caller's out")
     got = res.float().cpu().numpy().astype(np.float64)
+    if info is not None:
+        info.update(desc=d, fqd=fqd, raw=res.cpu(), hot=hot, gate_out=None if gate_out is None else gate_out.cpu().numpy().astype(np.float64))
     if dumps is not None:
         dumps = {{"gs": "scores", "gp": "probs", "gc": "ctx"}[k]: t.cpu().numpy() for k, t in dumps.items()}
     return name, got, dumps

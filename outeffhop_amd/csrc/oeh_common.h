@@ -84,6 +84,8 @@ __device__ __forceinline__ float grid_rel_m(float s, float k1, float lo_m, float
 // wave-uniform branches.  Written per element with the three conditions inline the compiler turns them into selects and
 // evaluates BOTH quantisers for every element (21 vector instructions per element where 10 do: a quarter of the int8 core's
 // vector instructions were this epilogue).  The opaque asm in a pass keeps it a branch.  rel (tests' index dumps): idx - zp.
+// The written value is oscale * rel + 0 in one fma: a quotient in (-0.5, 0) rounds to -0 (and lo is -0 at zp = 0), while the reference's
+// (idx - zp) * scale is never -0 (fq_rel_sat above) - as a product the output carried the sign, and its fp16 / bf16 forms with it.
 template <int N, bool WANT_REL = false>
 __device__ __forceinline__ void ctx_chain(float (&x)[N], const FqP& fc, const int before_gate, const bool gated, const float gatev, float* rel = nullptr) {
   const bool first = fc.en && (before_gate || !gated), last = fc.en && !before_gate && gated;
@@ -93,7 +95,7 @@ __device__ __forceinline__ void ctx_chain(float (&x)[N], const FqP& fc, const in
     for (int i = 0; i < N; ++i) {
       const float r = fq_rel(x[i], fc);
       if constexpr (WANT_REL) rel[i] = r;
-      x[i] = fc.oscale * r;
+      x[i] = __builtin_fmaf(fc.oscale, r, 0.0f);
     }
   }
   if (gated) {
@@ -107,7 +109,7 @@ __device__ __forceinline__ void ctx_chain(float (&x)[N], const FqP& fc, const in
     for (int i = 0; i < N; ++i) {
       const float r = fq_rel(x[i], fc);
       if constexpr (WANT_REL) rel[i] = r;
-      x[i] = fc.oscale * r;
+      x[i] = __builtin_fmaf(fc.oscale, r, 0.0f);
     }
   }
 }

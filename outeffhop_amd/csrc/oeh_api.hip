@@ -1,9 +1,10 @@
-// extern "C" entry points of liboeh_hip.so (declared in include/oeh.h): argument validation, kernel
-// variant selection and launch.  No allocation, no synchronisation: safe under hipGraph capture.
+// The attention forward dispatcher of liboeh_hip.so - oeh_attn_fwd[_ex], oeh_attn_variant[_ex] and oeh_attn_calibrate: descriptor validation,
+// kernel variant selection and the launch across the attention units (oeh_launch.h) - plus what belongs to the whole library: the debug
+// hooks, oeh_abi_version, oeh_build_info, oeh_strerror.  Every other extern "C" entry point of include/oeh.h lives in the unit that owns its
+// kernels.  No allocation, no synchronisation: safe under hipGraph capture.
 #include "../../include/oeh.h"
 #include "../../include/oeh_debug.h"
 #include "oeh_desc.h"
-#include "oeh_gemm.h"
 #include "oeh_launch.h"
 
 #include <cmath>
@@ -14,11 +15,9 @@
 using oeh::AttnParams;
 using oeh::FqP;
 // the descriptor predicates and the descriptor -> kernel block fill (oeh_desc.h)
-using oeh::addr; using oeh::aligned16; using oeh::all16; using oeh::any_fq; using oeh::desc_sane; using oeh::dtype_ok; using oeh::softmax_base_ok;
+using oeh::addr; using oeh::aligned16; using oeh::all16; using oeh::any_fq; using oeh::desc_sane; using oeh::dtype_ok; using oeh::elem_bytes; using oeh::softmax_base_ok;
 
 namespace {
-
-int elem_bytes(int d) { return d == OEH_F32 ? 4 : d == OEH_I8 ? 1 : 2; }
 
 using oeh::make_fq;  // (oeh_attn_params.h)
 
@@ -384,7 +383,7 @@ AttnPlan plan_attn(const oeh_attn_desc* d, const oeh_attn_opts* opts, const void
 
 const char* variant_name(const AttnPlan& pl, const oeh_attn_desc* d, bool fq) {
   static thread_local char buf[64];
-  const char* dt = d->dtype == OEH_F16 ? "f16" : (d->dtype == OEH_BF16 ? "bf16" : "f32");
+  const char* dt = oeh::dtype_name(d->dtype);  // (not used by V_I8, whose dtype is none of the three)
   const char* pv2 = pl.pv2 ? "+pv2" : "";
   switch (pl.var) {
     case V_NONE: return nullptr;
@@ -455,270 +454,6 @@ const char* oeh_attn_variant_ex(const oeh_attn_desc* desc, const oeh_attn_opts* 
 
 const char* oeh_attn_variant(const oeh_attn_desc* desc, const oeh_fq_desc* fq) { return oeh_attn_variant_ex(desc, nullptr, fq); }
 
-int oeh_softmax_rows(const void* x, void* y, int64_t rows, int32_t cols, int32_t dtype, int32_t softmax_base, int32_t clip,
-                     float gamma, float eta, void* stream) {
-  if (x == nullptr || y == nullptr || rows < 0 || cols <= 0 || !dtype_ok(dtype)) return OEH_EINVAL;
-  if (softmax_base != OEH_SOFTMAX_VANILLA && softmax_base != OEH_SOFTMAX_ONE) return OEH_EINVAL;
-  if (rows == 0) return OEH_OK;
-  const float w = (float)((double)eta - (double)gamma);
-  return oeh::launch_softmax_rows(x, y, rows, cols, dtype, softmax_base, clip ? 1 : 0, w, gamma, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_fake_quant(const void* x, void* y, uint8_t* idx, int64_t n, int32_t dtype, float scale, float zero_point, float qmax,
-                   void* stream) {
-  if (x == nullptr || n < 0 || !dtype_ok(dtype)) return OEH_EINVAL;
-  if (!oeh::fq_grid_ok(scale, zero_point, qmax, false)) return OEH_EINVAL;
-  if (idx != nullptr && qmax > 255.0f) return OEH_ENOTSUP;
-  if (n == 0 || (y == nullptr && idx == nullptr)) return OEH_OK;
-  const oeh_fq f = {1, scale, zero_point, qmax, nullptr};
-  return oeh::launch_fake_quant(x, y, idx, n, dtype, make_fq(&f), reinterpret_cast<hipStream_t>(stream));
-}
-
-// oeh_resid_ln_quant / oeh_resid_ln_variant: the descriptor's own refusals (no pointers), then the launch form for `vec16`
-static int ln_check(const oeh_ln_desc* d, bool with_sum, bool with_sum_idx, bool with_y_idx) {
-  if (d == nullptr || d->cols < 1 || d->rows < 0 || !dtype_ok(d->dtype) || !(d->eps >= 0.0f) || d->reserved != 0) return OEH_EINVAL;
-  if (d->x_stride < 0 || d->r_stride < 0 || d->sum_stride < 0 || d->y_stride < 0) return OEH_EINVAL;
-  if (d->rows > 1 && (d->y_stride < d->cols || (with_sum && d->sum_stride < d->cols))) return OEH_EINVAL;
-  if (d->fq_sum.enable && !oeh::fq_grid_ok(d->fq_sum, false)) return OEH_EINVAL;
-  if (d->fq_out.enable && !oeh::fq_grid_ok(d->fq_out, false)) return OEH_EINVAL;
-  if ((with_sum_idx && !d->fq_sum.enable) || (with_y_idx && !d->fq_out.enable)) return OEH_EINVAL;
-  if (d->cols > oeh::kLnMaxCols || d->rows >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
-  if ((with_sum_idx && d->fq_sum.qmax > 255.0f) || (with_y_idx && d->fq_out.qmax > 255.0f)) return OEH_ENOTSUP;
-  return OEH_OK;
-}
-static bool ln_strides_vec16(const oeh_ln_desc* d, bool with_r, bool with_sum) {
-  const int nv = d->dtype == OEH_F32 ? 4 : 8;
-  return d->cols % nv == 0 && d->x_stride % nv == 0 && d->y_stride % nv == 0 && (!with_r || d->r_stride % nv == 0) &&
-         (!with_sum || d->sum_stride % nv == 0);
-}
-
-int oeh_resid_ln_quant(const oeh_ln_desc* d, const void* x, const void* r, const float* gamma, const float* beta, void* sum_out, void* y,
-                       uint8_t* sum_idx, uint8_t* y_idx, void* stream) {
-  if (x == nullptr || gamma == nullptr || y == nullptr) return OEH_EINVAL;
-  const int rc = ln_check(d, sum_out != nullptr, sum_idx != nullptr, y_idx != nullptr);
-  if (rc != OEH_OK) return rc;
-  if (d->rows == 0) return OEH_OK;
-  const bool vec16 = ln_strides_vec16(d, r != nullptr, sum_out != nullptr) && all16(addr(x) | addr(r) | addr(gamma) | addr(beta) | addr(sum_out) | addr(y));
-  oeh::LnArgs a = {};
-  a.x = x; a.r = r; a.gamma = gamma; a.beta = beta; a.sum = sum_out; a.y = y; a.sum_idx = sum_idx; a.y_idx = y_idx;
-  a.rows = d->rows; a.cols = d->cols;
-  a.x_stride = d->x_stride; a.r_stride = d->r_stride; a.sum_stride = d->sum_stride; a.y_stride = d->y_stride;
-  a.eps = d->eps;
-  a.fq_sum = make_fq(&d->fq_sum); a.fq_out = make_fq(&d->fq_out);
-  return oeh::launch_resid_ln(a, d->dtype, oeh::ln_plan(d->cols, d->dtype, vec16), reinterpret_cast<hipStream_t>(stream));
-}
-
-const char* oeh_resid_ln_variant(const oeh_ln_desc* d) {
-  static thread_local char name[48];
-  if (ln_check(d, d != nullptr && d->sum_stride != 0, false, false) != OEH_OK) return nullptr;
-  const oeh::LnPlan pl = oeh::ln_plan(d->cols, d->dtype, ln_strides_vec16(d, true, true));
-  std::snprintf(name, sizeof name, "ln/%s/CH%d/%s", pl.form == oeh::LN_WAVE ? "wave" : pl.form == oeh::LN_BLOCK ? "block" : "scalar", pl.ch,
-                d->dtype == OEH_F32 ? "f32" : d->dtype == OEH_BF16 ? "bf16" : "f16");
-  return name;
-}
-
-// oeh_embed_sum_quant / oeh_embed_sum_variant: every refusal in the order OEH_EINVAL -> OEH_ENOTSUP -> OEH_EALIGN, then whether the 16-byte forms apply
-static int embed_check(const oeh_embed_desc* d, const float* gamma, const float* beta, const void* sum_out, const void* y, bool with_sum_idx,
-                       bool with_y_idx, bool* vec16) {
-  if (d == nullptr || y == nullptr || d->n_tab < 1 || d->n_tab > 3 || d->cols < 1 || d->B < 0 || d->S < 0 || !dtype_ok(d->dtype)) return OEH_EINVAL;
-  if (d->reserved != 0 || d->reserved2 != 0 || d->sum_stride < 0 || d->y_stride < 0) return OEH_EINVAL;
-  const int64_t rows = (int64_t)d->B * d->S;
-  if (rows > 1 && (d->y_stride < d->cols || (sum_out != nullptr && d->sum_stride < d->cols))) return OEH_EINVAL;
-  for (int t = 0; t < d->n_tab; ++t) {
-    const oeh_embed_lookup& l = d->tab[t];
-    if (l.table == nullptr || (t >= 1 && l.ids == nullptr) || l.reserved != 0) return OEH_EINVAL;
-    if (l.ids == nullptr && l.n_rows < rows) return OEH_EINVAL;  // dense rows: one per (b, s)
-    if (l.n_rows < 0 || l.row_stride < 0 || l.id_stride_b < 0 || l.id_stride_s < 0) return OEH_EINVAL;
-    if ((l.id_dtype != OEH_ID_I32 && l.id_dtype != OEH_ID_I64) || l.form < OEH_TAB_PLAIN || l.form > OEH_TAB_I8) return OEH_EINVAL;
-    if (l.form != OEH_TAB_PLAIN && (!(l.scale > 0.0f) || !std::isfinite(l.scale) || !(l.int_min < l.int_max))) return OEH_EINVAL;
-  }
-  for (int t = 0; t < 3; ++t) {
-    if (d->fq_sum[t].enable && (t == 0 || t >= d->n_tab || !oeh::fq_grid_ok(d->fq_sum[t], false))) return OEH_EINVAL;
-  }
-  if (d->fq_out.enable && !oeh::fq_grid_ok(d->fq_out, false)) return OEH_EINVAL;
-  if (gamma == nullptr && (beta != nullptr || d->fq_out.enable || with_y_idx)) return OEH_EINVAL;
-  if ((with_sum_idx && !d->fq_sum[d->n_tab - 1].enable) || (with_y_idx && !d->fq_out.enable)) return OEH_EINVAL;
-  if (gamma != nullptr && !(d->eps >= 0.0f)) return OEH_EINVAL;
-  if (d->cols > oeh::kLnMaxCols || rows >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
-  for (int t = 0; t < d->n_tab; ++t) {
-    if (d->tab[t].form == OEH_TAB_I8 && (d->tab[t].int_min < -128.0f || d->tab[t].int_max > 127.0f)) return OEH_ENOTSUP;
-  }
-  if ((with_sum_idx && d->fq_sum[d->n_tab - 1].qmax > 255.0f) || (with_y_idx && d->fq_out.qmax > 255.0f)) return OEH_ENOTSUP;
-  const int eb = elem_bytes(d->dtype), nv = d->dtype == OEH_F32 ? 4 : 8;
-  bool v16 = d->cols % nv == 0 && d->y_stride % nv == 0 && (sum_out == nullptr || d->sum_stride % nv == 0) &&
-             all16(addr(gamma) | addr(beta) | addr(sum_out) | addr(y));
-  for (int t = 0; t < d->n_tab; ++t) {
-    const oeh_embed_lookup& l = d->tab[t];
-    if (l.ids != nullptr && addr(l.ids) % (l.id_dtype == OEH_ID_I64 ? 8 : 4) != 0) return OEH_EALIGN;
-    if (addr(l.table) % (l.form == OEH_TAB_I8 ? 4 : eb) != 0) return OEH_EALIGN;
-    // (an int8 row is read nv BYTES at a time; a float row nv elements = 16 bytes)
-    v16 = v16 && l.row_stride % nv == 0 && (l.form == OEH_TAB_I8 ? addr(l.table) % nv == 0 : all16(addr(l.table)));
-  }
-  if (addr(y) % eb != 0 || addr(sum_out) % eb != 0 || addr(gamma) % 4 != 0 || addr(beta) % 4 != 0) return OEH_EALIGN;
-  *vec16 = v16;
-  return OEH_OK;
-}
-
-int oeh_embed_sum_quant(const oeh_embed_desc* d, const float* gamma, const float* beta, void* sum_out, void* y, uint8_t* sum_idx, uint8_t* y_idx,
-                        int32_t* bad_rows, void* stream) {
-  bool vec16 = false;
-  const int rc = embed_check(d, gamma, beta, sum_out, y, sum_idx != nullptr, y_idx != nullptr, &vec16);
-  if (rc != OEH_OK) return rc;
-  if (addr(bad_rows) % 4 != 0) return OEH_EALIGN;
-  if ((int64_t)d->B * d->S == 0) return OEH_OK;
-  oeh::EmbedArgs a = {};
-  for (int t = 0; t < d->n_tab; ++t) {
-    const oeh_embed_lookup& l = d->tab[t];
-    a.tab[t] = oeh::EmbedTab{l.table, l.ids, l.n_rows, l.row_stride, l.id_stride_b, l.id_stride_s, l.form, l.id_dtype == OEH_ID_I64, l.scale, l.int_min, l.int_max};
-    a.fq_sum[t] = make_fq(&d->fq_sum[t]);
-  }
-  a.gamma = gamma; a.beta = beta; a.sum = sum_out; a.y = y; a.sum_idx = sum_idx; a.y_idx = y_idx; a.bad_rows = bad_rows;
-  a.rows = (long)d->B * d->S; a.S = d->S; a.cols = d->cols;
-  a.sum_stride = d->sum_stride; a.y_stride = d->y_stride;
-  a.eps = d->eps;
-  a.fq_out = make_fq(&d->fq_out);
-  return oeh::launch_embed(a, d->dtype, d->n_tab, oeh::ln_plan(d->cols, d->dtype, vec16), reinterpret_cast<hipStream_t>(stream));
-}
-
-const char* oeh_embed_sum_variant(const oeh_embed_desc* d) {
-  static thread_local char name[48];
-  bool vec16 = false;
-  // (the outputs and gamma / beta are taken as given with every part and 16-byte aligned, as oeh_resid_ln_variant does)
-  const void* const aligned = reinterpret_cast<const void*>((uintptr_t)4096);
-  if (embed_check(d, static_cast<const float*>(aligned), nullptr, d != nullptr && d->sum_stride != 0 ? aligned : nullptr, aligned, false, false, &vec16) != OEH_OK)
-    return nullptr;
-  const oeh::LnPlan pl = oeh::ln_plan(d->cols, d->dtype, vec16);
-  std::snprintf(name, sizeof name, "embed/%s/CH%d/T%d/%s", pl.form == oeh::LN_WAVE ? "wave" : pl.form == oeh::LN_BLOCK ? "block" : "scalar", pl.ch,
-                d->n_tab, d->dtype == OEH_F32 ? "f32" : d->dtype == OEH_BF16 ? "bf16" : "f16");
-  return name;
-}
-
-// oeh_xent_fwd / oeh_xent_bwd / oeh_xent_variant: every refusal in the order OEH_EINVAL -> OEH_ENOTSUP -> OEH_EALIGN.  bwd: dx_stride is looked at.
-static int xent_check(const oeh_xent_desc* d, const void* logits, const void* labels, bool bwd) {
-  if (d == nullptr || logits == nullptr || labels == nullptr || d->V < 1 || d->B < 0 || d->S < 0 || !dtype_ok(d->dtype)) return OEH_EINVAL;
-  if (d->label_dtype != OEH_ID_I32 && d->label_dtype != OEH_ID_I64) return OEH_EINVAL;
-  for (int i = 0; i < 2; ++i) {
-    if (d->x_stride[i] < 0 || d->label_stride[i] < 0 || (bwd && d->dx_stride[i] < 0)) return OEH_EINVAL;
-  }
-  if (bwd && ((d->S > 1 && d->dx_stride[1] < d->V) || (d->B > 1 && d->dx_stride[0] < d->V))) return OEH_EINVAL;
-  if (!(d->label_smoothing >= 0.0f && d->label_smoothing < 1.0f) || d->reserved != 0) return OEH_EINVAL;
-  if ((int64_t)d->B * d->S >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
-  if (addr(logits) % elem_bytes(d->dtype) != 0 || addr(labels) % (d->label_dtype == OEH_ID_I64 ? 8 : 4) != 0) return OEH_EALIGN;
-  return OEH_OK;
-}
-static oeh::XentArgs xent_args(const oeh_xent_desc* d, const void* logits, const void* labels) {
-  oeh::XentArgs a = {};
-  a.x = logits; a.labels = labels;
-  a.x_sb = d->x_stride[0]; a.x_ss = d->x_stride[1]; a.l_sb = d->label_stride[0]; a.l_ss = d->label_stride[1];
-  a.dx_sb = d->dx_stride[0]; a.dx_ss = d->dx_stride[1];
-  a.ignore_index = d->ignore_index; a.rows = (long)d->B * d->S;
-  a.S = d->S; a.V = d->V; a.in = d->dtype; a.label64 = d->label_dtype == OEH_ID_I64; a.mean_reduction = d->mean_reduction != 0;
-  a.eps_ls = d->label_smoothing;
-  return a;
-}
-// whether the gradient rows take element stores: a dlogits row that is not as far from a 16-byte boundary as its logits row
-static bool xent_el(const oeh_xent_desc* d, const void* logits, const void* dlogits) {
-  const int64_t eb = elem_bytes(d->dtype);
-  bool same = (addr(logits) - addr(dlogits)) % 16 == 0;
-  if (d->B > 1) same = same && ((d->x_stride[0] - d->dx_stride[0]) * eb) % 16 == 0;
-  if (d->S > 1) same = same && ((d->x_stride[1] - d->dx_stride[1]) * eb) % 16 == 0;
-  return !same;
-}
-
-int oeh_xent_fwd(const oeh_xent_desc* d, const void* logits, const void* labels, float* lse, float* row_loss, double* out2, float* mean,
-                 double* meter, int32_t* bad_rows, void* stream) {
-  if (lse == nullptr || out2 == nullptr) return OEH_EINVAL;
-  if (d != nullptr && row_loss == nullptr && d->label_smoothing > 0.0f) return OEH_EINVAL;
-  const int rc = xent_check(d, logits, labels, false);
-  if (rc != OEH_OK) return rc;
-  if ((addr(lse) | addr(row_loss) | addr(mean) | addr(bad_rows)) % 4 != 0 || (addr(out2) | addr(meter)) % 8 != 0) return OEH_EALIGN;
-  oeh::XentArgs a = xent_args(d, logits, labels);
-  a.lse = lse; a.row_loss = row_loss; a.out2 = out2; a.mean = mean; a.meter = meter; a.bad_rows = bad_rows;
-  return oeh::launch_xent_fwd(a, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_xent_bwd(const oeh_xent_desc* d, const void* logits, const void* labels, const float* lse, const double* out2, const float* grad,
-                 int64_t grad_stride, void* dlogits, void* stream) {
-  if (lse == nullptr || out2 == nullptr || grad == nullptr || dlogits == nullptr || grad_stride < 0) return OEH_EINVAL;
-  const int rc = xent_check(d, logits, labels, true);
-  if (rc != OEH_OK) return rc;
-  if ((addr(lse) | addr(grad)) % 4 != 0 || addr(out2) % 8 != 0 || addr(dlogits) % elem_bytes(d->dtype) != 0) return OEH_EALIGN;
-  oeh::XentArgs a = xent_args(d, logits, labels);
-  a.lse = const_cast<float*>(lse); a.out2 = const_cast<double*>(out2); a.grad = grad; a.grad_stride = grad_stride; a.dx = dlogits;
-  return oeh::launch_xent_bwd(a, xent_el(d, logits, dlogits), reinterpret_cast<hipStream_t>(stream));
-}
-
-const char* oeh_xent_variant(const oeh_xent_desc* d, const void* logits, const void* dlogits) {
-  static thread_local char name[48];
-  const void* const aligned = reinterpret_cast<const void*>((uintptr_t)4096);  // (the labels are taken as given and aligned)
-  if (xent_check(d, logits, aligned, dlogits != nullptr) != OEH_OK) return nullptr;
-  if (dlogits != nullptr && addr(dlogits) % elem_bytes(d->dtype) != 0) return nullptr;
-  std::snprintf(name, sizeof name, "xent/block/CH%d/%s%s%s", OEH_XENT_SLOTS, d->dtype == OEH_F32 ? "f32" : d->dtype == OEH_BF16 ? "bf16" : "f16",
-                d->label_smoothing > 0.0f ? "/ls" : "", dlogits != nullptr && xent_el(d, logits, dlogits) ? "/el" : "");
-  return name;
-}
-
-int oeh_gate_fwd(const void* hidden, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t d, int64_t hidden_stride_b,
-                 int64_t hidden_stride_t, const float* w1, const float* b1, const float* w2, const float* b2, int32_t hidden_units,
-                 int32_t per_head_pool, float scaling, float* gate_out, void* stream) {
-  if (hidden == nullptr || w1 == nullptr || b1 == nullptr || gate_out == nullptr || !dtype_ok(dtype)) return OEH_EINVAL;
-  if (B <= 0 || T <= 0 || H <= 0 || d <= 0 || hidden_units < 0) return OEH_EINVAL;
-  if (hidden_units > 0 && (w2 == nullptr || b2 == nullptr)) return OEH_EINVAL;
-  return oeh::launch_gate(hidden, dtype, B, T, H, d, hidden_stride_b, hidden_stride_t, w1, b1, w2, b2, hidden_units,
-                          per_head_pool ? 1 : 0, scaling, gate_out, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_minmax(const void* x, int64_t n, int32_t dtype, float* out2, void* stream) {
-  if (x == nullptr || out2 == nullptr || n <= 0 || !dtype_ok(dtype)) return OEH_EINVAL;
-  return oeh::launch_minmax(x, n, dtype, out2, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_percentile_ema(const void* x, int64_t n, int32_t dtype, double q_lo, double q_hi, double momentum, int32_t first, double* state,
-                       void* work, void* stream) {
-  if (x == nullptr || state == nullptr || work == nullptr || n <= 0 || n >= (int64_t)1 << 32 || !dtype_ok(dtype)) return OEH_EINVAL;
-  if (!(q_lo >= 0.0 && q_lo <= 100.0 && q_hi >= 0.0 && q_hi <= 100.0) || !(momentum >= 0.0 && momentum <= 1.0)) return OEH_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(work) & 7) != 0 || (reinterpret_cast<uintptr_t>(state) & 7) != 0) return OEH_EALIGN;
-  return oeh::launch_percentile_ema(x, n, dtype, q_lo, q_hi, momentum, first ? 1 : 0, state, work, reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t oeh_outlier_stats_work_bytes(int64_t rows, int64_t cols) {
-  if (rows < 1 || cols < 1) return 0;
-  return (size_t)rows * (size_t)oeh::stats_chunks(cols) * OEH_STATS_RECORD_BYTES;
-}
-
-int oeh_outlier_stats(const void* x, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, double eps, float* stats, double* meter,
-                      int32_t accumulate, void* work, void* stream) {
-  if (x == nullptr || stats == nullptr || rows < 1 || cols < 1 || row_stride < cols || !dtype_ok(dtype) || !(eps >= 0.0)) return OEH_EINVAL;
-  if (accumulate < 0 || accumulate > 3 || (accumulate != 0 && meter == nullptr)) return OEH_EINVAL;
-  const bool need_work = oeh::stats_chunks(cols) > 0;
-  if (need_work && work == nullptr) return OEH_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(stats) & 15) != 0 || (reinterpret_cast<uintptr_t>(meter) & 7) != 0 || (need_work && (reinterpret_cast<uintptr_t>(work) & 7) != 0) ||
-      (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem_bytes(dtype) - 1)) != 0)
-    return OEH_EALIGN;
-  return oeh::launch_outlier_stats(x, rows, cols, row_stride, dtype, eps, stats, meter, accumulate, work, reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t oeh_quant_mse_work_bytes(int64_t n, int32_t K) {
-  if (n < 1 || K < 1) return 0;
-  return (size_t)oeh::qmse_blocks(n, nullptr, nullptr) * (size_t)(K < OEH_QMSE_SLICE ? K : OEH_QMSE_SLICE) * sizeof(double);
-}
-
-int oeh_quant_mse(const void* x, int64_t n, int32_t dtype, const float* cand, int32_t K, double* loss, int32_t accumulate, void* work,
-                  void* stream) {
-  if (x == nullptr || cand == nullptr || loss == nullptr || work == nullptr || n < 1 || K < 1 || !dtype_ok(dtype)) return OEH_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(cand) & 15) != 0 || (reinterpret_cast<uintptr_t>(loss) & 7) != 0 || (reinterpret_cast<uintptr_t>(work) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem_bytes(dtype) - 1)) != 0)
-    return OEH_EALIGN;
-  return oeh::launch_quant_mse(x, n, dtype, cand, K, loss, accumulate != 0, work, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_fake_quant_range(const void* x, void* y, int64_t n, int32_t dtype, const double* xmin_xmax, int32_t n_bits, double eps,
-                         void* stream) {
-  if (x == nullptr || y == nullptr || xmin_xmax == nullptr || n < 0 || !dtype_ok(dtype) || n_bits < 1 || n_bits > 16 || !(eps > 0.0)) return OEH_EINVAL;
-  if (n == 0) return OEH_OK;
-  return oeh::launch_fake_quant_range(x, y, n, dtype, xmin_xmax, (float)((1 << n_bits) - 1), eps, reinterpret_cast<hipStream_t>(stream));
-}
-
 int oeh_attn_calibrate(const oeh_attn_desc* desc, const void* q, const void* k, const void* v, float* ctx_out, int32_t which,
                        const double* scores_range, const double* probs_range, int32_t n_bits, double eps, double q_lo, double q_hi,
                        double momentum, int32_t first, double* state, void* work, void* stream) {
@@ -739,71 +474,6 @@ int oeh_attn_calibrate(const oeh_attn_desc* desc, const void* q, const void* k, 
   fill_params(P, desc, q, k, v, ctx_out, nullptr);
   return oeh::launch_attn_calibrate(P, desc->dtype, which, scores_range, probs_range, (float)((1 << n_bits) - 1), eps, q_lo, q_hi, momentum, first ? 1 : 0,
                                     state, work, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_quantize_heads_i8(const void* x, int8_t* out, void* y, int64_t B, int32_t S, int32_t H, const int64_t x_stride[2], const int64_t y_stride[2],
-                          int32_t dtype, float scale, float zero_point, int32_t transpose, float alpha, const float* bias, void* stream) {
-  if (x == nullptr || (out == nullptr && (y == nullptr || transpose)) || x_stride == nullptr || B <= 0 || S <= 0 || H <= 0 || !dtype_ok(dtype)) return OEH_EINVAL;
-  if (!(scale > 0.0f) || zero_point < 0.0f || zero_point > 255.0f || zero_point != std::nearbyint(zero_point)) return OEH_EINVAL;
-  if (y != nullptr && y_stride == nullptr) return OEH_EINVAL;
-  if (!transpose && x_stride[0] != (int64_t)S * x_stride[1]) return OEH_ENOTSUP;
-  if (!transpose && y != nullptr && y_stride[0] != (int64_t)S * y_stride[1]) return OEH_ENOTSUP;
-  if (transpose && (S & 15) != 0) return OEH_ENOTSUP;
-  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return OEH_EALIGN;
-  {  // 16-byte vector loads of the input rows and of the bias
-    const int eb = elem_bytes(dtype);
-    if (!all16(addr(x) | (uintptr_t)(x_stride[0] * eb) | (uintptr_t)(x_stride[1] * eb) | addr(bias))) return OEH_EALIGN;
-  }
-  if (y != nullptr && !all16(addr(y) | (uintptr_t)(y_stride[0] * elem_bytes(dtype)) | (uintptr_t)(y_stride[1] * elem_bytes(dtype)))) return OEH_EALIGN;  // 16-byte value stores
-  const oeh_fq f = {1, scale, zero_point, 255.0f, nullptr};
-  return oeh::launch_quantize_heads_i8(x, reinterpret_cast<signed char*>(out), y, B, S, H, x_stride[0], x_stride[1], y != nullptr ? y_stride[0] : 0,
-                                       y != nullptr ? y_stride[1] : 0, dtype, make_fq(&f), transpose ? 1 : 0, alpha, bias, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* bias, int64_t B, int32_t S, int32_t K, int32_t E, int32_t n_seg,
-                      const oeh_proj_seg* segs, int64_t lda, int64_t ldw, void* stream) {
-  if (a == nullptr || w == nullptr || bias == nullptr || segs == nullptr || B <= 0 || S <= 0 || K <= 0 || E <= 0 || n_seg < 1 || n_seg > 3) return OEH_EINVAL;
-  if ((K % oeh::kGemmBK) != 0 || (E & 63) != 0 || (S & 15) != 0 || B * (int64_t)S > 0x7fffffffLL) return OEH_ENOTSUP;
-  if (pairs < 0 || pairs > 3) return OEH_EINVAL;
-  const int64_t aeb = pairs == 2 ? 4 : pairs == 3 ? 1 : 2;  // (pairs == 2: a is the fp32 activation matrix itself; 3: int8 a and w)
-  const int64_t web = pairs == 3 ? 1 : 2;
-  if (pairs == 3 && (K & 63) != 0) return OEH_ENOTSUP;
-  if (lda < (pairs == 1 ? 2 : 1) * (int64_t)K || ldw < K) return OEH_EINVAL;
-  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) | (uintptr_t)(lda * aeb) | (uintptr_t)(ldw * web)) & 15) != 0) return OEH_EALIGN;
-  if (B * (int64_t)S * lda * aeb >= 0xffffffffLL || (int64_t)n_seg * E * ldw * web >= 0xffffffffLL) return OEH_ENOTSUP;  // (32-bit lane offsets)
-  oeh::GemmParams P;
-  std::memset(&P, 0, sizeof(P));
-  P.a = a; P.w = w; P.bias = bias; P.lda = lda; P.ldw = ldw; P.M = (int)(B * S); P.N = n_seg * E; P.K = K; P.pairs = pairs;
-  P.E = E; P.S = S; P.H = E / 64;
-  for (int i = 0; i < n_seg; ++i) {
-    const oeh_proj_seg& g = segs[i];
-    if (g.out == nullptr && g.y == nullptr) return OEH_EINVAL;
-    if (!(g.scale > 0.0f) || g.zero_point < 0.0f || g.zero_point > 255.0f || g.zero_point != std::nearbyint(g.zero_point)) return OEH_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(g.out) & 15) != 0 || (reinterpret_cast<uintptr_t>(g.y) & 3) != 0) return OEH_EALIGN;
-    if (g.y != nullptr && g.y_stride_row < E) return OEH_EINVAL;
-    if (g.y != nullptr && (12 * g.y_stride_row + 16) * 4 >= 0xffffffffLL) return OEH_ENOTSUP;  // (32-bit lane offsets of the value stores: oeh_gemm.hip y_voff)
-    oeh::GemmSeg& t = P.seg[i];
-    t.alpha = g.alpha; t.out = reinterpret_cast<signed char*>(g.out); t.y = g.y; t.y_ld = g.y_stride_row; t.transpose = g.transpose ? 1 : 0;
-    t.acc_add = pairs == 3 ? g.acc_add : nullptr;
-    if ((reinterpret_cast<uintptr_t>(g.acc_add) & 3) != 0) return OEH_EALIGN;
-    const oeh_fq f = {1, g.scale, g.zero_point, 255.0f, nullptr};
-    t.f = make_fq(&f);
-  }
-  return oeh::launch_gemm(P, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_split_triples(const float* x, void* out_f16, int64_t rows, int32_t K, int64_t x_stride_row, void* stream) {
-  if (x == nullptr || out_f16 == nullptr || rows <= 0 || K <= 0) return OEH_EINVAL;
-  if ((K & 7) != 0) return OEH_ENOTSUP;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out_f16) | (uintptr_t)(x_stride_row * 4)) & 15) != 0) return OEH_EALIGN;
-  return oeh::launch_split_triples(x, out_f16, rows, K, x_stride_row, reinterpret_cast<hipStream_t>(stream));
-}
-
-int oeh_split_pairs(const float* x, void* out_f16, int64_t rows, int32_t K, int64_t x_stride_row, void* stream) {
-  if (x == nullptr || out_f16 == nullptr || rows <= 0 || K <= 0) return OEH_EINVAL;
-  if ((K & 7) != 0) return OEH_ENOTSUP;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out_f16) | (uintptr_t)(x_stride_row * 4)) & 15) != 0) return OEH_EALIGN;
-  return oeh::launch_split_pairs(x, out_f16, rows, K, x_stride_row, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Diagnostic hooks: include/oeh_debug.h (NOT part of the product ABI; inert unless OEH_DEBUG_HOOKS=1 in the environment)

@@ -12,6 +12,7 @@
 //                        (uniform_quantizers.py:72-82), so the host never reads the range while it is still moving.
 // The selection reads the tensor four times (a 50 M-element score tensor: ~0.2 ms) instead of sorting it.
 #include "oeh_launch.h"
+#include "oeh_desc.h"
 
 namespace oeh {
 
@@ -462,7 +463,7 @@ int launch_attn_calibrate(const AttnParams& P, int in, int which, const double* 
   return launch_status();
 }
 
-int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_hi, double momentum, int first, double* state, void* workv,
+static int launch_percentile_ema(const void* x, long n, int in, double q_lo, double q_hi, double momentum, int first, double* state, void* workv,
                           hipStream_t st) {
   unsigned* work = static_cast<unsigned*>(workv);
   // np.percentile, method "linear": virtual index h = (n - 1) q / 100, i = floor(h), frac = h - i
@@ -497,7 +498,7 @@ __global__ __launch_bounds__(256) void fake_quant_range_kernel(const void* __res
     y[i] = In<IN>::from_f32(f.scale * fq_rel_sat(In<IN>::to_f32(x[i]), f));
 }
 
-int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st) {
+static int launch_fake_quant_range(const void* x, void* y, long n, int in, const double* range, float qmax, double eps, hipStream_t st) {
   const unsigned blocks = (unsigned)((n + 256L * 8 - 1) / (256L * 8) < 4096 ? (n + 256L * 8 - 1) / (256L * 8) : 4096);
   dispatch_in(in, [&](auto t) { hipLaunchKernelGGL(fake_quant_range_kernel<decltype(t)::value>, dim3(blocks), dim3(256), 0, st, x, y, n, range, qmax, eps); });
   return launch_status();
@@ -629,7 +630,7 @@ __global__ __launch_bounds__(256) void quantize_heads_t_kernel(const void* __res
   }
 }
 
-int launch_quantize_heads_i8(const void* x, signed char* out, void* y, long B, int S, int H, long x_sb, long x_ss, long y_sb, long y_ss, int in,
+static int launch_quantize_heads_i8(const void* x, signed char* out, void* y, long B, int S, int H, long x_sb, long x_ss, long y_sb, long y_ss, int in,
                              FqP f, int transpose, float alpha, const float* bias, hipStream_t st) {
   const bool wy = y != nullptr;
   if (!transpose) {
@@ -716,14 +717,14 @@ __global__ __launch_bounds__(256) void split_triples_kernel(const float* __restr
   }
 }
 
-int launch_split_triples(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st) {
+static int launch_split_triples(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st) {
   const long total = rows * ((long)K / 8 + 1);
   const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(split_triples_kernel, dim3(blocks), dim3(256), 0, st, x, static_cast<unsigned short*>(out), rows, K, x_sr);
   return launch_status();
 }
 
-int launch_split_pairs(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st) {
+static int launch_split_pairs(const float* x, void* out, long rows, int K, long x_sr, hipStream_t st) {
   const long total = rows * (K / 8);
   const unsigned blocks = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
   hipLaunchKernelGGL(split_pairs_kernel, dim3(blocks), dim3(256), 0, st, x, static_cast<unsigned short*>(out), rows, K, x_sr);
@@ -731,3 +732,59 @@ int launch_split_pairs(const float* x, void* out, long rows, int K, long x_sr, h
 }
 
 }  // namespace oeh
+
+using namespace oeh;
+
+extern "C" {
+
+int oeh_percentile_ema(const void* x, int64_t n, int32_t dtype, double q_lo, double q_hi, double momentum, int32_t first, double* state,
+                       void* work, void* stream) {
+  if (x == nullptr || state == nullptr || work == nullptr || n <= 0 || n >= (int64_t)1 << 32 || !dtype_ok(dtype)) return OEH_EINVAL;
+  if (!(q_lo >= 0.0 && q_lo <= 100.0 && q_hi >= 0.0 && q_hi <= 100.0) || !(momentum >= 0.0 && momentum <= 1.0)) return OEH_EINVAL;
+  if ((addr(work) & 7) != 0 || (addr(state) & 7) != 0) return OEH_EALIGN;
+  return launch_percentile_ema(x, n, dtype, q_lo, q_hi, momentum, first ? 1 : 0, state, work, reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_fake_quant_range(const void* x, void* y, int64_t n, int32_t dtype, const double* xmin_xmax, int32_t n_bits, double eps,
+                         void* stream) {
+  if (x == nullptr || y == nullptr || xmin_xmax == nullptr || n < 0 || !dtype_ok(dtype) || n_bits < 1 || n_bits > 16 || !(eps > 0.0)) return OEH_EINVAL;
+  if (n == 0) return OEH_OK;
+  return launch_fake_quant_range(x, y, n, dtype, xmin_xmax, (float)((1 << n_bits) - 1), eps, reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_quantize_heads_i8(const void* x, int8_t* out, void* y, int64_t B, int32_t S, int32_t H, const int64_t x_stride[2], const int64_t y_stride[2],
+                          int32_t dtype, float scale, float zero_point, int32_t transpose, float alpha, const float* bias, void* stream) {
+  if (x == nullptr || (out == nullptr && (y == nullptr || transpose)) || x_stride == nullptr || B <= 0 || S <= 0 || H <= 0 || !dtype_ok(dtype)) return OEH_EINVAL;
+  if (!(scale > 0.0f) || zero_point < 0.0f || zero_point > 255.0f || zero_point != std::nearbyint(zero_point)) return OEH_EINVAL;
+  if (y != nullptr && y_stride == nullptr) return OEH_EINVAL;
+  if (!transpose && x_stride[0] != (int64_t)S * x_stride[1]) return OEH_ENOTSUP;
+  if (!transpose && y != nullptr && y_stride[0] != (int64_t)S * y_stride[1]) return OEH_ENOTSUP;
+  if (transpose && (S & 15) != 0) return OEH_ENOTSUP;
+  if ((addr(out) & 15) != 0) return OEH_EALIGN;
+  const int eb = elem_bytes(dtype);
+  // 16-byte vector loads of the input rows and of the bias, 16-byte value stores
+  if (!all16(addr(x) | (uintptr_t)(x_stride[0] * eb) | (uintptr_t)(x_stride[1] * eb) | addr(bias))) return OEH_EALIGN;
+  if (y != nullptr && !all16(addr(y) | (uintptr_t)(y_stride[0] * eb) | (uintptr_t)(y_stride[1] * eb))) return OEH_EALIGN;
+  const oeh_fq f = {1, scale, zero_point, 255.0f, nullptr};
+  return launch_quantize_heads_i8(x, reinterpret_cast<signed char*>(out), y, B, S, H, x_stride[0], x_stride[1], y != nullptr ? y_stride[0] : 0,
+                                  y != nullptr ? y_stride[1] : 0, dtype, make_fq(&f), transpose ? 1 : 0, alpha, bias, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the two operand splits share their refusals
+static int split_check(const float* x, const void* out_f16, int64_t rows, int32_t K, int64_t x_stride_row) {
+  if (x == nullptr || out_f16 == nullptr || rows <= 0 || K <= 0) return OEH_EINVAL;
+  if ((K & 7) != 0) return OEH_ENOTSUP;
+  return all16(addr(x) | addr(out_f16) | (uintptr_t)(x_stride_row * 4)) ? OEH_OK : OEH_EALIGN;
+}
+
+int oeh_split_triples(const float* x, void* out_f16, int64_t rows, int32_t K, int64_t x_stride_row, void* stream) {
+  const int rc = split_check(x, out_f16, rows, K, x_stride_row);
+  return rc != OEH_OK ? rc : launch_split_triples(x, out_f16, rows, K, x_stride_row, reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_split_pairs(const float* x, void* out_f16, int64_t rows, int32_t K, int64_t x_stride_row, void* stream) {
+  const int rc = split_check(x, out_f16, rows, K, x_stride_row);
+  return rc != OEH_OK ? rc : launch_split_pairs(x, out_f16, rows, K, x_stride_row, reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // The attention descriptor (include/oeh.h: oeh_attn_desc, oeh_fq_desc) on the host: one text for every rule that the attention entry points
 // share - what a sane descriptor is, which strides and rows the kernels can address, what a quantiser grid is, when causal tiles may be
-// skipped, and how the descriptor becomes the problem part of a kernel-argument block.  Only the predicates live here: each entry point keeps
-// the ORDER of its refusals and its codes where they can be read (oeh_api.hip: validate / plan_attn, oeh_attn_decode.hip: plan_decode,
-// oeh_attn_bwd.hip: check_desc / fwd_train / bwd_run).  Host only, no device code.
+// skipped, and how the descriptor becomes the problem part of a kernel-argument block - and the small storage-type predicates every entry
+// point of the library uses (dtype_ok, elem_bytes, vec16_elems, dtype_name, addr, all16).  Only the predicates live here: each entry point
+// keeps the ORDER of its refusals and its codes where they can be read (oeh_api.hip: validate / plan_attn, oeh_attn_decode.hip: plan_decode,
+// oeh_attn_bwd.hip: check_desc / fwd_train / bwd_run, and the *_check function next to every other entry point).  Host only, no device code.
 #pragma once
 #include "../../include/oeh.h"
 #include "oeh_attn_params.h"
@@ -12,6 +13,10 @@
 namespace oeh {
 
 inline bool dtype_ok(int d) { return d == OEH_F16 || d == OEH_BF16 || d == OEH_F32; }
+// of a storage type: bytes per element, elements per 16-byte vector, and its name in the *_variant strings
+inline int elem_bytes(int d) { return d == OEH_F32 ? 4 : d == OEH_I8 ? 1 : 2; }
+inline int vec16_elems(int d) { return d == OEH_F32 ? 4 : 8; }
+inline const char* dtype_name(int d) { return d == OEH_F32 ? "f32" : d == OEH_BF16 ? "bf16" : "f16"; }
 inline bool softmax_base_ok(int base) { return base == OEH_SOFTMAX_VANILLA || base == OEH_SOFTMAX_ONE; }
 
 // The descriptor sanity every entry point starts with: positive sizes (the head dim where the caller does not judge it itself) and a
@@ -39,12 +44,12 @@ inline bool desc_strides_in_range(const oeh_attn_desc* d) {
   return strides_in_range(d->q_stride) && strides_in_range(d->k_stride) && strides_in_range(d->v_stride) && strides_in_range(d->o_stride);
 }
 
-// 16-byte alignment of an OR of addresses and byte counts; of a tensor's rows: the pointer and its three strides (elements of elem_bytes),
+// 16-byte alignment of an OR of addresses and byte counts; of a tensor's rows: the pointer and its three strides (elements of eb bytes),
 // for the matrix-core paths' 16-B loads / 8..16-B stores
 inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
 inline bool all16(uintptr_t ored) { return (ored & 15) == 0; }
-inline bool aligned16(const void* p, const int64_t* st, int elem_bytes) {
-  return all16(addr(p) | (uintptr_t)(st[0] * elem_bytes) | (uintptr_t)(st[1] * elem_bytes) | (uintptr_t)(st[2] * elem_bytes));
+inline bool aligned16(const void* p, const int64_t* st, int eb) {
+  return all16(addr(p) | (uintptr_t)(st[0] * eb) | (uintptr_t)(st[1] * eb) | (uintptr_t)(st[2] * eb));
 }
 
 inline bool any_fq(const oeh_fq_desc* fq) { return fq != nullptr && (fq->scores.enable || fq->probs.enable || fq->ctx.enable); }

@@ -13,7 +13,32 @@
 // Every load of a thread (ids, table rows) is issued before its first store.
 #include "oeh_ln_row.h"
 
+#include <cmath>
+#include <cstdio>
+
 namespace oeh {
+
+enum { TAB_PLAIN = 0, TAB_GRID = 1, TAB_I8 = 2 };
+struct EmbedTab {
+  const void* w;       // the table: storage type (TAB_PLAIN, TAB_GRID) or int8 indices (TAB_I8)
+  const void* ids;     // null: lookup 0 reads row (b * S + s) of w ("dense rows")
+  long n_rows, row_stride, id_sb, id_ss;
+  int form, id64;
+  float scale, lo, hi;  // the weight grid of TAB_GRID / TAB_I8: fp32 scale (rounded to the storage type in the kernel), int_min, int_max
+};
+struct EmbedArgs {
+  EmbedTab tab[3];
+  FqP fq_sum[3];                  // [t]: behind the add of lookup t (t >= 1); [0] is never enabled
+  const float *gamma, *beta;      // gamma null: no LayerNorm, y is the final sum
+  void *sum, *y;                  // sum may be null
+  unsigned char *sum_idx, *y_idx; // tests; may be null
+  int* bad_rows;                  // may be null
+  long rows;
+  int S, cols;
+  long sum_stride, y_stride;
+  float eps;
+  FqP fq_out;
+};
 
 // thread t's chunks of row `id` of table tb, as fp32 values of the storage type IN
 template <int IN, int CH, int FORM, int NV = LnForm<IN, FORM>::NV>
@@ -92,7 +117,7 @@ __global__ __launch_bounds__(256) void oeh_embed_kernel(const EmbedArgs p) {
   const long row = Fm::row();
   if (FORM == LN_WAVE && row >= p.rows) return;  // (wave-uniform; this form has no workgroup barrier)
   const int nchunk = p.cols / NV;
-  const unsigned b = (unsigned)row / (unsigned)p.S, s = (unsigned)row - b * (unsigned)p.S;  // (rows < 2^31: oeh_api.hip)
+  const unsigned b = (unsigned)row / (unsigned)p.S, s = (unsigned)row - b * (unsigned)p.S;  // (rows < 2^31: embed_check)
   E* sr = p.sum != nullptr ? reinterpret_cast<E*>(p.sum) + row * p.sum_stride : nullptr;
   E* yr = reinterpret_cast<E*>(p.y) + row * p.y_stride;
 
@@ -152,33 +177,100 @@ __global__ __launch_bounds__(256) void oeh_embed_kernel(const EmbedArgs p) {
   ln_norm_stage<IN, CH, FORM>(v, acc, t, row, p.cols, nchunk, p.gamma, p.beta, p.eps, p.fq_out, p.y_idx, yr, red);
 }
 
-template <int IN, int FORM, int NT>
-static int launch_embed_form(const EmbedArgs& a, const int ch, hipStream_t st) {
-  const unsigned grid = (unsigned)(FORM == LN_WAVE ? (a.rows + 3) / 4 : a.rows);
-  return dispatch_ln_ch<IN, FORM>(ch, [&](auto c) {
-    hipLaunchKernelGGL((oeh_embed_kernel<IN, decltype(c)::value, FORM, NT>), dim3(grid), dim3(256), 0, st, a);
-    return launch_status();
+namespace {
+
+template <int NT>
+int launch_embed_nt(const EmbedArgs& a, const int in, const LnPlan pl, hipStream_t st) {
+  return launch_ln_rows(in, pl, a.rows, [&](auto t, auto form, auto ch, unsigned grid) {
+    hipLaunchKernelGGL((oeh_embed_kernel<decltype(t)::value, decltype(ch)::value, decltype(form)::value, NT>), dim3(grid), dim3(256), 0, st, a);
   });
 }
 
-template <int IN, int NT>
-static int launch_embed_nt(const EmbedArgs& a, LnPlan pl, hipStream_t st) {
-  switch (pl.form) {
-    case LN_WAVE: return launch_embed_form<IN, LN_WAVE, NT>(a, pl.ch, st);
-    case LN_BLOCK: return launch_embed_form<IN, LN_BLOCK, NT>(a, pl.ch, st);
-    default: return launch_embed_form<IN, LN_SCALAR, NT>(a, pl.ch, st);
+// oeh_embed_sum_quant / oeh_embed_sum_variant: every refusal in the order OEH_EINVAL -> OEH_ENOTSUP -> OEH_EALIGN, then whether the 16-byte forms apply
+int embed_check(const oeh_embed_desc* d, const float* gamma, const float* beta, const void* sum_out, const void* y, bool with_sum_idx,
+                bool with_y_idx, bool* vec16) {
+  if (d == nullptr || y == nullptr || d->n_tab < 1 || d->n_tab > 3 || d->cols < 1 || d->B < 0 || d->S < 0 || !dtype_ok(d->dtype)) return OEH_EINVAL;
+  if (d->reserved != 0 || d->reserved2 != 0 || d->sum_stride < 0 || d->y_stride < 0) return OEH_EINVAL;
+  const int64_t rows = (int64_t)d->B * d->S;
+  if (rows > 1 && (d->y_stride < d->cols || (sum_out != nullptr && d->sum_stride < d->cols))) return OEH_EINVAL;
+  for (int t = 0; t < d->n_tab; ++t) {
+    const oeh_embed_lookup& l = d->tab[t];
+    if (l.table == nullptr || (t >= 1 && l.ids == nullptr) || l.reserved != 0) return OEH_EINVAL;
+    if (l.ids == nullptr && l.n_rows < rows) return OEH_EINVAL;  // dense rows: one per (b, s)
+    if (l.n_rows < 0 || l.row_stride < 0 || l.id_stride_b < 0 || l.id_stride_s < 0) return OEH_EINVAL;
+    if ((l.id_dtype != OEH_ID_I32 && l.id_dtype != OEH_ID_I64) || l.form < OEH_TAB_PLAIN || l.form > OEH_TAB_I8) return OEH_EINVAL;
+    if (l.form != OEH_TAB_PLAIN && (!(l.scale > 0.0f) || !std::isfinite(l.scale) || !(l.int_min < l.int_max))) return OEH_EINVAL;
+  }
+  for (int t = 0; t < 3; ++t) {
+    if (d->fq_sum[t].enable && (t == 0 || t >= d->n_tab || !fq_grid_ok(d->fq_sum[t], false))) return OEH_EINVAL;
+  }
+  if (d->fq_out.enable && !fq_grid_ok(d->fq_out, false)) return OEH_EINVAL;
+  if (gamma == nullptr && (beta != nullptr || d->fq_out.enable || with_y_idx)) return OEH_EINVAL;
+  if ((with_sum_idx && !d->fq_sum[d->n_tab - 1].enable) || (with_y_idx && !d->fq_out.enable)) return OEH_EINVAL;
+  if (gamma != nullptr && !(d->eps >= 0.0f)) return OEH_EINVAL;
+  if (d->cols > kLnMaxCols || rows >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
+  for (int t = 0; t < d->n_tab; ++t) {
+    if (d->tab[t].form == OEH_TAB_I8 && (d->tab[t].int_min < -128.0f || d->tab[t].int_max > 127.0f)) return OEH_ENOTSUP;
+  }
+  if ((with_sum_idx && d->fq_sum[d->n_tab - 1].qmax > 255.0f) || (with_y_idx && d->fq_out.qmax > 255.0f)) return OEH_ENOTSUP;
+  const int eb = elem_bytes(d->dtype), nv = vec16_elems(d->dtype);
+  bool v16 = rows_vec16(d->dtype, d->cols, {d->y_stride, sum_out != nullptr ? d->sum_stride : 0}) && all16(addr(gamma) | addr(beta) | addr(sum_out) | addr(y));
+  for (int t = 0; t < d->n_tab; ++t) {
+    const oeh_embed_lookup& l = d->tab[t];
+    if (l.ids != nullptr && addr(l.ids) % (l.id_dtype == OEH_ID_I64 ? 8 : 4) != 0) return OEH_EALIGN;
+    if (addr(l.table) % (l.form == OEH_TAB_I8 ? 4 : eb) != 0) return OEH_EALIGN;
+    // (an int8 row is read nv BYTES at a time; a float row nv elements = 16 bytes)
+    v16 = v16 && rows_vec16(d->dtype, d->cols, {l.row_stride}) && (l.form == OEH_TAB_I8 ? addr(l.table) % nv == 0 : all16(addr(l.table)));
+  }
+  if (addr(y) % eb != 0 || addr(sum_out) % eb != 0 || addr(gamma) % 4 != 0 || addr(beta) % 4 != 0) return OEH_EALIGN;
+  *vec16 = v16;
+  return OEH_OK;
+}
+
+}  // namespace
+}  // namespace oeh
+
+using namespace oeh;
+
+extern "C" {
+
+int oeh_embed_sum_quant(const oeh_embed_desc* d, const float* gamma, const float* beta, void* sum_out, void* y, uint8_t* sum_idx, uint8_t* y_idx,
+                        int32_t* bad_rows, void* stream) {
+  bool vec16 = false;
+  const int rc = embed_check(d, gamma, beta, sum_out, y, sum_idx != nullptr, y_idx != nullptr, &vec16);
+  if (rc != OEH_OK) return rc;
+  if (addr(bad_rows) % 4 != 0) return OEH_EALIGN;
+  if ((int64_t)d->B * d->S == 0) return OEH_OK;
+  EmbedArgs a = {};
+  for (int t = 0; t < d->n_tab; ++t) {
+    const oeh_embed_lookup& l = d->tab[t];
+    a.tab[t] = EmbedTab{l.table, l.ids, l.n_rows, l.row_stride, l.id_stride_b, l.id_stride_s, l.form, l.id_dtype == OEH_ID_I64, l.scale, l.int_min, l.int_max};
+    a.fq_sum[t] = make_fq(&d->fq_sum[t]);
+  }
+  a.gamma = gamma; a.beta = beta; a.sum = sum_out; a.y = y; a.sum_idx = sum_idx; a.y_idx = y_idx; a.bad_rows = bad_rows;
+  a.rows = (long)d->B * d->S; a.S = d->S; a.cols = d->cols;
+  a.sum_stride = d->sum_stride; a.y_stride = d->y_stride;
+  a.eps = d->eps;
+  a.fq_out = make_fq(&d->fq_out);
+  const LnPlan pl = ln_plan(d->cols, d->dtype, vec16);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  switch (d->n_tab) {
+    case 1: return launch_embed_nt<1>(a, d->dtype, pl, st);
+    case 2: return launch_embed_nt<2>(a, d->dtype, pl, st);
+    default: return launch_embed_nt<3>(a, d->dtype, pl, st);
   }
 }
 
-int launch_embed(const EmbedArgs& a, int in, int n_tab, LnPlan pl, hipStream_t st) {
-  return dispatch_in(in, [&](auto t) {
-    constexpr int IN = decltype(t)::value;
-    switch (n_tab) {
-      case 1: return launch_embed_nt<IN, 1>(a, pl, st);
-      case 2: return launch_embed_nt<IN, 2>(a, pl, st);
-      default: return launch_embed_nt<IN, 3>(a, pl, st);
-    }
-  });
+const char* oeh_embed_sum_variant(const oeh_embed_desc* d) {
+  static thread_local char name[48];
+  bool vec16 = false;
+  // (the outputs and gamma / beta are taken as given with every part and 16-byte aligned, as oeh_resid_ln_variant does)
+  const void* const aligned = reinterpret_cast<const void*>((uintptr_t)4096);
+  if (embed_check(d, static_cast<const float*>(aligned), nullptr, d != nullptr && d->sum_stride != 0 ? aligned : nullptr, aligned, false, false, &vec16) != OEH_OK)
+    return nullptr;
+  const LnPlan pl = ln_plan(d->cols, d->dtype, vec16);
+  std::snprintf(name, sizeof name, "embed/%s/CH%d/T%d/%s", ln_form_name(pl.form), pl.ch, d->n_tab, dtype_name(d->dtype));
+  return name;
 }
 
-}  // namespace oeh
+}  // extern "C"

@@ -32,15 +32,41 @@
 // is 52-55 us = 1.1 PFLOP/s (40 us with the DMA and the barriers knocked out: the matrix core at the clock it holds under this load).
 #include "../../include/oeh.h"
 #include "oeh_common.h"
-#include "oeh_gemm.h"
 #include "oeh_launch.h"
+#include "oeh_desc.h"
 
 #include <cstdio>
+#include <cstring>
 #include <type_traits>
 #include <utility>
 #include <cstdlib>
 
 namespace oeh {
+
+struct GemmSeg {            // one column segment (a projection): columns [n0, n0 + E)
+  float alpha;              // weight scale
+  FqP f;                    // output quantiser
+  signed char* out;         // centred indices: (B, S, E) or (B, H, 64, S) [transpose]
+  float* y;                 // dequantised values (B, S, E) fp32 with row stride y_ld, or nullptr
+  long y_ld;
+  int transpose;
+  const int* acc_add;       // int8 form: per-column integer added to the int32 accumulator (E entries), or nullptr
+};
+
+struct GemmParams {
+  const void* a;            // (M, 2K) fp16 pairs, or (M, K) fp16 [pairs == 0]
+  const void* w;            // (N, K) fp16
+  const float* bias;        // (N) fp32
+  long lda, ldw;            // row strides in elements
+  int M, N, K, pairs;
+  int MT, NT;               // tiles
+  int dbg;                  // diagnostic knock-outs (launch_gemm), 0 in production
+  unsigned magic_s;         // floor(2^32 / S)
+  int E, S, H;              // segment width, rows per batch element, heads per segment (E = 64 H)
+  GemmSeg seg[3];
+};
+
+constexpr int kGemmBK = 32;  // K must be a multiple (64 in the int8 form: a step is 64 bytes of a row)
 
 // The outputs leave WRITE-THROUGH (as the attention kernels' do, oeh_common.h: store_wt16): a plain store leaves the line dirty in the XCD's L2
 // and what is still there at the end of the kernel goes to memory after the last wave, where nothing overlaps it (out_proj, 25 MB of
@@ -523,7 +549,7 @@ static int launch_gemm_t(const GemmParams& P, hipStream_t st) {
 // Tile choice.  128 x 288 (two workgroups per CU, 144 accumulator registers) when the problem fills the chip with such tiles and the
 // columns divide evenly enough; 64 x 192 (four workgroups per CU) otherwise: narrow outputs (out_proj: N = 768 is 4 x 192) and
 // problems of fewer than 512 large tiles.
-int launch_gemm(const GemmParams& P0, hipStream_t st) {
+static int launch_gemm(const GemmParams& P0, hipStream_t st) {
   GemmParams P = P0;
   // diagnostic switches (include/oeh_debug.h), inert unless OEH_DEBUG_HOOKS=1: OEH_GEMM_DBG knocks parts of the kernel out for timing
   // (results are then wrong), OEH_GEMM_TILE = 1 | 2 forces the 128 x 288 | 64 x 192 tile
@@ -560,3 +586,37 @@ int launch_gemm(const GemmParams& P0, hipStream_t st) {
 }
 
 }  // namespace oeh
+
+using namespace oeh;
+
+extern "C" int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* bias, int64_t B, int32_t S, int32_t K, int32_t E, int32_t n_seg,
+                                 const oeh_proj_seg* segs, int64_t lda, int64_t ldw, void* stream) {
+  if (a == nullptr || w == nullptr || bias == nullptr || segs == nullptr || B <= 0 || S <= 0 || K <= 0 || E <= 0 || n_seg < 1 || n_seg > 3) return OEH_EINVAL;
+  if ((K % kGemmBK) != 0 || (E & 63) != 0 || (S & 15) != 0 || B * (int64_t)S > 0x7fffffffLL) return OEH_ENOTSUP;
+  if (pairs < 0 || pairs > 3) return OEH_EINVAL;
+  const int64_t aeb = pairs == 2 ? 4 : pairs == 3 ? 1 : 2;  // (pairs == 2: a is the fp32 activation matrix itself; 3: int8 a and w)
+  const int64_t web = pairs == 3 ? 1 : 2;
+  if (pairs == 3 && (K & 63) != 0) return OEH_ENOTSUP;
+  if (lda < (pairs == 1 ? 2 : 1) * (int64_t)K || ldw < K) return OEH_EINVAL;
+  if (!all16(addr(a) | addr(w) | (uintptr_t)(lda * aeb) | (uintptr_t)(ldw * web))) return OEH_EALIGN;
+  if (B * (int64_t)S * lda * aeb >= 0xffffffffLL || (int64_t)n_seg * E * ldw * web >= 0xffffffffLL) return OEH_ENOTSUP;  // (32-bit lane offsets)
+  GemmParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.a = a; P.w = w; P.bias = bias; P.lda = lda; P.ldw = ldw; P.M = (int)(B * S); P.N = n_seg * E; P.K = K; P.pairs = pairs;
+  P.E = E; P.S = S; P.H = E / 64;
+  for (int i = 0; i < n_seg; ++i) {
+    const oeh_proj_seg& g = segs[i];
+    if (g.out == nullptr && g.y == nullptr) return OEH_EINVAL;
+    if (!(g.scale > 0.0f) || g.zero_point < 0.0f || g.zero_point > 255.0f || g.zero_point != std::nearbyint(g.zero_point)) return OEH_EINVAL;
+    if ((addr(g.out) & 15) != 0 || (addr(g.y) & 3) != 0) return OEH_EALIGN;
+    if (g.y != nullptr && g.y_stride_row < E) return OEH_EINVAL;
+    if (g.y != nullptr && (12 * g.y_stride_row + 16) * 4 >= 0xffffffffLL) return OEH_ENOTSUP;  // (32-bit lane offsets of the value stores: y_voff)
+    GemmSeg& t = P.seg[i];
+    t.alpha = g.alpha; t.out = reinterpret_cast<signed char*>(g.out); t.y = g.y; t.y_ld = g.y_stride_row; t.transpose = g.transpose ? 1 : 0;
+    t.acc_add = pairs == 3 ? g.acc_add : nullptr;
+    if ((addr(g.acc_add) & 3) != 0) return OEH_EALIGN;
+    const oeh_fq f = {1, g.scale, g.zero_point, 255.0f, nullptr};
+    t.f = make_fq(&f);
+  }
+  return launch_gemm(P, reinterpret_cast<hipStream_t>(stream));
+}

@@ -1,12 +1,45 @@
-// The row arithmetic that the block-tail kernel (oeh_ln.hip) and the embedding front (oeh_embed.hip) share, from the point where a thread holds
-// its chunks of the summed row in registers: sum quantiser -> sum output -> first moment, then second moment -> rstd -> affine -> output
-// quantiser -> store (include/oeh.h: oeh_resid_ln_quant has the formulas and their order).  One text: the two kernels give the same bits for the
+// What the LayerNorm-row family - the block-tail kernel (oeh_ln.hip), the embedding front (oeh_embed.hip) and the training tail
+// (oeh_ln_train.hip) - shares.  Host: the launch forms (ln_plan), the one launcher over IN x FORM x CH (launch_ln_rows), the "rows are vector
+// multiples" predicate and the form's name.  Device: a thread's chunk loads and stores, and the row arithmetic from the point where a thread
+// holds its chunks of the summed row in registers: sum quantiser -> sum output -> first moment, then second moment -> rstd -> affine -> output
+// quantiser -> store (include/oeh.h: oeh_resid_ln_quant has the formulas and their order).  One text: the kernels give the same bits for the
 // same row in the same launch form, because there is no second copy of a summation order to drift.
 #pragma once
 #include "oeh_stream.h"
 #include "oeh_launch.h"
+#include "oeh_desc.h"
+
+#include <initializer_list>
 
 namespace oeh {
+
+// ---- host: which of the three launch forms a problem takes and with how many accesses per thread (CH), for the launches and the
+// *_variant names alike
+enum { LN_WAVE = 0, LN_BLOCK = 1, LN_SCALAR = 2 };
+constexpr int kLnWaveCols = 1024, kLnMaxCols = 8192;
+struct LnPlan {
+  int form, ch;
+};
+// vec16: every base pointer is 16-byte aligned and cols and every row stride are multiples of the 16-byte vector (4 fp32 / 8 16-bit elements)
+inline LnPlan ln_plan(const int cols, const int in, const bool vec16) {
+  const int nv = vec16_elems(in);
+  auto pow2_at_least = [](int need, int lo) { while (lo < need) lo *= 2; return lo; };
+  if (!vec16) {
+    const int need = (cols + 255) / 256;
+    return LnPlan{LN_SCALAR, need <= 1 ? 1 : need <= 4 ? 4 : need <= 16 ? 16 : 32};
+  }
+  const int chunks = cols / nv;
+  if (cols <= kLnWaveCols) return LnPlan{LN_WAVE, pow2_at_least((chunks + 63) / 64, 1)};
+  return LnPlan{LN_BLOCK, pow2_at_least((chunks + 255) / 256, 1)};
+}
+inline const char* ln_form_name(const int form) { return form == LN_WAVE ? "wave" : form == LN_BLOCK ? "block" : "scalar"; }
+// the stride half of vec16: cols and every row stride that is in use (the caller passes 0 for one that is not) are vector multiples
+inline bool rows_vec16(const int dtype, const long cols, std::initializer_list<int64_t> strides) {
+  const int nv = vec16_elems(dtype);
+  bool ok = cols % nv == 0;
+  for (const int64_t s : strides) ok = ok && s % nv == 0;
+  return ok;
+}
 
 // what a value becomes when it is stored in the storage type and read back
 template <int IN>
@@ -23,6 +56,32 @@ struct LnForm {
   static __device__ __forceinline__ int thread() { return FORM == LN_WAVE ? (int)(threadIdx.x & 63) : (int)threadIdx.x; }
   static __device__ __forceinline__ long row() { return FORM == LN_WAVE ? (long)blockIdx.x * 4 + (threadIdx.x >> 6) : (long)blockIdx.x; }
 };
+
+// chunk ch of a row of the storage type <-> NV fp32 values: one element in the scalar form, one 16-byte access otherwise.  (oeh_stream.h's rule:
+// the sites below and in oeh_ln.hip / oeh_embed.hip that still spell this pair out change their kernels' instruction streams on the helper -
+// profiles/entry_points.txt lists them.)
+template <int IN, int FORM, int NV>
+__device__ __forceinline__ void load_chunk(const typename In<IN>::elem* rowp, const int ch, float (&out)[NV]) {
+  if constexpr (FORM == LN_SCALAR) out[0] = In<IN>::to_f32(rowp[ch]);
+  else Vec16<IN>::load(rowp + (long)ch * NV, out);
+}
+template <int IN, int FORM, int NV>
+__device__ __forceinline__ void store_chunk(typename In<IN>::elem* rowp, const int ch, const float (&v)[NV]) {
+  if constexpr (FORM == LN_SCALAR) rowp[ch] = In<IN>::from_f32(v[0]);
+  else Vec16<IN>::store(rowp + (long)ch * NV, v);
+}
+// NV fp32 values from p (16-byte aligned unless NV == 1)
+template <int NV>
+__device__ __forceinline__ void load_f32(const float* p, float (&out)[NV]) {
+  if constexpr (NV == 1) out[0] = p[0];
+  else {
+#pragma unroll
+    for (int i = 0; i < NV; i += 4) {
+      const f4 w = *reinterpret_cast<const f4*>(p + i);
+      out[i] = w[0]; out[i + 1] = w[1]; out[i + 2] = w[2]; out[i + 3] = w[3];
+    }
+  }
+}
 
 // ---- sum quantiser, sum output, first moment: returns this thread's share of sum(s); v becomes the quantised, storage-rounded sum
 template <int IN, int CH, int FORM, int NV = LnForm<IN, FORM>::NV>
@@ -158,6 +217,27 @@ inline int dispatch_ln_ch(const int ch, F&& f) {
     }
   }
 #undef OEH_CH
+}
+
+// ---- the launch of a plan: f(IN, FORM, CH as std::integral_constants, grid) launches the kernel instantiation; grid is a workgroup per row,
+// in the wave form one per four rows (a kernel with a grid of its own ignores it)
+template <class F>
+inline int launch_ln_rows(const int in, const LnPlan pl, const long rows, F&& f) {
+  return dispatch_in(in, [&](auto t) {
+    auto go = [&](auto form) {
+      constexpr int FORM = decltype(form)::value;
+      const unsigned grid = (unsigned)(FORM == LN_WAVE ? (rows + 3) / 4 : rows);
+      return dispatch_ln_ch<decltype(t)::value, FORM>(pl.ch, [&](auto c) {
+        f(t, form, c, grid);
+        return launch_status();
+      });
+    };
+    switch (pl.form) {
+      case LN_WAVE: return go(std::integral_constant<int, LN_WAVE>{});
+      case LN_BLOCK: return go(std::integral_constant<int, LN_BLOCK>{});
+      default: return go(std::integral_constant<int, LN_SCALAR>{});
+    }
+  });
 }
 
 }  // namespace oeh

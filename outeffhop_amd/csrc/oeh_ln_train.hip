@@ -84,29 +84,7 @@ __device__ __forceinline__ void drop_scale(float (&v)[NV], const int j0, const l
   }
 }
 
-template <int IN, int FORM, int NV>
-__device__ __forceinline__ void load_chunk(const typename In<IN>::elem* rowp, const int ch, float (&out)[NV]) {
-  if constexpr (FORM == LN_SCALAR) out[0] = In<IN>::to_f32(rowp[ch]);
-  else Vec16<IN>::load(rowp + (long)ch * NV, out);
-}
-template <int IN, int FORM, int NV>
-__device__ __forceinline__ void store_chunk(typename In<IN>::elem* rowp, const int ch, const float (&v)[NV]) {
-  if constexpr (FORM == LN_SCALAR) rowp[ch] = In<IN>::from_f32(v[0]);
-  else Vec16<IN>::store(rowp + (long)ch * NV, v);
-}
-// NV fp32 values from / to p (16-byte aligned unless NV == 1)
-template <int NV>
-__device__ __forceinline__ void load_f32(const float* p, float (&out)[NV]) {
-  if constexpr (NV == 1) out[0] = p[0];
-  else {
-#pragma unroll
-    for (int i = 0; i < NV; i += 4) {
-      const f4 w = *reinterpret_cast<const f4*>(p + i);
-      out[i] = w[0]; out[i + 1] = w[1]; out[i + 2] = w[2]; out[i + 3] = w[3];
-    }
-  }
-}
-// NV float64 values from / to p (16-byte aligned unless NV == 1): the backward's column partials
+// (load_chunk, store_chunk, load_f32: oeh_ln_row.h)  NV float64 values from / to p (16-byte aligned unless NV == 1): the backward's column partials
 typedef double d2 __attribute__((ext_vector_type(2)));
 template <int NV>
 __device__ __forceinline__ void load_f64(const double* p, double (&out)[NV]) {
@@ -455,9 +433,7 @@ int check_fwd(const oeh_ln_train_desc* d) { return d == nullptr ? OEH_EINVAL : c
 int check_bwd(const oeh_ln_train_desc* d, const bool with_dr) { return d == nullptr ? OEH_EINVAL : check_desc(d, d->x_stride, with_dr, d->r_stride); }
 
 bool strides_vec16(const oeh_ln_train_desc* d, const bool with_r, const bool with_dsum) {
-  const int nv = d->dtype == OEH_F32 ? 4 : 8;
-  return d->cols % nv == 0 && d->x_stride % nv == 0 && d->sum_stride % nv == 0 && d->y_stride % nv == 0 && (!with_r || d->r_stride % nv == 0) &&
-         (!with_dsum || d->dsum_stride % nv == 0);
+  return rows_vec16(d->dtype, d->cols, {d->x_stride, d->sum_stride, d->y_stride, with_r ? d->r_stride : 0, with_dsum ? d->dsum_stride : 0});
 }
 
 // the backward's slabs: workgroups of the row kernel (= partials in `work`) and rows per group (a workgroup; in the wave form a wave)
@@ -475,42 +451,6 @@ BwdPlan bwd_plan(const long rows, const int cols, const int in, const bool vec16
   b.workgroups = (groups + per_wg - 1) / per_wg;
   return b;
 }
-
-template <template <int, int, int, bool> class K, class A>
-int launch_forms(const A& a, const int in, const LnPlan pl, const bool drop, const unsigned grid, hipStream_t st) {
-  return dispatch_in(in, [&](auto t) {
-    constexpr int IN = decltype(t)::value;
-    auto go = [&](auto form) {
-      constexpr int FORM = decltype(form)::value;
-      return dispatch_ln_ch<IN, FORM>(pl.ch, [&](auto c) {
-        constexpr int CH = decltype(c)::value;
-        if (drop) K<IN, CH, FORM, true>::launch(a, grid, st);
-        else K<IN, CH, FORM, false>::launch(a, grid, st);
-        return launch_status();
-      });
-    };
-    switch (pl.form) {
-      case LN_WAVE: return go(std::integral_constant<int, LN_WAVE>{});
-      case LN_BLOCK: return go(std::integral_constant<int, LN_BLOCK>{});
-      default: return go(std::integral_constant<int, LN_SCALAR>{});
-    }
-  });
-}
-template <int IN, int CH, int FORM, bool DROP>
-struct FwdK {
-  static void launch(const LnTrainArgs& a, unsigned grid, hipStream_t st) {
-    hipLaunchKernelGGL((oeh_ln_train_fwd_kernel<IN, CH, FORM, DROP>), dim3(grid), dim3(256), 0, st, a);
-  }
-};
-template <int IN, int CH, int FORM, bool DROP>
-struct BwdK {
-  static void launch(const LnTrainBwdArgs& a, unsigned grid, hipStream_t st) {
-    hipLaunchKernelGGL((oeh_ln_train_bwd_kernel<IN, CH, FORM, DROP>), dim3(grid), dim3(256), 0, st, a);
-  }
-};
-
-const char* form_name(const int form) { return form == LN_WAVE ? "wave" : form == LN_BLOCK ? "block" : "scalar"; }
-const char* dtype_name(const int dtype) { return dtype == OEH_F32 ? "f32" : dtype == OEH_BF16 ? "bf16" : "f16"; }
 
 }  // namespace
 }  // namespace oeh
@@ -533,9 +473,12 @@ int oeh_drop_resid_ln_fwd(const oeh_ln_train_desc* d, const void* x, const void*
   a.x_stride = d->x_stride; a.r_stride = d->r_stride; a.sum_stride = d->sum_stride; a.y_stride = d->y_stride;
   a.eps = d->eps;
   a.drop = make_drop(d->drop);
-  const LnPlan pl = ln_plan(d->cols, d->dtype, vec16);
-  const unsigned grid = (unsigned)(pl.form == LN_WAVE ? (d->rows + 3) / 4 : d->rows);
-  return launch_forms<FwdK>(a, d->dtype, pl, d->drop.p > 0.0f, grid, reinterpret_cast<hipStream_t>(stream));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return launch_ln_rows(d->dtype, ln_plan(d->cols, d->dtype, vec16), d->rows, [&](auto in, auto form, auto ch, unsigned grid) {
+    constexpr int IN = decltype(in)::value, CH = decltype(ch)::value, FORM = decltype(form)::value;
+    if (d->drop.p > 0.0f) hipLaunchKernelGGL((oeh_ln_train_fwd_kernel<IN, CH, FORM, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((oeh_ln_train_fwd_kernel<IN, CH, FORM, false>), dim3(grid), dim3(256), 0, st, a);
+  });
 }
 
 size_t oeh_drop_resid_ln_bwd_work_bytes(const oeh_ln_train_desc* d) {
@@ -567,7 +510,12 @@ int oeh_drop_resid_ln_bwd(const oeh_ln_train_desc* d, const void* dy, const void
   a.drop = make_drop(d->drop);
   const BwdPlan pl = bwd_plan(d->rows, d->cols, d->dtype, vec16);
   a.rows_per_group = pl.rows_per_group;
-  const int rc2 = launch_forms<BwdK>(a, d->dtype, pl.ln, d->drop.p > 0.0f, (unsigned)pl.workgroups, st);
+  const dim3 grid((unsigned)pl.workgroups);  // (the slabs' own grid, not a workgroup per row)
+  const int rc2 = launch_ln_rows(d->dtype, pl.ln, d->rows, [&](auto in, auto form, auto ch, unsigned) {
+    constexpr int IN = decltype(in)::value, CH = decltype(ch)::value, FORM = decltype(form)::value;
+    if (d->drop.p > 0.0f) hipLaunchKernelGGL((oeh_ln_train_bwd_kernel<IN, CH, FORM, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((oeh_ln_train_bwd_kernel<IN, CH, FORM, false>), grid, dim3(256), 0, st, a);
+  });
   if (rc2 != OEH_OK) return rc2;
   hipLaunchKernelGGL(oeh_ln_train_cols_kernel, dim3((unsigned)((d->cols + 31) / 32)), dim3(1024), 0, st, a.work, (int)pl.workgroups, d->cols, dgamma, dbeta);
   return launch_status();
@@ -594,10 +542,10 @@ const char* oeh_drop_resid_ln_variant(const oeh_ln_train_desc* d, int backward) 
   const char* drop = d->drop.p > 0.0f ? "/drop" : "";
   if (!backward) {
     const LnPlan pl = ln_plan(d->cols, d->dtype, vec16);
-    std::snprintf(name, sizeof name, "ln_train/fwd/%s/CH%d/%s%s", form_name(pl.form), pl.ch, dtype_name(d->dtype), drop);
+    std::snprintf(name, sizeof name, "ln_train/fwd/%s/CH%d/%s%s", ln_form_name(pl.form), pl.ch, dtype_name(d->dtype), drop);
   } else {
     const BwdPlan pl = bwd_plan(std::max<long>(d->rows, 1), d->cols, d->dtype, vec16);
-    std::snprintf(name, sizeof name, "ln_train/bwd/%s/CH%d/%s%s/G%ldx%ld", form_name(pl.ln.form), pl.ln.ch, dtype_name(d->dtype), drop, pl.workgroups,
+    std::snprintf(name, sizeof name, "ln_train/bwd/%s/CH%d/%s%s/G%ldx%ld", ln_form_name(pl.ln.form), pl.ln.ch, dtype_name(d->dtype), drop, pl.workgroups,
                   pl.rows_per_group);
   }
   return name;

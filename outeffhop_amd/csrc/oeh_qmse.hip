@@ -26,6 +26,7 @@
 // every sum has a fixed order, so results are bitwise reproducible.
 #include "oeh_stream.h"
 #include "oeh_launch.h"
+#include "oeh_desc.h"
 
 namespace oeh {
 
@@ -160,8 +161,7 @@ __global__ __launch_bounds__(256) void oeh_qmse_merge_kernel(const double* __res
   if (lane == 0) loss[k] = accumulate ? loss[k] + s : s;
 }
 
-}  // namespace
-
+// workgroups of a pass (= records in `work`), with the chunks and the chunks per workgroup behind that number
 long qmse_blocks(long n, long* nch_out, long* cpb_out) {
   const long nch = chunks_for(n, kQmseC);
   const long cpb = (nch + kQmseMaxBlocks - 1) / kQmseMaxBlocks;
@@ -170,7 +170,23 @@ long qmse_blocks(long n, long* nch_out, long* cpb_out) {
   return (nch + cpb - 1) / cpb;
 }
 
-int launch_quant_mse(const void* x, long n, int in, const float* cand, int K, double* loss, int accumulate, void* work, hipStream_t st) {
+}  // namespace
+}  // namespace oeh
+
+using namespace oeh;
+
+extern "C" {
+
+size_t oeh_quant_mse_work_bytes(int64_t n, int32_t K) {
+  if (n < 1 || K < 1) return 0;
+  return (size_t)qmse_blocks(n, nullptr, nullptr) * (size_t)(K < OEH_QMSE_SLICE ? K : OEH_QMSE_SLICE) * sizeof(double);
+}
+
+int oeh_quant_mse(const void* x, int64_t n, int32_t dtype, const float* cand, int32_t K, double* loss, int32_t accumulate, void* work,
+                  void* stream) {
+  if (x == nullptr || cand == nullptr || loss == nullptr || work == nullptr || n < 1 || K < 1 || !dtype_ok(dtype)) return OEH_EINVAL;
+  if ((addr(cand) & 15) != 0 || (addr(loss) & 7) != 0 || (addr(work) & 7) != 0 || (addr(x) & (uintptr_t)(elem_bytes(dtype) - 1)) != 0) return OEH_EALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   long nch, cpb;
   const long blocks = qmse_blocks(n, &nch, &cpb);
   const QmseCand* c = reinterpret_cast<const QmseCand*>(cand);
@@ -178,14 +194,14 @@ int launch_quant_mse(const void* x, long n, int in, const float* cand, int K, do
   const bool f64 = K <= OEH_QMSE_F64_K;
   for (int k0 = 0; k0 < K; k0 += kQmseSlice) {
     const int ks = K - k0 < kQmseSlice ? K - k0 : kQmseSlice;
-    dispatch_in(in, [&](auto t) {
+    dispatch_in(dtype, [&](auto t) {
       constexpr int IN = decltype(t)::value;
       if (f64) hipLaunchKernelGGL((oeh_qmse_chunk_kernel<IN, true>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, nch, cpb, c + k0, ks, w);
       else hipLaunchKernelGGL((oeh_qmse_chunk_kernel<IN, false>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, nch, cpb, c + k0, ks, w);
     });
-    hipLaunchKernelGGL(oeh_qmse_merge_kernel, dim3((unsigned)((ks + 3) / 4)), dim3(256), 0, st, w, (int)blocks, ks, loss + k0, accumulate);
+    hipLaunchKernelGGL(oeh_qmse_merge_kernel, dim3((unsigned)((ks + 3) / 4)), dim3(256), 0, st, w, (int)blocks, ks, loss + k0, accumulate != 0);
   }
   return launch_status();
 }
 
-}  // namespace oeh
+}  // extern "C"

@@ -4,6 +4,7 @@
 // (range_estimators.py:71-72,96-97).  All HBM-bound: 16-B accesses, one pass where the row fits LDS.
 #include "oeh_stream.h"
 #include "oeh_launch.h"
+#include "oeh_desc.h"
 
 namespace oeh {
 
@@ -134,7 +135,7 @@ static bool launch_softmax_rows_wave(const void* x, void* y, long rows, int cols
   return true;
 }
 
-int launch_softmax_rows(const void* x, void* y, long rows, int cols, int in, int base, int clip, float w, float g, hipStream_t st) {
+static int launch_softmax_rows(const void* x, void* y, long rows, int cols, int in, int base, int clip, float w, float g, hipStream_t st) {
   {  // rows that fit a wave's registers (<= 2048 fp32 / 4096 16-bit elements, multiple of the 16-B vector)
     const bool done = dispatch_in(in, [&](auto t) { return launch_softmax_rows_wave<decltype(t)::value>(x, y, rows, cols, base, clip, w, g, st); });
     if (done) return launch_status();
@@ -202,9 +203,9 @@ __global__ __launch_bounds__(256) void oeh_fake_quant_vec_kernel(const void* __r
   }
 }
 
-int launch_fake_quant(const void* x, void* y, unsigned char* idx, long n, int in, FqP f, hipStream_t st) {
+static int launch_fake_quant(const void* x, void* y, unsigned char* idx, long n, int in, FqP f, hipStream_t st) {
   if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 && (reinterpret_cast<uintptr_t>(idx) & 3) == 0 && (idx == nullptr || f.qmax <= 255.0f)) {
-    const long nvec = n / (in == IN_F32 ? 4 : 8);
+    const long nvec = n / vec16_elems(in);
     long blocks = (nvec + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
@@ -492,7 +493,7 @@ element_kernel:
   }
 }
 
-int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_b, long hs_t, const float* w1, const float* b1,
+static int launch_gate(const void* hidden, int in, int B, int T, int H, int d, long hs_b, long hs_t, const float* w1, const float* b1,
                 const float* w2, const float* b2, int m_units, int pool, float scaling, float* out, hipStream_t st) {
   const bool done = dispatch_in(in, [&](auto t) {
     return launch_gate_fast<decltype(t)::value>(hidden, B, T, H, d, hs_b, hs_t, w1, b1, w2, b2, m_units, !pool, scaling, out, st);
@@ -589,11 +590,11 @@ __global__ __launch_bounds__(256) void oeh_minmax_vec_kernel(const void* __restr
   }
 }
 
-int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st) {
+static int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st) {
   int* keys = reinterpret_cast<int*>(out2);
   hipLaunchKernelGGL(oeh_minmax_init_kernel, dim3(1), dim3(1), 0, st, keys);
   if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-    const long nvec = n / (in == IN_F32 ? 4 : 8);
+    const long nvec = n / vec16_elems(in);
     long vb = (nvec + 1023) / 1024;  // four vectors per thread
     if (vb > 2048) vb = 2048;
     if (vb < 1) vb = 1;
@@ -610,3 +611,43 @@ int launch_minmax(const void* x, long n, int in, float* out2, hipStream_t st) {
 }
 
 }  // namespace oeh
+
+using namespace oeh;
+
+extern "C" {
+
+int oeh_softmax_rows(const void* x, void* y, int64_t rows, int32_t cols, int32_t dtype, int32_t softmax_base, int32_t clip,
+                     float gamma, float eta, void* stream) {
+  if (x == nullptr || y == nullptr || rows < 0 || cols <= 0 || !dtype_ok(dtype)) return OEH_EINVAL;
+  if (!softmax_base_ok(softmax_base)) return OEH_EINVAL;
+  if (rows == 0) return OEH_OK;
+  const float w = (float)((double)eta - (double)gamma);
+  return launch_softmax_rows(x, y, rows, cols, dtype, softmax_base, clip ? 1 : 0, w, gamma, reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_fake_quant(const void* x, void* y, uint8_t* idx, int64_t n, int32_t dtype, float scale, float zero_point, float qmax,
+                   void* stream) {
+  if (x == nullptr || n < 0 || !dtype_ok(dtype)) return OEH_EINVAL;
+  if (!fq_grid_ok(scale, zero_point, qmax, false)) return OEH_EINVAL;
+  if (idx != nullptr && qmax > 255.0f) return OEH_ENOTSUP;
+  if (n == 0 || (y == nullptr && idx == nullptr)) return OEH_OK;
+  const oeh_fq f = {1, scale, zero_point, qmax, nullptr};
+  return launch_fake_quant(x, y, idx, n, dtype, make_fq(&f), reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_gate_fwd(const void* hidden, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t d, int64_t hidden_stride_b,
+                 int64_t hidden_stride_t, const float* w1, const float* b1, const float* w2, const float* b2, int32_t hidden_units,
+                 int32_t per_head_pool, float scaling, float* gate_out, void* stream) {
+  if (hidden == nullptr || w1 == nullptr || b1 == nullptr || gate_out == nullptr || !dtype_ok(dtype)) return OEH_EINVAL;
+  if (B <= 0 || T <= 0 || H <= 0 || d <= 0 || hidden_units < 0) return OEH_EINVAL;
+  if (hidden_units > 0 && (w2 == nullptr || b2 == nullptr)) return OEH_EINVAL;
+  return launch_gate(hidden, dtype, B, T, H, d, hidden_stride_b, hidden_stride_t, w1, b1, w2, b2, hidden_units,
+                     per_head_pool ? 1 : 0, scaling, gate_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int oeh_minmax(const void* x, int64_t n, int32_t dtype, float* out2, void* stream) {
+  if (x == nullptr || out2 == nullptr || n <= 0 || !dtype_ok(dtype)) return OEH_EINVAL;
+  return launch_minmax(x, n, dtype, out2, reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -23,6 +23,7 @@
 // same chain, rows in ascending order in float64.  Plain launches on one stream: no atomics, no allocation, no host synchronisation.
 #include "oeh_stream.h"
 #include "oeh_launch.h"
+#include "oeh_desc.h"
 
 namespace oeh {
 
@@ -300,25 +301,41 @@ __global__ __launch_bounds__(64) void oeh_stats_meter_kernel(const float* __rest
   if (lane == 0) meter_store(meter, accumulate, si, sk, rows);
 }
 
-}  // namespace
-
+// records per row in `work`: 0 in the one-wave form
 long stats_chunks(long cols) { return cols <= kStatsW ? 0 : chunks_for(cols, kStatsC); }
 
-int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, int in, double eps, float* stats, double* meter, int accumulate, void* work,
-                         hipStream_t st) {
+}  // namespace
+}  // namespace oeh
+
+using namespace oeh;
+
+extern "C" {
+
+size_t oeh_outlier_stats_work_bytes(int64_t rows, int64_t cols) {
+  if (rows < 1 || cols < 1) return 0;
+  return (size_t)rows * (size_t)stats_chunks(cols) * OEH_STATS_RECORD_BYTES;
+}
+
+int oeh_outlier_stats(const void* x, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, double eps, float* stats, double* meter,
+                      int32_t accumulate, void* work, void* stream) {
+  if (x == nullptr || stats == nullptr || rows < 1 || cols < 1 || row_stride < cols || !dtype_ok(dtype) || !(eps >= 0.0)) return OEH_EINVAL;
+  if (accumulate < 0 || accumulate > 3 || (accumulate != 0 && meter == nullptr)) return OEH_EINVAL;
   const long nch = stats_chunks(cols);
-  const int eb = in == IN_F32 ? 4 : 2;
+  if (nch > 0 && work == nullptr) return OEH_EINVAL;
+  const int eb = elem_bytes(dtype);
+  if ((addr(stats) & 15) != 0 || (addr(meter) & 7) != 0 || (nch > 0 && (addr(work) & 7) != 0) || (addr(x) & (uintptr_t)(eb - 1)) != 0) return OEH_EALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long blocks4 = (rows + 3) / 4;
   if (blocks4 >= ((long)1 << 31) || rows * (nch > 0 ? nch : 1) >= ((long)1 << 31)) return OEH_ENOTSUP;
   if (nch == 0) {
-    dispatch_in(in, [&](auto t) {
+    dispatch_in(dtype, [&](auto t) {
       constexpr int IN = decltype(t)::value;
       hipLaunchKernelGGL(oeh_stats_wave_kernel<IN>, dim3((unsigned)blocks4), dim3(256), 0, st, x, rows, (int)cols, row_stride * eb, eps, stats);
     });
   } else {
     StatsRec* w = reinterpret_cast<StatsRec*>(work);
     const unsigned grid = (unsigned)(rows * nch);
-    dispatch_in(in, [&](auto t) {
+    dispatch_in(dtype, [&](auto t) {
       constexpr int IN = decltype(t)::value;
       hipLaunchKernelGGL(oeh_stats_chunk_kernel<IN>, dim3(grid), dim3(256), 0, st, x, cols, row_stride * eb, (int)nch, w);
     });
@@ -328,4 +345,4 @@ int launch_outlier_stats(const void* x, long rows, long cols, long row_stride, i
   return launch_status();
 }
 
-}  // namespace oeh
+}  // extern "C"

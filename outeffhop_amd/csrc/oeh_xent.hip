@@ -26,8 +26,26 @@
 //     slots take element stores), per element otherwise.
 #include "oeh_stream.h"
 #include "oeh_launch.h"
+#include "oeh_desc.h"
+
+#include <cstdio>
 
 namespace oeh {
+
+struct XentArgs {
+  const void *x, *labels;
+  float *lse, *row_loss;  // row_loss may be null (without label smoothing)
+  double* out2;           // {sum, count}: written by the reduce launch, read by the backward with mean_reduction
+  float* mean;            // may be null
+  double* meter;          // may be null
+  int* bad_rows;          // may be null
+  const float* grad;      // backward only
+  void* dx;               // backward only
+  long x_sb, x_ss, l_sb, l_ss, dx_sb, dx_ss, grad_stride;  // elements
+  long ignore_index, rows;
+  int S, V, in, label64, mean_reduction;
+  float eps_ls;           // label smoothing
+};
 
 namespace {
 
@@ -40,7 +58,7 @@ __device__ __forceinline__ float qnan() { return bits_f32(0x7fc00000u); }
 __device__ __forceinline__ float mref(const float m) { return m == neg_inf() ? 0.0f : m; }
 
 __device__ __forceinline__ long xent_label(const XentArgs& p, const unsigned row, unsigned& b, unsigned& s) {
-  b = row / (unsigned)p.S;  // (rows < 2^31: oeh_api.hip)
+  b = row / (unsigned)p.S;  // (rows < 2^31: xent_check)
   s = row - b * (unsigned)p.S;
   const long off = (long)b * p.l_sb + (long)s * p.l_ss;
   return p.label64 ? reinterpret_cast<const long*>(p.labels)[off] : (long)reinterpret_cast<const int*>(p.labels)[off];
@@ -339,9 +357,55 @@ __global__ __launch_bounds__(256) void oeh_xent_bwd_kernel(const XentArgs p) {
   }
 }
 
-}  // namespace
+// oeh_xent_fwd / oeh_xent_bwd / oeh_xent_variant: every refusal in the order OEH_EINVAL -> OEH_ENOTSUP -> OEH_EALIGN.  bwd: dx_stride is looked at.
+int xent_check(const oeh_xent_desc* d, const void* logits, const void* labels, bool bwd) {
+  if (d == nullptr || logits == nullptr || labels == nullptr || d->V < 1 || d->B < 0 || d->S < 0 || !dtype_ok(d->dtype)) return OEH_EINVAL;
+  if (d->label_dtype != OEH_ID_I32 && d->label_dtype != OEH_ID_I64) return OEH_EINVAL;
+  for (int i = 0; i < 2; ++i) {
+    if (d->x_stride[i] < 0 || d->label_stride[i] < 0 || (bwd && d->dx_stride[i] < 0)) return OEH_EINVAL;
+  }
+  if (bwd && ((d->S > 1 && d->dx_stride[1] < d->V) || (d->B > 1 && d->dx_stride[0] < d->V))) return OEH_EINVAL;
+  if (!(d->label_smoothing >= 0.0f && d->label_smoothing < 1.0f) || d->reserved != 0) return OEH_EINVAL;
+  if ((int64_t)d->B * d->S >= ((int64_t)1 << 31)) return OEH_ENOTSUP;
+  if (addr(logits) % elem_bytes(d->dtype) != 0 || addr(labels) % (d->label_dtype == OEH_ID_I64 ? 8 : 4) != 0) return OEH_EALIGN;
+  return OEH_OK;
+}
+XentArgs xent_args(const oeh_xent_desc* d, const void* logits, const void* labels) {
+  XentArgs a = {};
+  a.x = logits; a.labels = labels;
+  a.x_sb = d->x_stride[0]; a.x_ss = d->x_stride[1]; a.l_sb = d->label_stride[0]; a.l_ss = d->label_stride[1];
+  a.dx_sb = d->dx_stride[0]; a.dx_ss = d->dx_stride[1];
+  a.ignore_index = d->ignore_index; a.rows = (long)d->B * d->S;
+  a.S = d->S; a.V = d->V; a.in = d->dtype; a.label64 = d->label_dtype == OEH_ID_I64; a.mean_reduction = d->mean_reduction != 0;
+  a.eps_ls = d->label_smoothing;
+  return a;
+}
+// whether the gradient rows take element stores: a dlogits row that is not as far from a 16-byte boundary as its logits row
+bool xent_el(const oeh_xent_desc* d, const void* logits, const void* dlogits) {
+  const int64_t eb = elem_bytes(d->dtype);
+  bool same = (addr(logits) - addr(dlogits)) % 16 == 0;
+  if (d->B > 1) same = same && ((d->x_stride[0] - d->dx_stride[0]) * eb) % 16 == 0;
+  if (d->S > 1) same = same && ((d->x_stride[1] - d->dx_stride[1]) * eb) % 16 == 0;
+  return !same;
+}
 
-int launch_xent_fwd(const XentArgs& a, hipStream_t st) {
+}  // namespace
+}  // namespace oeh
+
+using namespace oeh;
+
+extern "C" {
+
+int oeh_xent_fwd(const oeh_xent_desc* d, const void* logits, const void* labels, float* lse, float* row_loss, double* out2, float* mean,
+                 double* meter, int32_t* bad_rows, void* stream) {
+  if (lse == nullptr || out2 == nullptr) return OEH_EINVAL;
+  if (d != nullptr && row_loss == nullptr && d->label_smoothing > 0.0f) return OEH_EINVAL;
+  const int rc = xent_check(d, logits, labels, false);
+  if (rc != OEH_OK) return rc;
+  if ((addr(lse) | addr(row_loss) | addr(mean) | addr(bad_rows)) % 4 != 0 || (addr(out2) | addr(meter)) % 8 != 0) return OEH_EALIGN;
+  XentArgs a = xent_args(d, logits, labels);
+  a.lse = lse; a.row_loss = row_loss; a.out2 = out2; a.mean = mean; a.meter = meter; a.bad_rows = bad_rows;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (a.rows > 0) {
     dispatch_in(a.in, [&](auto t) {
       constexpr int IN = decltype(t)::value;
@@ -353,8 +417,17 @@ int launch_xent_fwd(const XentArgs& a, hipStream_t st) {
   return launch_status();
 }
 
-int launch_xent_bwd(const XentArgs& a, bool el, hipStream_t st) {
+int oeh_xent_bwd(const oeh_xent_desc* d, const void* logits, const void* labels, const float* lse, const double* out2, const float* grad,
+                 int64_t grad_stride, void* dlogits, void* stream) {
+  if (lse == nullptr || out2 == nullptr || grad == nullptr || dlogits == nullptr || grad_stride < 0) return OEH_EINVAL;
+  const int rc = xent_check(d, logits, labels, true);
+  if (rc != OEH_OK) return rc;
+  if ((addr(lse) | addr(grad)) % 4 != 0 || addr(out2) % 8 != 0 || addr(dlogits) % elem_bytes(d->dtype) != 0) return OEH_EALIGN;
+  XentArgs a = xent_args(d, logits, labels);
+  a.lse = const_cast<float*>(lse); a.out2 = const_cast<double*>(out2); a.grad = grad; a.grad_stride = grad_stride; a.dx = dlogits;
   if (a.rows == 0) return OEH_OK;
+  const bool el = xent_el(d, logits, dlogits);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)a.rows);
   dispatch_in(a.in, [&](auto t) {
     constexpr int IN = decltype(t)::value;
@@ -367,4 +440,14 @@ int launch_xent_bwd(const XentArgs& a, bool el, hipStream_t st) {
   return launch_status();
 }
 
-}  // namespace oeh
+const char* oeh_xent_variant(const oeh_xent_desc* d, const void* logits, const void* dlogits) {
+  static thread_local char name[48];
+  const void* const aligned = reinterpret_cast<const void*>((uintptr_t)4096);  // (the labels are taken as given and aligned)
+  if (xent_check(d, logits, aligned, dlogits != nullptr) != OEH_OK) return nullptr;
+  if (dlogits != nullptr && addr(dlogits) % elem_bytes(d->dtype) != 0) return nullptr;
+  std::snprintf(name, sizeof name, "xent/block/CH%d/%s%s%s", OEH_XENT_SLOTS, dtype_name(d->dtype), d->label_smoothing > 0.0f ? "/ls" : "",
+                dlogits != nullptr && xent_el(d, logits, dlogits) ? "/el" : "");
+  return name;
+}
+
+}  // extern "C"

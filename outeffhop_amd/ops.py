@@ -872,6 +872,33 @@ def _rows_view(t: torch.Tensor, cols: int):
     return v, (v.stride(0) if v.shape[0] > 1 else cols)
 
 
+def _own_rows(t: torch.Tensor, cols: int, what: str):
+    """An output as rows: it must BE the memory it was given as - no copy may stand in for it."""
+    v, st = _rows_view(t, cols)
+    if v.data_ptr() != t.data_ptr() or (v.shape[0] > 1 and st < cols):
+        raise ValueError(f"{what} needs a contiguous last dimension and leading dimensions that collapse to one row stride")
+    return v, st
+
+
+def _ln_rows_in(op: str, x, residual, weight, bias, out, sum_out, allow_grad: bool):
+    """The opening `resid_ln_quant` and `drop_resid_ln_fwd` share: device and dtype, cols, the optional tensors' shape and dtype, the row views of
+    x and residual, gamma / beta as fp32.  Returns (dev, cols, xv, xs, rv, rs, g, b)."""
+    dev = _need_gpu(x, residual, weight, bias, out, sum_out, allow_grad=allow_grad)
+    _need_dtype(x)
+    cols = x.shape[-1] if x.dim() else 0
+    if cols < 1:
+        raise ValueError(f"{op} needs a last dimension of at least 1")
+    for t_, what in ((residual, "residual"), (out, "out"), (sum_out, "sum_out")):
+        if t_ is not None and (t_.shape != x.shape or t_.dtype != x.dtype):
+            raise ValueError(f"{what} must have x's shape and dtype")
+    if weight.numel() != cols or (bias is not None and bias.numel() != cols):
+        raise ValueError("weight / bias must hold one value per column")
+    xv, xs = _rows_view(x.detach(), cols)
+    rv, rs = _rows_view(residual.detach(), cols) if residual is not None else (None, 0)
+    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+    return dev, cols, xv, xs, rv, rs, f32(weight), f32(bias)
+
+
 def _ln_desc(rows: int, cols: int, dtype, strides, eps: float, fq_sum: Optional[FakeQuantSpec], fq_out: Optional[FakeQuantSpec]) -> _lib.oeh_ln_desc:
     d = _lib.oeh_ln_desc()
     d.rows, d.cols, d.dtype = rows, cols, _DT[dtype]
@@ -893,34 +920,12 @@ def resid_ln_quant(x: torch.Tensor, residual: Optional[torch.Tensor] = None, wei
     quantiser; tests).  out / sum_out: where to write (x's shape and dtype); sum_out may be `residual` or `x`, and out may be `x`."""
     if weight is None:
         raise ValueError("resid_ln_quant needs the LayerNorm's weight")
-    dev = _need_gpu(x, residual, weight, bias, out, sum_out)
-    _need_dtype(x)
-    cols = x.shape[-1] if x.dim() else 0
-    if cols < 1:
-        raise ValueError("resid_ln_quant needs a last dimension of at least 1")
-    for t_, what in ((residual, "residual"), (out, "out"), (sum_out, "sum_out")):
-        if t_ is not None and (t_.shape != x.shape or t_.dtype != x.dtype):
-            raise ValueError(f"{what} must have x's shape and dtype")
-    if weight.numel() != cols or (bias is not None and bias.numel() != cols):
-        raise ValueError("weight / bias must hold one value per column")
+    dev, cols, xv, xs, rv, rs, g, b = _ln_rows_in("resid_ln_quant", x, residual, weight, bias, out, sum_out, False)
     want_sum = want_sum or want_idx or sum_out is not None
-    xv, xs = _rows_view(x.detach(), cols)
-    rv, rs = _rows_view(residual.detach(), cols) if residual is not None else (None, 0)
     y = out if out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
     s = (sum_out if sum_out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)) if want_sum else None
-    outs = []
-    for t_ in (s, y):  # an output must BE the memory it was given as: no copy may stand in for it
-        if t_ is None:
-            outs.append((None, 0))
-            continue
-        v_, st_ = _rows_view(t_, cols)
-        if v_.data_ptr() != t_.data_ptr() or (v_.shape[0] > 1 and st_ < cols):
-            raise ValueError("out / sum_out need a contiguous last dimension and leading dimensions that collapse to one row stride")
-        outs.append((v_, st_))
-    (sv, ss), (yv, ys) = outs
+    (sv, ss), (yv, ys) = _own_rows(s, cols, "sum_out") if want_sum else (None, 0), _own_rows(y, cols, "out")
     rows = xv.shape[0]
-    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
-    g, b = f32(weight), f32(bias)
     sidx = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_idx and fq_sum is not None else None
     yidx = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_idx and fq_out is not None else None
     d = _ln_desc(rows, cols, x.dtype, (xs, rs, ss, ys), eps, fq_sum, fq_out)
@@ -955,14 +960,6 @@ def _ln_train_desc(rows: int, cols: int, dtype, strides, eps: float, p: float, s
     return d
 
 
-def _own_rows(t: torch.Tensor, cols: int, what: str):
-    """An output as rows: it must BE the memory it was given as - no copy may stand in for it."""
-    v, st = _rows_view(t, cols)
-    if v.data_ptr() != t.data_ptr() or (v.shape[0] > 1 and st < cols):
-        raise ValueError(f"{what} needs a contiguous last dimension and leading dimensions that collapse to one row stride")
-    return v, st
-
-
 def drop_resid_ln_fwd(x: torch.Tensor, residual: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor] = None, eps: float = 1e-5,
                       *, p: float = 0.0, seed: Optional[int] = None, out: Optional[torch.Tensor] = None, sum_out: Optional[torch.Tensor] = None):
     """(sum, y, mean, rstd) of LayerNorm(dropout(x) + residual) over the last dimension in ONE kernel (`include/oeh.h: oeh_drop_resid_ln_fwd`):
@@ -970,26 +967,13 @@ def drop_resid_ln_fwd(x: torch.Tensor, residual: Optional[torch.Tensor], weight:
     row statistics (x.shape[:-1]; formed in float64, stored as fp32).  x, residual (..., N) fp16 / bf16 / fp32; weight (N) and bias (N) are taken as fp32.  p > 0 needs the
     uint64 `seed` of the keep mask (`drop_resid_ln_mask`).  No autograd here (see `layers.dropout_add_layer_norm`).  sum_out may be `residual`,
     out may be `x`."""
-    dev = _need_gpu(x, residual, weight, bias, out, sum_out, allow_grad=True)
-    _need_dtype(x)
-    cols = x.shape[-1] if x.dim() else 0
-    if cols < 1:
-        raise ValueError("drop_resid_ln_fwd needs a last dimension of at least 1")
-    for t_, what in ((residual, "residual"), (out, "out"), (sum_out, "sum_out")):
-        if t_ is not None and (t_.shape != x.shape or t_.dtype != x.dtype):
-            raise ValueError(f"{what} must have x's shape and dtype")
-    if weight.numel() != cols or (bias is not None and bias.numel() != cols):
-        raise ValueError("weight / bias must hold one value per column")
-    xv, xs = _rows_view(x.detach(), cols)
-    rv, rs = _rows_view(residual.detach(), cols) if residual is not None else (None, 0)
+    dev, cols, xv, xs, rv, rs, g, b = _ln_rows_in("drop_resid_ln_fwd", x, residual, weight, bias, out, sum_out, True)
     y = out if out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
     s = sum_out if sum_out is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
     (sv, ss), (yv, ys) = _own_rows(s, cols, "sum_out"), _own_rows(y, cols, "out")
     rows = xv.shape[0]
     mean = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
     rstd = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
-    g, b = f32(weight), f32(bias)
     d = _ln_train_desc(rows, cols, x.dtype, (xs, rs, ss, ys), eps, p, seed)
     if rows:  # (an empty tensor has no address to hand over)
         with _on_device(dev):

@@ -10,7 +10,7 @@ form, y and its indices equal `ops.resid_ln_quant` on the stored sum bit for bit
 check_indices against a float64 evaluation of the stored sum, with the helpers' factor and band cap and the unit of tests/test_ln_gpu.py
 (the distance of CPU fp32 F.layer_norm from float64 on the same case).
 
-Launch forms (oeh_launch.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements):
+Launch forms (oeh_ln_row.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements):
   cols 8, 72, 768, 1024   one wave per row, four rows per workgroup: B * S = 1, 6, 15 leave waves of the last workgroup without a row
   cols 1032, 8192         one workgroup per row
   cols 1, 4 (16-bit)      element accesses; also: table row strides, output strides and bases off the 16-byte vector"""

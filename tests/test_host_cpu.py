@@ -483,7 +483,7 @@ def test_autograd_routes_to_the_differentiable_torch_op_path(monkeypatch):
 
 
 def test_projection_gemm_refusals_before_any_launch():
-    """`oeh_proj_quant_i8` (csrc/oeh_api.hip) refuses on the host, before anything is launched - dummy pointers, no GPU: what
+    """`oeh_proj_quant_i8` (csrc/oeh_gemm.hip) refuses on the host, before anything is launched - dummy pointers, no GPU: what
     tests/test_abi.py does not already try (no segments, K % 32, S % 16, pairs with lda < 2K, a first segment with neither output)."""
     import ctypes as C
 

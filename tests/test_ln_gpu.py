@@ -9,7 +9,7 @@ the distance of CPU fp32 F.layer_norm from float64 on the same case (err64) as t
                         index may differ by one step; the band holds <= 1e-3 of the elements; every value is scale * (idx - zp)
 The factor 4 covers the kernel's different summation tree and the two extra roundings of rstd.  The measured ratios are printed (-s).
 
-Launch forms (oeh_launch.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements):
+Launch forms (oeh_ln_row.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements):
   cols 8, 72, 768, 1024   one wave per row (cols <= 1024, cols % VEC == 0), CH = 1 .. 4 accesses per lane; rows 1, 3, 5 leave waves of the
                           last workgroup without a row, 64 rows are 16 workgroups
   cols 1032, 2048, 8192   one workgroup per row (cols <= 8192), CH = 1 .. 8

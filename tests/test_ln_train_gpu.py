@@ -18,7 +18,7 @@ and round once, so each value is the fp32 number next to float64's and no fp32 e
 the CPU's rounding happens to be in a call of one or three rows (a single mean; an entry of dgamma that is one product).  
 Worst ratios measured on an MI355X: y 3.65, dx 1.37, dr 1.45, dr - dr0 1.60, mean 1.00, rstd 1.00, dgamma 1.00, dbeta 1.00.
 
-Launch forms (oeh_launch.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements): cols 8, 72, 768, 1024 one wave per row; 1032, 2048, 8192 one
+Launch forms (oeh_ln_row.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements): cols 8, 72, 768, 1024 one wave per row; 1032, 2048, 8192 one
 workgroup per row; 1, 770, a row stride that is no multiple of VEC and a base pointer one element off a 16-byte boundary element accesses.
 The backward's slab loop (ops.drop_resid_ln_variant(..., backward=True) ends in G<workgroups>x<rows per slab>): one workgroup; several
 workgroups of one row-step each; more rows than the grid bound takes in one step, with a ragged last slab."""

@@ -10,6 +10,7 @@ from __future__ import annotations
 import math
 import weakref
 from enum import Flag
+from functools import partial
 from typing import Optional, Tuple
 
 import numpy as np
@@ -71,6 +72,28 @@ def build_gate(num_heads: int, head_dim: int, model_dim: int, gate_type, gate_in
             nn.init.normal_(fc.weight, mean=0.0, std=ft_std)
         heads.append(fc)
     return nn.ModuleList(heads)
+
+
+# what a quantised module takes over from the module it wraps (quantization._QuantAttnBase._init_common)
+GATE_ATTRS = ("attn_gate_type", "attn_gate_init", "attn_gate_mlp", "attn_gate_mlp2", "attn_gate_linear_all_features", "alpha", "gate_fn", "pooling_fn")
+
+
+def init_gate(mod: nn.Module, num_heads: int, head_dim: int, model_dim: int, gate_type, gate_init, use_mlp: bool, use_mlp2: bool,
+              all_features: bool, fine_tuning: bool, ft_std: float) -> None:
+    """The gate attributes of a module's constructor as the reference sets them, `alpha` (`build_gate`) last: call it where the
+    reference builds `alpha`, so that parameter order and the draws from the RNG are the reference's."""
+    mod.last_gate_avg_prob = None
+    mod.last_gate_all_probs = None
+    mod.attn_gate_type = gate_type
+    mod.attn_gate_init = gate_init
+    mod.attn_gate_mlp = use_mlp
+    mod.attn_gate_mlp2 = use_mlp2
+    mod.attn_gate_linear_all_features = all_features
+    mod.gate_fn = torch.sigmoid
+    mod.pooling_fn = partial(torch.mean, dim=1, keepdims=True)
+    mod.fine_tuning = fine_tuning
+    mod.gate_scaling_factor = 1.0 / gate_init if (fine_tuning and gate_init is not None) else 1.0
+    mod.alpha = build_gate(num_heads, head_dim, model_dim, gate_type, gate_init, use_mlp, use_mlp2, all_features, fine_tuning, ft_std)
 
 
 class GateBookkeeping:
@@ -210,6 +233,27 @@ class GateState:
         return gate
 
 
+def module_gate(mod: nn.Module, hidden_states: torch.Tensor, num_heads: int, in_kernel: bool):
+    """The gate of one forward of a float module: (gate values | None, ops.GatePredictor | None).  `in_kernel`: this forward may
+    evaluate a conditional per-token gate inside the attention kernel (it fuses, and the predictor's input is the query side's) -
+    then the predictor, scaling inside, and `GateState.finish_predictor` after the launch.  Otherwise the values, times
+    gate_scaling_factor unless the gate is unconditional (context *= gate * scaling, bert_attention.py:327)."""
+    gp = GateState.predictor(mod, hidden_states, num_heads, mod.gate_scaling_factor) if in_kernel else None
+    if gp is not None:
+        return None, gp
+    gate = GateState.evaluate(mod, hidden_states, num_heads)
+    if gate is not None and mod.attn_gate_type != AttentionGateType.unconditional_per_head:
+        gate = gate * mod.gate_scaling_factor
+    return gate, None
+
+
+def gated_merge(ctx: torch.Tensor, gate: Optional[torch.Tensor]) -> torch.Tensor:
+    """The tail of the differentiable cores (fused_train_core, unfused_core): (B,H,S,d) context * gate -> (B,S,H*d)."""
+    if gate is not None:
+        ctx = ctx * gate.to(ctx.dtype)
+    return ctx.transpose(1, 2).reshape(ctx.shape[0], ctx.shape[2], -1)
+
+
 # ---- fused q/k/v projection (SURVEY 8f-1): the three E->E Linears of a self-attention layer as ONE library GEMM with the
 # concatenated weight, returning strided (B,S,E) views of its (B,S,3E) output (the attention kernel takes strides, so there is
 # no copy either side).  Inference only: parameters keep the reference's names (query/key/value, q_proj/k_proj/v_proj) and the
@@ -288,7 +332,10 @@ def linear_fp32(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
 
 
 def has_hooks(*mods: nn.Module) -> bool:
-    return any(len(m._forward_hooks) or len(m._forward_pre_hooks) for m in mods)
+    for m in mods:  # (a plain loop, not any() over a generator: every eager forward asks)
+        if m._forward_hooks or m._forward_pre_hooks:
+            return True
+    return False
 
 
 def mask_min_of(attention_mask: Optional[torch.Tensor], fallback_dtype: torch.dtype) -> float:
@@ -308,70 +355,88 @@ def split_mask(mask: Optional[torch.Tensor], B: int, Sq: int, Sk: int):
     return None, mask.expand(B, 1, Sq, Sk)
 
 
-_causal_cache = {}  # id(mask) -> (weakref to the mask tensor, its version counter, result)
+class _TensorMemo(dict):
+    """A result per LIVE tensor object: id(tensor) -> (weak reference to the tensor, its version counter, result).  An entry answers only
+    while its weak reference still points at the asking tensor and the version counter is unchanged, never by address alone: the
+    caching allocator gives the next batch's mask the same address (and Python the same id), and a result remembered by address
+    would apply the previous batch's padding to it.  Entries die with their tensors; 64 at the most."""
+
+    def lookup(self, t: torch.Tensor, compute):
+        key = id(t)
+        hit = self.get(key)
+        if hit is not None:
+            if hit[0]() is t and hit[1] == t._version:
+                return hit[2]
+            del self[key]
+        res = compute(t)
+
+        def _forget(dead, _k=key):  # the tensor object is gone: its id may be reused by any other object
+            ent = self.get(_k)
+            if ent is not None and ent[0] is dead:
+                del self[_k]
+
+        if len(self) > 64:
+            self.clear()
+        self[key] = (weakref.ref(t, _forget), t._version, res)
+        return res
 
 
-def classify_causal(mask: torch.Tensor):
-    """Recognise HF's decoder mask: a (B,1,T,S) additive tensor that equals causal(finfo.min above the shifted
-    diagonal) + key-padding(finfo.min columns), up to the clamp at finfo.min the attention applies anyway
-    (opt_attention.py:220-223).  Returns (True, pad_vector_or_None) or (False, None).
+_causal_cache = _TensorMemo()
+_padbool_cache = _TensorMemo()
 
-    One pass over the mask per distinct tensor OBJECT: HF hands the same tensor to every layer of a forward, so the
-    result is remembered - keyed on the identity of the live object (a weak reference that must still point at
-    `mask`) and its version counter, never on its address: the caching allocator gives the next batch's mask the
-    same address, and a result remembered by address would apply the previous batch's padding to it."""
-    key = id(mask)
-    hit = _causal_cache.get(key)
-    if hit is not None:
-        if hit[0]() is mask and hit[1] == mask._version:
-            return hit[2]
-        del _causal_cache[key]
+
+def _classify_causal(mask: torch.Tensor):
     B, _, T, S = mask.shape
     fmin = torch.finfo(mask.dtype).min
     causal = torch.full((T, S), fmin, dtype=mask.dtype, device=mask.device).triu(1 + S - T)
     pad = mask[:, 0, -1, :].clamp(min=fmin)  # the last query row sees every key: what is left is padding
     recon = (causal[None, None] + pad[:, None, None, :]).clamp(min=fmin)
     ok = bool(torch.equal(mask.clamp(min=fmin), recon)) and bool(((pad == 0) | (pad == fmin)).all())
-    res = (True, (pad.contiguous() if bool((pad != 0).any()) else None)) if ok else (False, None)
-
-    def _forget(dead, _k=key):  # the mask object is gone: its id may be reused by any other object
-        ent = _causal_cache.get(_k)
-        if ent is not None and ent[0] is dead:
-            del _causal_cache[_k]
-
-    ref = weakref.ref(mask, _forget)
-    if len(_causal_cache) > 64:
-        _causal_cache.clear()
-    _causal_cache[key] = (ref, mask._version, res)
-    return res
+    return (True, (pad.contiguous() if bool((pad != 0).any()) else None)) if ok else (False, None)
 
 
-_padbool_cache = {}  # id(mask) -> (weakref to the mask tensor, its version counter, result)
+def classify_causal(mask: torch.Tensor):
+    """Recognise HF's decoder mask: a (B,1,T,S) additive tensor that equals causal(finfo.min above the shifted
+    diagonal) + key-padding(finfo.min columns), up to the clamp at finfo.min the attention applies anyway
+    (opt_attention.py:220-223).  Returns (True, pad_vector_or_None) or (False, None).
+    One pass over the mask per distinct tensor OBJECT (_TensorMemo): HF hands the same tensor to every layer of a forward."""
+    return _causal_cache.lookup(mask, _classify_causal)
 
 
 def pad_is_boolean(mask: torch.Tensor) -> bool:
     """True when an additive mask holds only 0 (visible) and values <= -1e4 (hidden) - HF's extended masks hold 0 / finfo.min.
     The integer-matrix-core attention (`ops.attn_fwd_i8`) DROPS a padded key instead of adding the mask value to its score, which
-    is the reference's result exactly for such masks.  One pass (and one host read) per distinct mask tensor object - HF hands
-    the same tensor to every layer -, remembered like `classify_causal` does: by the identity of the live object and its
-    version counter, never by address."""
-    key = id(mask)
-    hit = _padbool_cache.get(key)
-    if hit is not None:
-        if hit[0]() is mask and hit[1] == mask._version:
-            return hit[2]
-        del _padbool_cache[key]
-    res = bool(((mask == 0) | (mask <= -1.0e4)).all())
+    is the reference's result exactly for such masks.  One pass (and one host read) per distinct mask tensor object (_TensorMemo)."""
+    return _padbool_cache.lookup(mask, lambda m: bool(((m == 0) | (m <= -1.0e4)).all()))
 
-    def _forget(dead, _k=key):
-        ent = _padbool_cache.get(_k)
-        if ent is not None and ent[0] is dead:
-            del _padbool_cache[_k]
 
-    if len(_padbool_cache) > 64:
-        _padbool_cache.clear()
-    _padbool_cache[key] = (weakref.ref(mask, _forget), mask._version, res)
-    return res
+def resolve_mask(attention_mask: Optional[torch.Tensor], B: int, Sq: int, Sk: int, dtype: torch.dtype, detect_causal: bool = False):
+    """An additive HF mask as the kernels take it: (key-padding vector (B,Sk) | None, full (B,1,Sq,Sk) mask | None, causal, mask_min).
+    With `detect_causal` a full mask that is HF's decoder mask becomes the analytic causal mask plus its padding vector
+    (`classify_causal`: one device pass per mask tensor object); `dtype`: the activations', the floor's fallback (`mask_min_of`)."""
+    pad, full = split_mask(attention_mask, B, Sq, Sk)
+    causal = False
+    if full is not None and detect_causal and Sq <= Sk:
+        causal, padvec = classify_causal(full)
+        if causal:
+            full, pad = None, padvec
+    return pad, full, causal, mask_min_of(attention_mask, dtype)
+
+
+def kv_source(k_proj, v_proj, to_heads, hidden_states, cross_states, past_key_value, fused_kv=None):
+    """HF's rule for where a forward's keys and values come from, as logical (B,H,S,d) tensors: projected from the layer input; those
+    appended to a cached pair on dim 2; projected from `cross_states`; or, for cross-attention with a cache, the cached pair as it
+    is.  `fused_kv`: the k / v parts of an already fused QKV result of the layer input (`fused_qkv`), used instead of the projections."""
+    if cross_states is not None and past_key_value is not None:
+        return past_key_value[0], past_key_value[1]
+    if fused_kv is not None:
+        k, v = to_heads(fused_kv[0]), to_heads(fused_kv[1])
+    else:
+        src = hidden_states if cross_states is None else cross_states
+        k, v = to_heads(k_proj(src)), to_heads(v_proj(src))
+    if cross_states is None and past_key_value is not None:
+        k, v = torch.cat([past_key_value[0], k], dim=2), torch.cat([past_key_value[1], v], dim=2)
+    return k, v
 
 
 # ---- fp32-accurate context for fp32 models (opt-in): with COMPENSATED_PV on, every fused inference call on fp32 storage without fake-quant
@@ -426,14 +491,9 @@ def attention_core(
     B, H, Sq, D = q.shape
     Sk = k.shape[2]
     spec = spec_of(softmax_fn)
-    pad, full = split_mask(attention_mask, B, Sq, Sk)
-    causal = False
-    if full is not None and detect_causal and Sq <= Sk:
-        causal, padvec = classify_causal(full)
-        if causal:
-            full, pad = None, padvec
-    if mask_min is None:
-        mask_min = mask_min_of(attention_mask, q.dtype)
+    pad, full, causal, floor = resolve_mask(attention_mask, B, Sq, Sk, q.dtype, detect_causal)
+    if mask_min is None:  # (a caller may set the floor itself)
+        mask_min = floor
     # the fused INT8 chain stays on the quantiser grid with padded keys when the mask is a mask (0 / finfo.min entries - what
     # classify_causal has verified for a decoder mask; else one look per mask tensor object): include/oeh.h key_pad_boolean
     pad_bool = pad is not None and fq is not None and (causal or pad_is_boolean(attention_mask))
@@ -513,15 +573,11 @@ def fused_train_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softm
         return None
     B, H, Sq, _ = q.shape
     Sk = k.shape[2]
-    pad, full = split_mask(attention_mask, B, Sq, Sk)
-    causal = False
-    if full is not None and detect_causal and Sq <= Sk:
-        causal, padvec = classify_causal(full)
-        if causal:
-            full, pad = None, padvec
-    clamp = clamp_min and attention_mask is not None
+    pad, full, causal, _ = resolve_mask(attention_mask, B, Sq, Sk, q.dtype, detect_causal)
+    # as unfused_core: the floor is finfo.min of the scores' dtype (not the mask's), and there is a clamp only where a mask was added
     return fused_attention(q, k, v, softmax=spec_of(softmax_fn), scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full,
-                           causal=causal, clamp_min=clamp, mask_min=float(torch.finfo(q.dtype).min), dropout_p=dropout_p)
+                           causal=causal, clamp_min=clamp_min and attention_mask is not None, mask_min=float(torch.finfo(q.dtype).min),
+                           dropout_p=dropout_p)
 
 
 def unfused_core(

@@ -10,14 +10,13 @@ fp32 inside the kernel - the semantics that branch intended - so OPT + softmax1 
 """
 from __future__ import annotations
 
-from functools import partial
 from typing import Optional, Tuple
 
 import torch
 from torch import nn
 
-from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_qkv, fused_train_core, has_hooks,
-                        linear_fp32, unfused_core)
+from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, fused_qkv, fused_train_core, gated_merge, has_hooks,
+                        init_gate, kv_source, linear_fp32, module_gate, unfused_core)
 from .softmax import make_clipped_softmax, make_clipped_softmax1, spec_of
 
 
@@ -53,19 +52,8 @@ class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
         else:
             self.softmax_fn = softmax_fn
         self.skip_attn = skip_attn  # accepted and ignored, as in the reference
-        self.last_gate_avg_prob = None
-        self.last_gate_all_probs = None
-        self.attn_gate_type = attn_gate_type
-        self.attn_gate_init = attn_gate_init
-        self.attn_gate_mlp = attn_gate_mlp
-        self.attn_gate_mlp2 = attn_gate_mlp2
-        self.attn_gate_linear_all_features = attn_gate_linear_all_features
-        self.gate_fn = torch.sigmoid
-        self.pooling_fn = partial(torch.mean, dim=1, keepdims=True)
-        self.fine_tuning = fine_tuning
-        self.gate_scaling_factor = 1.0 / attn_gate_init if (fine_tuning and attn_gate_init is not None) else 1.0
-        self.alpha = build_gate(num_heads, self.head_dim, embed_dim, attn_gate_type, attn_gate_init, attn_gate_mlp, attn_gate_mlp2,
-                                attn_gate_linear_all_features, fine_tuning, ft_std=0.001)
+        init_gate(self, num_heads, self.head_dim, embed_dim, attn_gate_type, attn_gate_init, attn_gate_mlp, attn_gate_mlp2,
+                  attn_gate_linear_all_features, fine_tuning, ft_std=0.001)
 
     def _heads(self, t: torch.Tensor, bsz: int) -> torch.Tensor:
         """(B,S,E) -> logical (B,H,S,d) view; no copy (the kernel takes strides)."""
@@ -80,73 +68,46 @@ class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[Tuple[torch.Tensor]]]:
         """Input shape: Batch x Time x Channel"""
         bsz, tgt_len, _ = hidden_states.size()
-        qkv = None
-        if key_value_states is None:  # self-attention: one GEMM for the three projections, the q scaling folded in (attention.fused_qkv)
-            qkv = fused_qkv(self, hidden_states, self.q_proj, self.k_proj, self.v_proj, self.scaling)
-        q = self._heads(qkv[0] if qkv is not None else self.q_proj(hidden_states) * self.scaling, bsz)
-        if qkv is not None:
-            k, v = self._heads(qkv[1], bsz), self._heads(qkv[2], bsz)
-            if past_key_value is not None:
-                k = torch.cat([past_key_value[0], k], dim=2)
-                v = torch.cat([past_key_value[1], v], dim=2)
-        elif key_value_states is not None and past_key_value is not None:
-            k, v = past_key_value[0], past_key_value[1]
-        elif key_value_states is not None:
-            k, v = self._heads(self.k_proj(key_value_states), bsz), self._heads(self.v_proj(key_value_states), bsz)
-        else:
-            k, v = self._heads(self.k_proj(hidden_states), bsz), self._heads(self.v_proj(hidden_states), bsz)
-            if past_key_value is not None:
-                k = torch.cat([past_key_value[0], k], dim=2)
-                v = torch.cat([past_key_value[1], v], dim=2)
+        self_attn, cached = key_value_states is None, past_key_value is not None
+        # self-attention: one GEMM for the three projections, the q scaling folded in (attention.fused_qkv)
+        qkv = fused_qkv(self, hidden_states, self.q_proj, self.k_proj, self.v_proj, self.scaling) if self_attn else None
+        q = self._heads(self.q_proj(hidden_states) * self.scaling if qkv is None else qkv[0], bsz)
+        k, v = kv_source(self.k_proj, self.v_proj, lambda t: self._heads(t, bsz), hidden_states, key_value_states, past_key_value,
+                         fused_kv=None if qkv is None else qkv[1:])
         new_past = (k, v) if self.is_decoder else past_key_value
         src_len = k.size(2)
         if attention_mask is not None and attention_mask.size() != (bsz, 1, tgt_len, src_len):
             raise ValueError(f"Attention mask should be of size {(bsz, 1, tgt_len, src_len)}, but is {attention_mask.size()}")
         if layer_head_mask is not None and layer_head_mask.size() != (self.num_heads,):
             raise ValueError(f"Head mask for a single layer should be of size {(self.num_heads,)}, but is {layer_head_mask.size()}")
-        fusable = (spec_of(self.softmax_fn) is not None and layer_head_mask is None and not output_attentions
-                   and not (self.training and self.dropout > 0.0) and not autograd_needed(self, hidden_states, key_value_states, q, k, v)
-                   and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout))
-        # conditional per-token gate: evaluated inside the attention kernel when the fused path runs (self-attention only:
-        # the predictor acts on the query-side layer input)
-        gp = None
-        if fusable and key_value_states is None and past_key_value is None:
-            gp = GateState.predictor(self, hidden_states, self.num_heads, self.gate_scaling_factor)
-        gate = None
-        if gp is None:
-            gate = GateState.evaluate(self, hidden_states, self.num_heads)
-            if gate is not None and self.attn_gate_type != AttentionGateType.unconditional_per_head:
-                gate = gate * self.gate_scaling_factor
+        # nothing observable is asked for: what both the fused forward and the fused training core need
+        plain = (layer_head_mask is None and not output_attentions
+                 and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout))
+        fusable = (plain and spec_of(self.softmax_fn) is not None and not (self.training and self.dropout > 0.0)
+                   and not autograd_needed(self, hidden_states, key_value_states, q, k, v))
+        # (the gate inside the attention kernel for self-attention without a cache only: the predictor acts on the query-side layer input)
+        gate, gp = module_gate(self, hidden_states, self.num_heads, in_kernel=fusable and self_attn and not cached)
+        kw = dict(softmax_fn=self.softmax_fn, attention_mask=attention_mask)
         weights = None
         if fusable:
-            merged = attention_core(q, k, v, softmax_fn=self.softmax_fn, scale=1.0, attention_mask=attention_mask,
-                                    clamp_min=attention_mask is not None, detect_causal=True, gate=gate, gate_mlp=gp,
-                                    decode=key_value_states is None and past_key_value is not None)
+            merged = attention_core(q, k, v, scale=1.0, clamp_min=attention_mask is not None, detect_causal=True, gate=gate, gate_mlp=gp,
+                                    decode=self_attn and cached, **kw)
             if gp is not None:
                 GateState.finish_predictor(self, gp, self.num_heads)
         else:
+            # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
+            # also needs attention.FUSED_DROPOUT)
             ctx = None
-            if (layer_head_mask is None and not output_attentions
-                    and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout)):
-                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
-                # also needs attention.FUSED_DROPOUT)
-                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=True, detect_causal=True,
-                                       dropout_p=self.dropout if self.training else 0.0)
-            if ctx is not None:
-                if gate is not None:
-                    ctx = ctx * gate.to(ctx.dtype)
-                merged = ctx.transpose(1, 2).reshape(bsz, tgt_len, self.embed_dim)
-                return linear_fp32(self.out_proj, merged), None, new_past
-            hm = None if layer_head_mask is None else layer_head_mask.view(1, -1, 1, 1)
-            drop = (lambda p: nn.functional.dropout(p, p=self.dropout, training=self.training))
-            fn = self.softmax_fn
-            if q.dtype == torch.float16 and spec_of(fn) is not None:  # upcast branch of the reference (:227-230), without its TypeError
-                fn = (lambda x, dim=-1, _f=self.softmax_fn: _f(x.float(), dim=dim).to(torch.float16))
-            ctx, _, used = unfused_core(q, k, v, softmax_fn=fn, attention_mask=attention_mask, clamp_min=attention_mask is not None,
-                                        scores_tap=self.attn_scores, probs_tap=self.attn_probs_before_dropout, dropout=drop,
-                                        probs_after_tap=self.attn_probs_after_dropout, head_mask=hm)
-            weights = used if output_attentions else None
-            if gate is not None:
-                ctx = ctx * gate.to(ctx.dtype)
-            merged = ctx.transpose(1, 2).reshape(bsz, tgt_len, self.embed_dim)
+            if plain:
+                ctx = fused_train_core(q, k, v, clamp_min=True, detect_causal=True, dropout_p=self.dropout if self.training else 0.0, **kw)
+            if ctx is None:
+                hm = None if layer_head_mask is None else layer_head_mask.view(1, -1, 1, 1)
+                drop = (lambda p: nn.functional.dropout(p, p=self.dropout, training=self.training))
+                if q.dtype == torch.float16 and spec_of(self.softmax_fn) is not None:  # upcast branch of the reference (:227-230), without its TypeError
+                    kw["softmax_fn"] = (lambda x, dim=-1, _f=self.softmax_fn: _f(x.float(), dim=dim).to(torch.float16))
+                ctx, _, used = unfused_core(q, k, v, clamp_min=attention_mask is not None, scores_tap=self.attn_scores,
+                                            probs_tap=self.attn_probs_before_dropout, dropout=drop, probs_after_tap=self.attn_probs_after_dropout,
+                                            head_mask=hm, **kw)
+                weights = used if output_attentions else None
+            merged = gated_merge(ctx, gate)
         return linear_fp32(self.out_proj, merged), weights, new_past  # (fp32 inference: one fp16 GEMM on operand triples)

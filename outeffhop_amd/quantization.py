@@ -33,8 +33,8 @@ from torch import nn
 from . import ops
 from ._lib import OehError as _OehError
 from ._watch import TensorWatch, cached
-from .attention import (AttentionGateType, BaseEnumOptions, GateBookkeeping, GateState, attention_core, classify_causal, has_hooks, mask_min_of,
-                        pad_is_boolean, split_mask, unfused_core)
+from .attention import (GATE_ATTRS, AttentionGateType, BaseEnumOptions, GateBookkeeping, GateState, attention_core, classify_causal, gated_merge,
+                        has_hooks, kv_source, mask_min_of, pad_is_boolean, resolve_mask, unfused_core)
 from .ops import AttnFakeQuant, FakeQuantSpec
 from .softmax import spec_of
 
@@ -1338,14 +1338,8 @@ class _QuantAttnBase(GateBookkeeping, QuantizedModel):
         self.attn_probs_act_quantizer = QuantizedActivation(**quant_params)
         self.context_act_quantizer = QuantizedActivation(**quant_params)
         self.softmax_fn = org_model.softmax_fn
-        self.attn_gate_type = org_model.attn_gate_type
-        self.attn_gate_init = org_model.attn_gate_init
-        self.attn_gate_mlp = org_model.attn_gate_mlp
-        self.attn_gate_mlp2 = org_model.attn_gate_mlp2
-        self.attn_gate_linear_all_features = org_model.attn_gate_linear_all_features
-        self.alpha = org_model.alpha  # the gate is not quantised (quantized_bert.py:256)
-        self.gate_fn = org_model.gate_fn
-        self.pooling_fn = org_model.pooling_fn
+        for name in GATE_ATTRS:  # the gate is not quantised (quantized_bert.py:256)
+            setattr(self, name, getattr(org_model, name))
         self.last_gate_avg_prob = None
         self.last_gate_all_probs = None
 
@@ -1386,14 +1380,8 @@ class _QuantAttnBase(GateBookkeeping, QuantizedModel):
         Sk = k.shape[2]
         if B * H * Sq * Sk >= 2 ** 32:
             return None
-        pad, full = split_mask(attention_mask, B, Sq, Sk)
-        causal = False
-        if full is not None and detect_causal and Sq <= Sk:
-            causal, padvec = classify_causal(full)
-            if causal:
-                full, pad = None, padvec
-        kw = dict(softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full, causal=causal, clamp_min=clamp_min,
-                  mask_min=mask_min_of(attention_mask, q.dtype))
+        pad, full, causal, mask_min = resolve_mask(attention_mask, B, Sq, Sk, q.dtype, detect_causal)
+        kw = dict(softmax=spec, scale=scale, scale_div=scale_div, key_pad_mask=pad, full_mask=full, causal=causal, clamp_min=clamp_min, mask_min=mask_min)
         states = []
         for which, mg in enumerate(mgrs):
             est, qz = mg.range_estimator, mg.quantizer
@@ -1602,21 +1590,20 @@ class QuantizedBertSelfAttentionWithExtras(_QuantAttnBase):
                 past_key_value=None, output_attentions=False):
         if self.position_embedding_type in ("relative_key", "relative_key_query"):
             raise NotImplementedError("relative position embeddings are not on the quantised MI355X path")
-        if (encoder_hidden_states is None and past_key_value is None and head_mask is None and not output_attentions
-                and not (self.training and self.dropout.p > 0.0)):
+        H, div = self.num_attention_heads, float(np.sqrt(self.attention_head_size))
+        # nothing observable is asked for: what every route but unfused_core needs
+        plain = head_mask is None and not output_attentions and not (self.training and self.dropout.p > 0.0)
+        fq = self._fq(ctx_before_gate=False)
+        gate, gated = None, False
+        if plain and fq is not None and encoder_hidden_states is None and past_key_value is None:
             # self-attention in inference: query / key / value are QuantLinear (quantized_bert.py:236-238) - their outputs are 8-bit
             # indices, and the whole core (scores / sqrt(d) -> fq -> + mask -> softmax -> fq -> P V -> gate -> fq) runs on them
-            fq8 = self._fq(ctx_before_gate=False)
-            pad8, ok = None, fq8 is not None
-            if ok and attention_mask is not None:
-                B_, T_ = hidden_states.shape[0], hidden_states.shape[1]
-                pad8, full8 = split_mask(attention_mask, B_, T_, T_)
-                ok = full8 is None and pad_is_boolean(attention_mask)
-            if ok:
-                gate8 = GateState.evaluate(self, hidden_states, self.num_attention_heads)
-                done = self._int8_storage_core(hidden_states, (self.query, self.key, self.value), self.num_attention_heads, self.attention_head_size,
-                                               scale=1.0, scale_div=float(np.sqrt(self.attention_head_size)), causal=False, padvec=pad8,
-                                               mask_min=mask_min_of(attention_mask, hidden_states.dtype), gate=gate8, fq=fq8, want_values=self.is_decoder)
+            T = hidden_states.shape[1]
+            pad8, full8, _, floor = resolve_mask(attention_mask, hidden_states.shape[0], T, T, hidden_states.dtype)
+            if full8 is None and (pad8 is None or pad_is_boolean(attention_mask)):
+                gate, gated = GateState.evaluate(self, hidden_states, H), True
+                done = self._int8_storage_core(hidden_states, (self.query, self.key, self.value), H, self.attention_head_size, scale=1.0, scale_div=div,
+                                               causal=False, padvec=pad8, mask_min=floor, gate=gate, fq=fq, want_values=self.is_decoder)
                 if done is not None:
                     context, (yk, yv), _ = done
                     outputs = (context,)
@@ -1624,36 +1611,22 @@ class QuantizedBertSelfAttentionWithExtras(_QuantAttnBase):
                         outputs = outputs + ((self.transpose_for_scores(yk), self.transpose_for_scores(yv)),)
                     return outputs
         q = self.transpose_for_scores(self.query(hidden_states))
-        src = hidden_states if encoder_hidden_states is None else encoder_hidden_states
         if encoder_hidden_states is not None:
             attention_mask = encoder_attention_mask
-        if encoder_hidden_states is not None and past_key_value is not None:
-            k, v = past_key_value[0], past_key_value[1]
-        else:
-            k, v = self.transpose_for_scores(self.key(src)), self.transpose_for_scores(self.value(src))
-            if encoder_hidden_states is None and past_key_value is not None:
-                k, v = torch.cat([past_key_value[0], k], dim=2), torch.cat([past_key_value[1], v], dim=2)
+        k, v = kv_source(self.key, self.value, self.transpose_for_scores, hidden_states, encoder_hidden_states, past_key_value)
         new_past = (k, v) if self.is_decoder else None
-        gate = GateState.evaluate(self, hidden_states, self.num_attention_heads)
-        div = float(np.sqrt(self.attention_head_size))
-        fq = self._fq(ctx_before_gate=False)
-        fusable = (fq is not None and spec_of(self.softmax_fn) is not None and head_mask is None and not output_attentions
-                   and not (self.training and self.dropout.p > 0.0))
+        if not gated:  # (else: the INT8 route declined after the gate was evaluated)
+            gate = GateState.evaluate(self, hidden_states, H)
+        kw = dict(softmax_fn=self.softmax_fn, scale_div=div, attention_mask=attention_mask)
         probs = None
-        if fusable:
-            context = attention_core(q, k, v, softmax_fn=self.softmax_fn, scale_div=div, attention_mask=attention_mask, gate=gate, fq=fq)
+        if plain and fq is not None and spec_of(self.softmax_fn) is not None:
+            context = attention_core(q, k, v, gate=gate, fq=fq, **kw)
         else:
-            ctx = None
-            if fq is None and head_mask is None and not output_attentions and not (self.training and self.dropout.p > 0.0):
-                ctx = self._calibrate_fused(q, k, v, scale_div=div, attention_mask=attention_mask)  # ranges without the (B,H,S,S) tensors
+            ctx = self._calibrate_fused(q, k, v, scale_div=div, attention_mask=attention_mask) if plain and fq is None else None  # ranges without the (B,H,S,S) tensors
             if ctx is None:
-                ctx, _, probs = unfused_core(q, k, v, softmax_fn=self.softmax_fn, scale_div=div, attention_mask=attention_mask,
-                                             dropout=self.dropout, head_mask=head_mask, fq_scores=self.attn_scores_act_quantizer,
-                                             fq_probs=self.attn_probs_act_quantizer)
-            if gate is not None:
-                ctx = ctx * gate.to(ctx.dtype)
-            context = ctx.permute(0, 2, 1, 3).contiguous().view(ctx.shape[0], ctx.shape[2], self.all_head_size)
-            context = self.context_act_quantizer(context)
+                ctx, _, probs = unfused_core(q, k, v, dropout=self.dropout, head_mask=head_mask, fq_scores=self.attn_scores_act_quantizer,
+                                             fq_probs=self.attn_probs_act_quantizer, **kw)
+            context = self.context_act_quantizer(gated_merge(ctx, gate))
         outputs = (context, probs) if output_attentions else (context,)
         if self.is_decoder:
             outputs = outputs + (new_past,)
@@ -1687,59 +1660,47 @@ class QuantizedOPTAttentionWithExtras(_QuantAttnBase):
     def forward(self, hidden_states, key_value_states=None, past_key_value=None, attention_mask=None, layer_head_mask=None,
                 output_attentions=False):
         bsz, tgt_len, _ = hidden_states.size()
-        if key_value_states is None and past_key_value is None and layer_head_mask is None and not output_attentions and not self.training:
-            fq8 = self._fq(ctx_before_gate=True)
-            if fq8 is not None:
-                if attention_mask is not None and attention_mask.size() != (bsz, 1, tgt_len, tgt_len):
-                    raise ValueError(f"Attention mask should be of size {(bsz, 1, tgt_len, tgt_len)}, but is {attention_mask.size()}")
-                ok, causal8, pad8 = True, False, None
-                if attention_mask is not None:  # HF's decoder mask: causal, plus finfo.min columns for padded keys (checked once per tensor)
-                    causal8, pad8 = classify_causal(attention_mask)
-                    ok = causal8
-                if ok:
-                    gate8 = GateState.evaluate(self, hidden_states, self.num_heads)
-                    done = self._int8_storage_core(hidden_states, (self.q_proj, self.k_proj, self.v_proj), self.num_heads, self.head_dim,
-                                                   scale=self.scaling, scale_div=0.0, causal=causal8, padvec=pad8, mask_min=mask_min_of(attention_mask, hidden_states.dtype),
-                                                   gate=gate8, fq=fq8, want_values=self.is_decoder, consumer=self.out_proj)
-                    if done is not None:
-                        merged, (yk, yv), projected = done
-                        kv = (self._heads(yk, bsz), self._heads(yv, bsz)) if self.is_decoder else past_key_value
-                        return (merged if projected else self.out_proj(merged)), None, kv
+        H, self_attn, cached = self.num_heads, key_value_states is None, past_key_value is not None
+        # nothing observable is asked for: what every route but unfused_core needs
+        plain = layer_head_mask is None and not output_attentions and not (self.training and self.dropout > 0.0)
+        fq = self._fq(ctx_before_gate=True)
+        gate, gated = None, False
+        if plain and not self.training and fq is not None and self_attn and not cached:
+            if attention_mask is not None and attention_mask.size() != (bsz, 1, tgt_len, tgt_len):  # (before any projection runs)
+                raise ValueError(f"Attention mask should be of size {(bsz, 1, tgt_len, tgt_len)}, but is {attention_mask.size()}")
+            # HF's decoder mask: causal, plus finfo.min columns for padded keys (checked once per tensor; the size-checked mask itself, not
+            # through resolve_mask: no split, and a mask that is not causal ends the route here)
+            causal8, pad8 = classify_causal(attention_mask) if attention_mask is not None else (False, None)
+            if causal8 or attention_mask is None:
+                gate, gated = GateState.evaluate(self, hidden_states, H), True
+                done = self._int8_storage_core(hidden_states, (self.q_proj, self.k_proj, self.v_proj), H, self.head_dim, scale=self.scaling, scale_div=0.0,
+                                               causal=causal8, padvec=pad8, mask_min=mask_min_of(attention_mask, hidden_states.dtype),
+                                               gate=gate, fq=fq, want_values=self.is_decoder, consumer=self.out_proj)
+                if done is not None:
+                    merged, (yk, yv), projected = done
+                    kv = (self._heads(yk, bsz), self._heads(yv, bsz)) if self.is_decoder else past_key_value
+                    return (merged if projected else self.out_proj(merged)), None, kv
         q = self._heads(self.q_proj(hidden_states) * self.scaling, bsz)
-        if key_value_states is not None and past_key_value is not None:
-            k, v = past_key_value[0], past_key_value[1]
-        else:
-            src = hidden_states if key_value_states is None else key_value_states
-            k, v = self._heads(self.k_proj(src), bsz), self._heads(self.v_proj(src), bsz)
-            if key_value_states is None and past_key_value is not None:
-                k, v = torch.cat([past_key_value[0], k], dim=2), torch.cat([past_key_value[1], v], dim=2)
+        k, v = kv_source(self.k_proj, self.v_proj, lambda t: self._heads(t, bsz), hidden_states, key_value_states, past_key_value)
         new_past = (k, v) if self.is_decoder else past_key_value
         src_len = k.size(2)
         if attention_mask is not None and attention_mask.size() != (bsz, 1, tgt_len, src_len):
             raise ValueError(f"Attention mask should be of size {(bsz, 1, tgt_len, src_len)}, but is {attention_mask.size()}")
-        gate = GateState.evaluate(self, hidden_states, self.num_heads)
-        fq = self._fq(ctx_before_gate=True)
-        fusable = (fq is not None and spec_of(self.softmax_fn) is not None and layer_head_mask is None and not output_attentions
-                   and not (self.training and self.dropout > 0.0))
+        if not gated:  # (else: the INT8 route declined after the gate was evaluated)
+            gate = GateState.evaluate(self, hidden_states, H)
+        kw = dict(attention_mask=attention_mask, clamp_min=attention_mask is not None)
         weights = None
-        if fusable:
-            merged = attention_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=attention_mask is not None,
-                                    detect_causal=True, gate=gate, fq=fq, decode=key_value_states is None and past_key_value is not None)
+        if plain and fq is not None and spec_of(self.softmax_fn) is not None:
+            merged = attention_core(q, k, v, softmax_fn=self.softmax_fn, detect_causal=True, gate=gate, fq=fq, decode=self_attn and cached, **kw)
         else:
-            ctx, used = None, None
-            if fq is None and layer_head_mask is None and not output_attentions and not (self.training and self.dropout > 0.0):
-                ctx = self._calibrate_fused(q, k, v, attention_mask=attention_mask, clamp_min=attention_mask is not None, detect_causal=True)
+            ctx = self._calibrate_fused(q, k, v, detect_causal=True, **kw) if plain and fq is None else None  # ranges without the (B,H,S,S) tensors
             if ctx is None:
                 hm = None if layer_head_mask is None else layer_head_mask.view(1, -1, 1, 1)
                 drop = (lambda p: nn.functional.dropout(p, p=self.dropout, training=self.training))
-                ctx, _, used = unfused_core(q, k, v, softmax_fn=self.softmax_fn, attention_mask=attention_mask, clamp_min=attention_mask is not None,
-                                            dropout=drop, head_mask=hm, fq_scores=self.attn_scores_act_quantizer,
-                                            fq_probs=self.attn_probs_act_quantizer)
-            weights = used if output_attentions else None
-            ctx = self.context_act_quantizer(ctx)
-            if gate is not None:
-                ctx = ctx * gate.to(ctx.dtype)
-            merged = ctx.transpose(1, 2).reshape(bsz, tgt_len, self.embed_dim)
+                ctx, _, used = unfused_core(q, k, v, softmax_fn=self.softmax_fn, dropout=drop, head_mask=hm, fq_scores=self.attn_scores_act_quantizer,
+                                            fq_probs=self.attn_probs_act_quantizer, **kw)
+                weights = used if output_attentions else None
+            merged = gated_merge(self.context_act_quantizer(ctx), gate)
         return self.out_proj(merged), weights, new_past
 
 

@@ -7,13 +7,12 @@ defined (= dim) so the option works instead of raising AttributeError.
 """
 from __future__ import annotations
 
-from functools import partial
 
 import torch
 from torch import nn
 
-from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, build_gate, fused_train_core, has_hooks, linear_fp32,
-                        unfused_core)
+from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, fused_train_core, gated_merge, has_hooks, init_gate,
+                        linear_fp32, module_gate, unfused_core)
 from .softmax import spec_of
 
 
@@ -42,19 +41,8 @@ class ViTSelfAttentionWithExtras(GateBookkeeping, nn.Module):
         self.gamma, self.ssm_eps, self.tau, self.max_seq_length = gamma, ssm_eps, tau, max_seq_length
         self.softmax_fn = softmax_fn
         self.skip_attn = skip_attn
-        self.last_gate_avg_prob = None
-        self.last_gate_all_probs = None
-        self.attn_gate_type = attn_gate_type
-        self.attn_gate_init = attn_gate_init
-        self.attn_gate_mlp = attn_gate_mlp
-        self.attn_gate_mlp2 = attn_gate_mlp2
-        self.attn_gate_linear_all_features = attn_gate_linear_all_features
-        self.gate_fn = torch.sigmoid
-        self.pooling_fn = partial(torch.mean, dim=1, keepdims=True)
-        self.fine_tuning = fine_tuning
-        self.gate_scaling_factor = 1.0 / attn_gate_init if (fine_tuning and attn_gate_init is not None) else 1.0
-        self.alpha = build_gate(num_heads, self.attention_head_size, dim, attn_gate_type, attn_gate_init, attn_gate_mlp,
-                                attn_gate_mlp2, attn_gate_linear_all_features, fine_tuning, ft_std=0.01)
+        init_gate(self, num_heads, self.attention_head_size, dim, attn_gate_type, attn_gate_init, attn_gate_mlp, attn_gate_mlp2,
+                  attn_gate_linear_all_features, fine_tuning, ft_std=0.01)
 
     def transpose_for_scores(self, x: torch.Tensor) -> torch.Tensor:
         return x.view(x.size()[:-1] + (self.num_attention_heads, self.attention_head_size)).permute(0, 2, 1, 3)
@@ -64,32 +52,21 @@ class ViTSelfAttentionWithExtras(GateBookkeeping, nn.Module):
         H, d = self.num_attention_heads, self.attention_head_size
         q, k, v = linear_fp32(self.qkv, x).reshape(B, N, 3, H, d).permute(2, 0, 3, 1, 4).unbind(0)  # (B,H,N,d) views, unit d stride
         q, k = self.q_norm(q), self.k_norm(k)
-        fusable = (spec_of(self.softmax_fn) is not None and not (self.training and self.attn_drop.p > 0.0) and not autograd_needed(self, x, q, k, v)
-                   and not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout))
-        gp = GateState.predictor(self, x, H, self.gate_scaling_factor) if fusable else None  # gate evaluated in the kernel
-        gate = None
-        if gp is None:
-            gate = GateState.evaluate(self, x, H)
-            if gate is not None and self.attn_gate_type != AttentionGateType.unconditional_per_head:
-                gate = gate * self.gate_scaling_factor
+        plain = not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout)  # nothing observable is asked for
+        fusable = (plain and spec_of(self.softmax_fn) is not None and not (self.training and self.attn_drop.p > 0.0)
+                   and not autograd_needed(self, x, q, k, v))
+        gate, gp = module_gate(self, x, H, in_kernel=fusable)
+        kw = dict(softmax_fn=self.softmax_fn, scale=self.scale)
         if fusable:
-            merged = attention_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale, gate=gate, gate_mlp=gp)
+            merged = attention_core(q, k, v, gate=gate, gate_mlp=gp, **kw)
             if gp is not None:
                 GateState.finish_predictor(self, gp, H)
         else:
-            ctx = None
-            if not has_hooks(self.attn_scores, self.attn_probs_before_dropout, self.attn_probs_after_dropout):
-                # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
-                # also needs attention.FUSED_DROPOUT)
-                ctx = fused_train_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale, dropout_p=self.attn_drop.p if self.training else 0.0)
-            if ctx is not None:
-                if gate is not None:
-                    ctx = ctx * gate.to(ctx.dtype)
-                return self.proj_drop(linear_fp32(self.proj, ctx.transpose(1, 2).reshape(B, N, C)))
-            ctx, _, _ = unfused_core(q, k, v, softmax_fn=self.softmax_fn, scale=self.scale, scores_tap=self.attn_scores,
-                                     probs_tap=self.attn_probs_before_dropout, dropout=self.attn_drop,
-                                     probs_after_tap=self.attn_probs_after_dropout)
-            if gate is not None:
-                ctx = ctx * gate.to(ctx.dtype)
-            merged = ctx.transpose(1, 2).reshape(B, N, C)
+            # training with attention.FUSED_BACKWARD on: the HIP training kernels (None: switch off / not supported; dropout > 0
+            # also needs attention.FUSED_DROPOUT)
+            ctx = fused_train_core(q, k, v, dropout_p=self.attn_drop.p if self.training else 0.0, **kw) if plain else None
+            if ctx is None:
+                ctx, _, _ = unfused_core(q, k, v, scores_tap=self.attn_scores, probs_tap=self.attn_probs_before_dropout, dropout=self.attn_drop,
+                                         probs_after_tap=self.attn_probs_after_dropout, **kw)
+            merged = gated_merge(ctx, gate)
         return self.proj_drop(linear_fp32(self.proj, merged))

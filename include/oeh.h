@@ -775,6 +775,47 @@ int oeh_grad_norm(const void* plan_dev, int64_t n_chunks, double max_norm, void*
 int oeh_grad_scale(const void* plan_dev, int64_t n_chunks, const double* clip4, void* stream);
 int oeh_adamw_step(const void* plan_dev, int64_t n_chunks, const oeh_adamw_desc* d, const double* clip4 /* may be NULL */, void* stream);
 
+/* The same phase under fp16 loss scaling (run_clm.py:587-606, a GradScaler loop): the unscale is folded into the clip coefficient, the
+ * overflow check is the norm's own float64 sum, a skipped step is one uniform early return, and the step counters live on the device -
+ * whether a step was skipped is known only there.  Nothing here reads anything back.
+ * oeh_grad_norm_amp: oeh_grad_norm's two launches (the same per-chunk partials pass, then a finalize of the same sum).  grad_scale, found_in
+ *   and found_acc are device pointers to one fp32 each; each may be NULL.  With s = (double)*grad_scale (NULL: 1) and
+ *     found = !isfinite(sumsq) || (found_in && *found_in != 0) || !(s > 0 && isfinite(s))
+ *   the finalize writes
+ *     out4 = {sumsq of the gradients as stored, norm = sqrt(sumsq) / s, coef = clipc / s, found ? 1.0 : 0.0}
+ *   clipc = min(1, max_norm / (norm + 1e-6)) from THAT norm, 1 for max_norm <= 0, NaN or +inf.  A power-of-two s changes neither norm nor
+ *   clipc by a bit.  If found and found_acc is not NULL the one finalizing thread stores *found_acc = 1.0f; nothing is stored there
+ *   otherwise (several optimizers may share one accumulator: it holds the OR of their flags).
+ *   Refusals: oeh_grad_norm's, and OEH_EALIGN for grad_scale, found_in or found_acc off 4 bytes.
+ * oeh_adamw_step_amp: two launches, `advance` then `step`.  d->step[] is not read: the counters are steps[], fp32 and integer-valued on the
+ *   device (torch's fused / capturable convention), and slot[i] (int32, device) is the counter of plan record i.  No two records may share
+ *   a slot - the device cannot tell.  clip4 is required: an out4 of oeh_grad_norm_amp.  work: oeh_adamw_amp_work_bytes(n_tensors) = 8
+ *   bytes per record, 4-byte aligned, device.
+ *   advance: one thread per record i, j = slot[i].  A record whose group is not below n_groups is left alone, counter included.  Otherwise
+ *     t = steps[j] + (clip4[3] != 0 ? 0 : 1);  steps[j] = t is stored only when clip4[3] == 0;
+ *     work[i] = {bc2 = RN32(sqrt(1 - pw(beta2, t))), ss = RN32(lr / (1 - pw(beta1, t)))}   (two fp32; zeros when t < 1)
+ *   in double from the descriptor's fp32 fields, plain `/` and sqrt, and pw binary exponentiation - IEEE multiplications only:
+ *     r = 1; base = beta; n = (int64)t;  while (n) { if (n & 1) r *= base;  n >>= 1;  if (n) base *= base; }
+ *   It depends on t alone: a resumed run equals an uninterrupted one.
+ *   step: if (clip4[3] != 0) return; first - uniform, one scalar load: on a skipped step p, m and v are neither read nor written.  Then
+ *   oeh_adamw_step's arithmetic, operation for operation, with bc2 and ss from work[record] and c = clip4[2] rounded to fp32 once; the
+ *   other five constants are the host's, as there.
+ *   Refusals: oeh_adamw_step's without the step < 1 rule; OEH_EINVAL - n_tensors < 0, or clip4, steps, slot or work NULL with n_chunks > 0;
+ *   OEH_EALIGN - clip4 off 8 bytes, steps, slot or work off 4.  n_chunks == 0: OEH_OK without a launch.
+ * oeh_loss_scale_update: state4 = {scale, growth_tracker, found, skipped}, four fp32 on the device, integer-valued where they count.  One
+ *   thread applies torch's _amp_update_scale_ rule:
+ *     found != 0:               scale = RN32(scale * (float)backoff_factor), tracker = 0, skipped += 1
+ *     tracker + 1 == interval:  ns = RN32(scale * (float)growth_factor); scale = ns when ns is finite; tracker = 0
+ *     otherwise:                tracker += 1
+ *   and then found = 0.  Refusals: OEH_EINVAL - state4 NULL, a factor that is not positive and finite, growth_interval < 1; OEH_EALIGN -
+ *   state4 off 4 bytes. */
+int oeh_grad_norm_amp(const void* plan_dev, int64_t n_chunks, double max_norm, const float* grad_scale /* may be NULL */,
+                      const float* found_in /* may be NULL */, float* found_acc /* may be NULL */, void* work, double* out4, void* stream);
+int64_t oeh_adamw_amp_work_bytes(int32_t n_tensors);
+int oeh_adamw_step_amp(const void* plan_dev, int64_t n_chunks, int32_t n_tensors, const oeh_adamw_desc* d, const double* clip4, float* steps,
+                       const int32_t* slot, void* work, void* stream);
+int oeh_loss_scale_update(float* state4, double growth_factor, double backoff_factor, int32_t growth_interval, void* stream);
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -6,7 +6,7 @@ Python host surface mirroring the reference's plugin interface:
     Quantized{Bert,OPT}...AttentionWithExtras, QuantEmbedding / QuantizedBertEmbeddings / opt_embed_front, kurtosis / inf_norm / OutlierMeter (the reference's result metrics),
     cross_entropy / FusedCrossEntropyLoss / causal_lm_loss / masked_lm_loss / PerplexityMeter (the models' loss and the perplexity),
     dropout_add_layer_norm / FusedDropoutAddLayerNorm / FusedBertSelfOutput / FusedBertOutput / fuse_block_tails (the block tail in training),
-    FusedAdamW / clip_grad_norm_ (the optimizer step with the global-norm clip folded in)
+    FusedAdamW / clip_grad_norm_ (the optimizer step with the global-norm clip folded in), LossScaler (fp16 loss scaling without a host synchronisation)
 over the C-ABI library `lib/liboeh_hip.so` (include/oeh.h).  There is no CPU implementation in this package:
 every op raises if the HIP library is missing or a tensor is not on a GPU.
 """
@@ -19,7 +19,7 @@ from .layers import (FusedBertOutput, FusedBertSelfOutput, FusedDropoutAddLayerN
 from .losses import FusedCrossEntropyLoss, PerplexityMeter, causal_lm_loss, cross_entropy, masked_lm_loss  # noqa: F401
 from .hopfield import Association, Hopfield, HopfieldPooling  # noqa: F401
 from .opt_attention import OPTAttentionWithExtras  # noqa: F401
-from .optim import FusedAdamW, clip_grad_norm_  # noqa: F401
+from .optim import FusedAdamW, LossScaler, clip_grad_norm_  # noqa: F401
 from .ops import AttnFakeQuant, FakeQuantSpec, SoftmaxSpec, attn_fwd, fake_quant, inf_norm, kurtosis, outlier_stats, softmax_rows  # noqa: F401
 from .outliers import OutlierMeter  # noqa: F401
 from .quantization import (  # noqa: F401

@@ -151,6 +151,7 @@ EXPORTS = (
     "oeh_xent_fwd", "oeh_xent_bwd", "oeh_xent_variant",
     "oeh_drop_resid_ln_fwd", "oeh_drop_resid_ln_bwd_work_bytes", "oeh_drop_resid_ln_bwd", "oeh_drop_resid_ln_mask", "oeh_drop_resid_ln_variant",
     "oeh_mt_plan_bytes", "oeh_mt_plan", "oeh_mt_variant", "oeh_grad_norm_work_bytes", "oeh_grad_norm", "oeh_grad_scale", "oeh_adamw_step",
+    "oeh_grad_norm_amp", "oeh_adamw_amp_work_bytes", "oeh_adamw_step_amp", "oeh_loss_scale_update",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
@@ -279,6 +280,14 @@ def load() -> C.CDLL:
     lib.oeh_grad_scale.restype = C.c_int
     lib.oeh_adamw_step.argtypes = [vp, i64, C.POINTER(oeh_adamw_desc), vp, vp]
     lib.oeh_adamw_step.restype = C.c_int
+    lib.oeh_grad_norm_amp.argtypes = [vp, i64, f64, vp, vp, vp, vp, vp, vp]
+    lib.oeh_grad_norm_amp.restype = C.c_int
+    lib.oeh_adamw_amp_work_bytes.argtypes = [i32]
+    lib.oeh_adamw_amp_work_bytes.restype = C.c_int64
+    lib.oeh_adamw_step_amp.argtypes = [vp, i64, i32, C.POINTER(oeh_adamw_desc), vp, vp, vp, vp, vp]
+    lib.oeh_adamw_step_amp.restype = C.c_int
+    lib.oeh_loss_scale_update.argtypes = [vp, f64, f64, i32, vp]
+    lib.oeh_loss_scale_update.restype = C.c_int
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

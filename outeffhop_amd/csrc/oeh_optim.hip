@@ -16,6 +16,10 @@
 //     (0 + 1) + (2 + 3); the second launch adds the chunk partials in a fixed order too.  No atomics: the same bits on every call.
 //   * Step: fp32, every operation rounded on its own (-ffp-contract=off), plain `/` and sqrt (correctly rounded, denormals kept); the
 //     per-group constants are formed in double by the host and rounded once.  The clip coefficient is read from the device.
+//   * Under fp16 loss scaling (oeh_grad_norm_amp, oeh_adamw_step_amp, oeh_loss_scale_update): the norm's finalize divides the scale out of
+//     norm and coefficient and raises the flag when the sum is not finite; the step is the same body behind one uniform early return on
+//     that flag, with the two constants that depend on the step number formed on the device from fp32 counters kept there (a launch of one
+//     thread per tensor); the scale's update is one thread.  Nothing is read back and the gradients get no pass of their own.
 #include "../../include/oeh.h"
 #include "oeh_desc.h"
 #include "oeh_launch.h"
@@ -234,8 +238,8 @@ __global__ __launch_bounds__(256) void oeh_mt_sumsq_kernel(const MtArgs a, doubl
 }
 
 constexpr int kNormT = 1024, kNormU = 8;  // threads of the second launch; partials a thread has in flight
-__global__ __launch_bounds__(kNormT) void oeh_mt_norm_kernel(const double* __restrict__ partial, const long n, const double max_norm,
-                                                             double* __restrict__ out4) {
+// the sum of the chunk partials in the fixed order of include/oeh.h; thread 0 has it
+__device__ __forceinline__ double norm_sumsq(const double* __restrict__ partial, const long n) {
   constexpr int W = kNormT / 64;
   __shared__ double red[W];
   const int t = threadIdx.x;
@@ -253,23 +257,56 @@ __global__ __launch_bounds__(kNormT) void oeh_mt_norm_kernel(const double* __res
   acc = wave_sum(acc);
   if ((t & 63) == 0) red[t >> 6] = acc;
   __syncthreads();
+  double s[W];
   if (t == 0) {
-    double s[W];
 #pragma unroll
     for (int w = 0; w < W; ++w) s[w] = red[w];
 #pragma unroll
     for (int w = W / 2; w >= 1; w >>= 1)
 #pragma unroll
       for (int i = 0; i < w; ++i) s[i] = s[2 * i] + s[2 * i + 1];
-    const double sumsq = s[0], norm = __builtin_sqrt(sumsq);
-    double coef = 1.0;
-    if (max_norm > 0.0 && max_norm < __builtin_inf()) {
-      const double c = max_norm / (norm + 1e-6);
-      coef = c > 1.0 ? 1.0 : c;  // (NaN stays NaN, as torch's clamp)
-    }
+  } else {
+    s[0] = 0.0;
+  }
+  return s[0];
+}
+// oeh_grad_norm's coefficient from a norm: 1 when max_norm <= 0, NaN or +inf
+__device__ __forceinline__ double clip_coef(const double norm, const double max_norm) {
+  double coef = 1.0;
+  if (max_norm > 0.0 && max_norm < __builtin_inf()) {
+    const double c = max_norm / (norm + 1e-6);
+    coef = c > 1.0 ? 1.0 : c;  // (NaN stays NaN, as torch's clamp)
+  }
+  return coef;
+}
+
+// the finalize under loss scaling (include/oeh.h: oeh_grad_norm_amp): the same sum, the scale divided out of norm and coefficient, the flag
+__global__ __launch_bounds__(kNormT) void oeh_mt_norm_amp_kernel(const double* __restrict__ partial, const long n, const double max_norm,
+                                                                 const float* __restrict__ grad_scale, const float* __restrict__ found_in,
+                                                                 float* __restrict__ found_acc, double* __restrict__ out4) {
+  const double sumsq = norm_sumsq(partial, n);
+  if (threadIdx.x == 0) {
+    const double s = grad_scale != nullptr ? (double)*grad_scale : 1.0;
+    const bool s_ok = s > 0.0 && s < __builtin_inf();
+    const bool finite = __builtin_fabs(sumsq) < __builtin_inf();  // (false for NaN)
+    const bool found = !finite || (found_in != nullptr && *found_in != 0.0f) || !s_ok;
+    const double norm = __builtin_sqrt(sumsq) / s;
     out4[0] = sumsq;
     out4[1] = norm;
-    out4[2] = coef;
+    out4[2] = clip_coef(norm, max_norm) / s;
+    out4[3] = found ? 1.0 : 0.0;
+    if (found && found_acc != nullptr) *found_acc = 1.0f;
+  }
+}
+
+__global__ __launch_bounds__(kNormT) void oeh_mt_norm_kernel(const double* __restrict__ partial, const long n, const double max_norm,
+                                                             double* __restrict__ out4) {
+  const double sumsq = norm_sumsq(partial, n);
+  if (threadIdx.x == 0) {
+    const double norm = __builtin_sqrt(sumsq);
+    out4[0] = sumsq;
+    out4[1] = norm;
+    out4[2] = clip_coef(norm, max_norm);
     out4[3] = 0.0;
   }
 }
@@ -293,17 +330,49 @@ __global__ __launch_bounds__(256) void oeh_mt_scale_kernel(const MtArgs a, const
 }
 
 // ---- the step
-__global__ __launch_bounds__(256) void oeh_adamw_kernel(const AdamwArgs a) {
+// the loss-scaling form's arguments: bc2 and ss per plan record from the advance launch, the other five constants per group from the host
+struct AdamwAmpArgs {
+  MtArgs mt;
+  const double* clip;  // required: clip[2] the coefficient, clip[3] != 0 skips the step
+  const float* work;   // {bc2, ss} per record
+  int n_groups;
+  float decay[kMaxGroups], omb1[kMaxGroups], b2[kMaxGroups], omb2[kMaxGroups], eps[kMaxGroups];
+};
+struct AdvanceArgs {
+  const MtRec* recs;
+  const double* clip;
+  float* steps;
+  const int* slot;
+  float* work;
+  int n_tensors, n_groups;
+  float lr[kMaxGroups], b1[kMaxGroups], b2[kMaxGroups];
+};
+
+// One body for both kernels: AMP = false is oeh_adamw_step's launch, AMP = true the step under loss scaling - the skip in front, bc2 and
+// ss from the device; the arithmetic per element is the same text.
+template <bool AMP, class Args>
+__device__ __forceinline__ void adamw_body(const Args& a) {
+  if constexpr (AMP) {
+    if (a.clip[3] != 0.0) return;  // (uniform) an overflow was found: p, m and v are neither read nor written
+  }
   const int t = threadIdx.x;
-  long off;
-  int cnt;
-  const MtRec& r = chunk_of(a.mt, off, cnt);
+  const MtEntry e = a.mt.entries[blockIdx.x];
+  const long off = e.off;
+  const int cnt = e.count;
+  const MtRec& r = a.mt.recs[e.tensor];
   const void* gp = r.g;
   void *pp = r.p, *mp = r.m, *vp = r.v;
   const int grp = r.group;
   if (grp < 0 || grp >= a.n_groups) return;  // (uniform) a tensor of a group the descriptor does not have is left as it is
-  const GroupK k = {a.decay[grp], a.omb1[grp], a.b2[grp], a.omb2[grp], a.bc2[grp], a.eps[grp], a.ss[grp]};
-  const float c = a.clip != nullptr ? (float)a.clip[2] : 1.0f;
+  GroupK k;
+  float c;
+  if constexpr (AMP) {
+    k = GroupK{a.decay[grp], a.omb1[grp], a.b2[grp], a.omb2[grp], a.work[2 * e.tensor], a.eps[grp], a.work[2 * e.tensor + 1]};
+    c = (float)a.clip[2];
+  } else {
+    k = GroupK{a.decay[grp], a.omb1[grp], a.b2[grp], a.omb2[grp], a.bc2[grp], a.eps[grp], a.ss[grp]};
+    c = a.clip != nullptr ? (float)a.clip[2] : 1.0f;
+  }
   dispatch_chunk(r.g_dtype, r.vec16, cnt, [&](auto in, auto mode) {
     constexpr int IN = decltype(in)::value, MODE = decltype(mode)::value;
     float g[kPer], p[kPer], m[kPer], v[kPer];
@@ -326,6 +395,59 @@ __global__ __launch_bounds__(256) void oeh_adamw_kernel(const AdamwArgs a) {
     mt_store<IN_F32, MODE>(mp, off, cnt, t, m);
     mt_store<IN_F32, MODE>(vp, off, cnt, t, v);
   });
+}
+__global__ __launch_bounds__(256) void oeh_adamw_kernel(const AdamwArgs a) { adamw_body<false>(a); }
+__global__ __launch_bounds__(256) void oeh_adamw_amp_kernel(const AdamwAmpArgs a) { adamw_body<true>(a); }
+
+// beta^n by binary exponentiation (include/oeh.h): IEEE multiplications only, so that numpy gives the same bits
+__device__ __forceinline__ double pw(const double beta, long n) {
+  double r = 1.0, base = beta;
+  while (n) {
+    if (n & 1) r *= base;
+    n >>= 1;
+    if (n) base *= base;
+  }
+  return r;
+}
+// the counters: one thread per plan record
+__global__ __launch_bounds__(256) void oeh_adamw_advance_kernel(const AdvanceArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_tensors) return;
+  const int grp = a.recs[i].group;
+  if (grp < 0 || grp >= a.n_groups) return;
+  const bool found = a.clip[3] != 0.0;
+  const int j = a.slot[i];
+  const float t = a.steps[j] + (found ? 0.0f : 1.0f);
+  if (!found) a.steps[j] = t;
+  float bc2 = 0.0f, ss = 0.0f;
+  if (t >= 1.0f) {
+    const long n = (long)t;
+    bc2 = (float)__builtin_sqrt(1.0 - pw((double)a.b2[grp], n));
+    ss = (float)((double)a.lr[grp] / (1.0 - pw((double)a.b1[grp], n)));
+  }
+  a.work[2 * i] = bc2;
+  a.work[2 * i + 1] = ss;
+}
+
+// the loss scale (include/oeh.h: oeh_loss_scale_update): one thread
+__global__ void oeh_loss_scale_kernel(float* __restrict__ st, const float growth, const float backoff, const float interval) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float scale = st[0], tracker = st[1], skipped = st[3];
+  if (st[2] != 0.0f) {
+    scale = scale * backoff;
+    tracker = 0.0f;
+    skipped = skipped + 1.0f;
+  } else if (tracker + 1.0f == interval) {
+    const float ns = scale * growth;
+    if (__builtin_fabsf(ns) < __builtin_inff()) scale = ns;
+    tracker = 0.0f;
+  } else {
+    tracker = tracker + 1.0f;
+  }
+  st[0] = scale;
+  st[1] = tracker;
+  st[2] = 0.0f;
+  st[3] = skipped;
 }
 
 // ---- host
@@ -357,6 +479,11 @@ MtArgs plan_view(const void* plan_dev, const int64_t n_chunks) {
 int plan_args_check(const void* plan_dev, const int64_t n_chunks) {
   if (n_chunks < 0 || (plan_dev == nullptr && n_chunks > 0)) return OEH_EINVAL;
   return n_chunks >= ((int64_t)1 << 31) ? OEH_ENOTSUP : OEH_OK;
+}
+
+bool hyper_ok(const oeh_adamw_desc& d, const int i) {
+  if (!(d.lr[i] >= 0.0f) || !(d.eps[i] >= 0.0f) || !(d.weight_decay[i] >= 0.0f)) return false;
+  return d.beta1[i] >= 0.0f && d.beta1[i] < 1.0f && d.beta2[i] >= 0.0f && d.beta2[i] < 1.0f;
 }
 
 }  // namespace
@@ -422,8 +549,7 @@ int oeh_adamw_step(const void* plan_dev, int64_t n_chunks, const oeh_adamw_desc*
   AdamwArgs a;
   std::memset(&a, 0, sizeof a);
   for (int i = 0; i < d->n_groups; ++i) {
-    if (d->step[i] < 1 || !(d->lr[i] >= 0.0f) || !(d->eps[i] >= 0.0f) || !(d->weight_decay[i] >= 0.0f)) return OEH_EINVAL;
-    if (!(d->beta1[i] >= 0.0f && d->beta1[i] < 1.0f) || !(d->beta2[i] >= 0.0f && d->beta2[i] < 1.0f)) return OEH_EINVAL;
+    if (d->step[i] < 1 || !hyper_ok(*d, i)) return OEH_EINVAL;
     const double lr = d->lr[i], b1 = d->beta1[i], b2 = d->beta2[i], wd = d->weight_decay[i], t = (double)d->step[i];
     a.decay[i] = (float)(1.0 - lr * wd);
     a.omb1[i] = (float)(1.0 - b1);
@@ -441,6 +567,71 @@ int oeh_adamw_step(const void* plan_dev, int64_t n_chunks, const oeh_adamw_desc*
   a.clip = clip4;
   a.n_groups = d->n_groups;
   hipLaunchKernelGGL(oeh_adamw_kernel, dim3((unsigned)n_chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return launch_status();
+}
+
+int oeh_grad_norm_amp(const void* plan_dev, int64_t n_chunks, double max_norm, const float* grad_scale, const float* found_in, float* found_acc,
+                      void* work, double* out4, void* stream) {
+  if (out4 == nullptr || (work == nullptr && n_chunks > 0)) return OEH_EINVAL;
+  const int rc = plan_args_check(plan_dev, n_chunks);
+  if (rc != OEH_OK) return rc;
+  if ((addr(work) | addr(out4)) % 8 != 0 || (addr(grad_scale) | addr(found_in) | addr(found_acc)) % 4 != 0) return OEH_EALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (n_chunks > 0) hipLaunchKernelGGL(oeh_mt_sumsq_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, plan_view(plan_dev, n_chunks), static_cast<double*>(work));
+  hipLaunchKernelGGL(oeh_mt_norm_amp_kernel, dim3(1), dim3(kNormT), 0, st, static_cast<const double*>(work), (long)n_chunks, max_norm, grad_scale, found_in,
+                     found_acc, out4);
+  return launch_status();
+}
+
+int64_t oeh_adamw_amp_work_bytes(int32_t n_tensors) { return n_tensors < 0 ? 0 : (int64_t)n_tensors * 8; }
+
+int oeh_adamw_step_amp(const void* plan_dev, int64_t n_chunks, int32_t n_tensors, const oeh_adamw_desc* d, const double* clip4, float* steps,
+                       const int32_t* slot, void* work, void* stream) {
+  if (d == nullptr || d->n_groups < 1 || d->n_groups > kMaxGroups || d->reserved != 0 || n_tensors < 0) return OEH_EINVAL;
+  AdamwAmpArgs a;
+  AdvanceArgs adv;
+  std::memset(&a, 0, sizeof a);
+  std::memset(&adv, 0, sizeof adv);
+  for (int i = 0; i < d->n_groups; ++i) {
+    if (!hyper_ok(*d, i)) return OEH_EINVAL;
+    const double lr = d->lr[i], b1 = d->beta1[i], b2 = d->beta2[i], wd = d->weight_decay[i];
+    a.decay[i] = (float)(1.0 - lr * wd);
+    a.omb1[i] = (float)(1.0 - b1);
+    a.b2[i] = d->beta2[i];
+    a.omb2[i] = (float)(1.0 - b2);
+    a.eps[i] = d->eps[i];
+    adv.lr[i] = d->lr[i];
+    adv.b1[i] = d->beta1[i];
+    adv.b2[i] = d->beta2[i];
+  }
+  const int rc = plan_args_check(plan_dev, n_chunks);
+  if (rc != OEH_OK) return rc;
+  if (n_chunks > 0 && (clip4 == nullptr || steps == nullptr || slot == nullptr || work == nullptr)) return OEH_EINVAL;
+  if (addr(clip4) % 8 != 0 || (addr(steps) | addr(slot) | addr(work)) % 4 != 0) return OEH_EALIGN;
+  if (n_chunks == 0) return OEH_OK;
+  a.mt = plan_view(plan_dev, n_chunks);
+  a.clip = clip4;
+  a.work = static_cast<const float*>(work);
+  a.n_groups = d->n_groups;
+  adv.recs = a.mt.recs;
+  adv.clip = clip4;
+  adv.steps = steps;
+  adv.slot = slot;
+  adv.work = static_cast<float*>(work);
+  adv.n_tensors = n_tensors;
+  adv.n_groups = d->n_groups;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (n_tensors > 0) hipLaunchKernelGGL(oeh_adamw_advance_kernel, dim3((unsigned)((n_tensors + 255) / 256)), dim3(256), 0, st, adv);
+  hipLaunchKernelGGL(oeh_adamw_amp_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, a);
+  return launch_status();
+}
+
+int oeh_loss_scale_update(float* state4, double growth_factor, double backoff_factor, int32_t growth_interval, void* stream) {
+  if (state4 == nullptr || growth_interval < 1) return OEH_EINVAL;
+  if (!(growth_factor > 0.0 && std::isfinite(growth_factor)) || !(backoff_factor > 0.0 && std::isfinite(backoff_factor))) return OEH_EINVAL;
+  if (addr(state4) % 4 != 0) return OEH_EALIGN;
+  hipLaunchKernelGGL(oeh_loss_scale_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), state4, (float)growth_factor, (float)backoff_factor,
+                     (float)growth_interval);
   return launch_status();
 }
 

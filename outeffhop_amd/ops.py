@@ -1490,6 +1490,118 @@ def adamw_step(plan: MtPlan, groups, clip: Optional[torch.Tensor] = None) -> Non
     _lib.check(rc, "oeh_adamw_step")
 
 
+# ---- the same phase under fp16 loss scaling (include/oeh.h: oeh_grad_norm_amp, oeh_adamw_step_amp, oeh_loss_scale_update)
+_adamw_amp_work = {}  # (device index, stream handle) -> the {bc2, ss} pair per plan record of that stream's step
+
+
+def _need_f32_scalar(t: Optional[torch.Tensor], what: str) -> None:
+    if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+        raise ValueError(f"{what} must be a float32 tensor of one element")
+
+
+def grad_norm_amp(plan: MtPlan, max_norm: Optional[float] = None, *, grad_scale: Optional[torch.Tensor] = None, found_inf: Optional[torch.Tensor] = None,
+                  found_acc: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`grad_norm` for gradients that carry a loss scale (`include/oeh.h: oeh_grad_norm_amp`): (4,) float64 {sum of squares of the gradients
+    as stored, norm / s, clip coefficient / s, 1 if the step must be skipped else 0}.  grad_scale (s), found_inf and found_acc are
+    one-element float32 tensors on the plan's GPU, each optional: the step is skipped when the sum is not finite, when found_inf is not 0 or
+    when s is not a positive finite number; found_acc is then set to 1 and left alone otherwise.  Two launches, nothing synchronises."""
+    if plan.device is None:
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    lib = _lib.load()
+    _need_gpu(grad_scale, found_inf, found_acc, out, plan.table)
+    for t_, what in ((grad_scale, "grad_scale"), (found_inf, "found_inf"), (found_acc, "found_acc")):
+        _need_f32_scalar(t_, what)
+    if out is not None:
+        _need_f64(out, 4, "out must be a contiguous float64 tensor of 4 elements")
+    out4 = out if out is not None else torch.empty(4, dtype=torch.float64, device=plan.device)
+    work = _scratch(_grad_norm_work, plan.device, max(int(lib.oeh_grad_norm_work_bytes(plan.n_chunks)), 8))
+    with _on_device(plan.device):
+        rc = lib.oeh_grad_norm_amp(_ptr(plan.table), plan.n_chunks, 0.0 if max_norm is None else float(max_norm), _ptr(grad_scale), _ptr(found_inf),
+                                   _ptr(found_acc), _ptr(work), _ptr(out4), _stream())
+    _lib.check(rc, "oeh_grad_norm_amp")
+    return out4
+
+
+class MtSlots:
+    """Which device step counter each record of a plan advances (`mt_slots`): the int32 table on the device, the pinned copy it was sent
+    from, and the entries as a tuple."""
+
+    def __init__(self, table, staging, entries):
+        self.table, self.staging, self.entries = table, staging, entries
+
+
+def mt_slots(plan: MtPlan, slots, *, replace: Optional[MtSlots] = None) -> MtSlots:
+    """The slot table of `adamw_step_amp` for `plan`: slots[i] is the index into `steps` of the plan's i-th non-empty tensor.  Entries must
+    be distinct (two records that shared a counter would advance it twice; the device cannot tell) and as many as the plan has records.
+    One small copy from pinned memory in stream order; replace: a table of the caller's to write over in place where it has the size."""
+    entries = tuple(int(s) for s in slots)
+    if plan.device is None:
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    if len(entries) != len(plan._records):
+        raise ValueError(f"the plan has {len(plan._records)} records, got {len(entries)} slots")
+    if len(set(entries)) != len(entries) or any(not 0 <= s < 2 ** 31 for s in entries):
+        raise ValueError("slots must be distinct indices: two records must not share a step counter")
+    host = torch.empty(max(len(entries), 1), dtype=torch.int32, pin_memory=True)
+    host[:len(entries)] = torch.tensor(entries, dtype=torch.int32)
+    with _on_device(plan.device):
+        if replace is not None and replace.table.device == plan.device and replace.table.numel() == host.numel():
+            table = replace.table
+            table.copy_(host, non_blocking=True)
+        else:
+            table = host.to(plan.device, non_blocking=True)
+    return MtSlots(table, host, entries)
+
+
+def adamw_step_amp(plan: MtPlan, groups, clip: torch.Tensor, steps: torch.Tensor, slots) -> torch.Tensor:
+    """One AdamW step of every tensor of the plan under loss scaling (`include/oeh.h: oeh_adamw_step_amp`), two launches.  groups: as for
+    `adamw_step`, their `step` ignored - the counters are `steps`, a contiguous float32 tensor on the plan's GPU, and record i advances
+    steps[slots[i]] (`slots`: an `MtSlots` of this plan, or the indices themselves).  clip: a `grad_norm_amp` result; when its flag is set
+    nothing is read or written - parameters, moments and counters stay.  Returns the (records, 2) float32 table {sqrt(1 - beta2^t),
+    lr / (1 - beta1^t)} the step used: the stream's scratch, written again by the next call.  Nothing synchronises."""
+    if plan.device is None:
+        raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+    if plan.norm_only:
+        raise ValueError("this plan was made without exp_avgs and exp_avg_sqs: it serves grad_norm and grad_scale_ only")
+    groups = list(groups)
+    if not 1 <= len(groups) <= MT_MAX_GROUPS:
+        raise ValueError(f"adamw_step_amp takes 1 to {MT_MAX_GROUPS} groups")
+    if plan.groups and max(plan.groups) >= len(groups):
+        raise ValueError("a tensor of the plan names a group that was not given")
+    if not isinstance(slots, MtSlots):
+        slots = mt_slots(plan, slots)
+    n = len(plan._records)
+    if len(slots.entries) != n:
+        raise ValueError(f"the plan has {n} records, the slot table {len(slots.entries)} entries")
+    _need_gpu(clip, steps, slots.table, plan.table)
+    _need_f64(clip, 4, "clip must be the (4,) float64 result of grad_norm_amp")
+    if steps.dtype != torch.float32 or not steps.is_contiguous():
+        raise ValueError("steps must be a contiguous float32 tensor")
+    if slots.entries and max(slots.entries) >= steps.numel():
+        raise ValueError(f"slot {max(slots.entries)} is outside the {steps.numel()} step counters")
+    d = _lib.oeh_adamw_desc()
+    d.n_groups = len(groups)
+    for i, g in enumerate(groups):
+        d.lr[i], d.beta1[i], d.beta2[i], d.eps[i], d.weight_decay[i] = g.lr, g.beta1, g.beta2, g.eps, g.weight_decay
+    lib = _lib.load()
+    work = _scratch(_adamw_amp_work, plan.device, max(int(lib.oeh_adamw_amp_work_bytes(n)), 8))
+    with _on_device(plan.device):
+        rc = lib.oeh_adamw_step_amp(_ptr(plan.table), plan.n_chunks, n, C.byref(d), _ptr(clip), _ptr(steps), _ptr(slots.table), _ptr(work), _stream())
+    _lib.check(rc, "oeh_adamw_step_amp")
+    return work.view(torch.float32)[:2 * n].view(n, 2)
+
+
+def loss_scale_update(state: torch.Tensor, growth_factor: float, backoff_factor: float, growth_interval: int) -> None:
+    """torch's _amp_update_scale_ rule on `state`, four float32 {scale, growth tracker, found, skipped} on a GPU, in one launch
+    (`include/oeh.h: oeh_loss_scale_update`): back off and count the skip when found is set, grow after growth_interval clean steps
+    (never to inf), then clear found."""
+    dev = _need_gpu(state)
+    if state.dtype != torch.float32 or state.numel() != 4 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float32 tensor of 4 elements")
+    with _on_device(dev):
+        rc = _lib.load().oeh_loss_scale_update(_ptr(state), float(growth_factor), float(backoff_factor), int(growth_interval), _stream())
+    _lib.check(rc, "oeh_loss_scale_update")
+
+
 _calib_work = {}  # (device index, stream handle) -> the 36-KB histograms of that stream's on-device percentile selection
 
 

@@ -11,8 +11,20 @@ The reference's loops build torch.optim.AdamW over a decay and a no-decay group 
 
 The update is include/oeh.h's (oeh_adamw_step): fp32, every operation rounded on its own; DESIGN.md section 17 bounds it against float64.
 It is not bit-equal to torch.optim.AdamW, whose lerp and addcmul contract.  State has torch's key names (step, exp_avg, exp_avg_sq; step a
-CPU fp32 scalar), so a state_dict() loads into torch.optim.AdamW and back.  Under a GradScaler the class takes no part in the fused
-found-inf protocol: the scaler unscales, synchronises and skips the call as for any optimizer (run_clm.py:603-606)."""
+CPU fp32 scalar), so a state_dict() loads into torch.optim.AdamW and back.
+
+fp16 mixed precision (the reference's regime, run_clm.py:587-606) is `FusedAdamW(..., amp=True)` with `LossScaler` or torch's GradScaler:
+
+    optimizer = FusedAdamW(grouped_parameters, lr=lr, max_grad_norm=max_grad_norm, amp=True)
+    scaler = LossScaler()
+    ...
+    scaler.scale(loss).backward()
+    scaler.step(optimizer)      # norm = overflow check, 1/scale folded into the clip coefficient, the skip decided on the device
+    scaler.update()             # one launch
+
+No pass unscales the gradients and nothing waits for the device: include/oeh.h (oeh_grad_norm_amp, oeh_adamw_step_amp,
+oeh_loss_scale_update), DESIGN.md section 17.1.  Without amp=True the class takes no part in the fused found-inf protocol: a GradScaler
+unscales, synchronises and skips the call as for any optimizer (run_clm.py:603-606)."""
 from __future__ import annotations
 
 import math
@@ -22,7 +34,7 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["FusedAdamW", "clip_grad_norm_"]
+__all__ = ["FusedAdamW", "LossScaler", "clip_grad_norm_"]
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -30,10 +42,22 @@ class FusedAdamW(torch.optim.Optimizer):
     to inside the step, without writing them - None: no clipping and no norm.  Parameters and state are fp32 and contiguous; gradients
     fp32, fp16 or bf16; everything on one GPU.  Parameters without a gradient sit a step out, as in torch.  At most `ops.MT_MAX_GROUPS`
     distinct (hyper-parameters, step count) combinations per step.  step() synchronises nothing and cannot be captured into a graph: the
-    step number and lr are host values recorded with the launch."""
+    step number and lr are host values recorded with the launch.
+
+    amp=True is the form for fp16 loss scaling.  The step counters then live in one fp32 device array of the optimizer's, one slot per
+    parameter; state[p]["step"] is the 0-dim view of its slot (a step tensor that is not - after load_state_dict, or state made by a plain
+    FusedAdamW or by torch - is copied into its slot once, which may wait for the device; the steady loop does not).  Kernel groups are
+    the distinct hyper-parameters alone, at most `ops.MT_MAX_GROUPS`.  step() always runs the norm - it is the overflow check - so
+    `grad_norm` (of the unscaled gradients) and `clip_coef` (with 1 / scale folded in) are always there, and max_grad_norm=None means a
+    coefficient of 1 / scale.  The scale and the flag are `self.grad_scale` and `self.found_inf`, one-element fp32 device tensors, where a
+    scaler has set them for the call (torch's protocol for optimizers with `_step_supports_amp_scaling`, which this instance then sets):
+    grad_scale None means the gradients are already unscaled; with neither, the scale is 1 and the flag is the norm's own.  On an overflow
+    nothing is read or written: parameters, moments and counters stay, and `step_skipped`, a 0-dim float64 view on the device, reads 1.
+    A parameter without a gradient sits out, counter included; an empty parameter has no plan record, so its counter is not advanced
+    either.  Capture into a graph still raises: lr stays a host value."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, amsgrad: bool = False, *,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, amp: bool = False):
         if amsgrad:
             raise ValueError("FusedAdamW has no amsgrad form")
         _check_hyper(lr, betas, eps, weight_decay)
@@ -46,6 +70,11 @@ class FusedAdamW(torch.optim.Optimizer):
         self.clip_coef: Optional[torch.Tensor] = None
         self._out4 = None
         self._plan, self._plan_key = None, None
+        self.amp = bool(amp)
+        self.step_skipped: Optional[torch.Tensor] = None  # amp: 0-dim float64 on the device, 1 when the last step() found an overflow
+        self._steps, self._slots = None, None  # amp: the device step counters, one slot per parameter in group order, and the plan's slot table
+        if self.amp:
+            self._step_supports_amp_scaling = True  # (on the instance: a plain FusedAdamW must stay on the scaler's generic path)
         self.plan_builds = 0  # how often step() had to plan anew: once, then only when a tensor has moved
         # (the keys torch.optim.AdamW keeps in a group, with its defaults: a state_dict travels both ways)
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
@@ -59,6 +88,9 @@ class FusedAdamW(torch.optim.Optimizer):
         self.__dict__.setdefault("max_grad_norm", None)
         self.grad_norm = self.clip_coef = self._plan = self._plan_key = self._out4 = None
         self.__dict__.setdefault("plan_builds", 0)
+        self.__dict__.setdefault("amp", False)
+        self.__dict__.setdefault("_steps", None)
+        self.step_skipped = self._slots = None
 
     @staticmethod
     def _check_hyper_group(group) -> None:
@@ -80,12 +112,94 @@ class FusedAdamW(torch.optim.Optimizer):
         self._check_group(self.param_groups[-1])
         self._plan_key = None
 
+    def _counters(self, dev) -> torch.Tensor:
+        """The device array of step counters, one slot per parameter in group order; grown (device to device) when a group was added."""
+        n = sum(len(g["params"]) for g in self.param_groups)
+        if self._steps is None or self._steps.numel() < n or self._steps.device != dev:
+            new = torch.zeros(n, dtype=torch.float32, device=dev)
+            old = self._steps
+            if old is not None:
+                new[:old.numel()].copy_(old)
+                for st in self.state.values():  # the views follow their array
+                    t = st.get("step")
+                    if t is not None and t.is_cuda and t.untyped_storage().data_ptr() == old.untyped_storage().data_ptr():
+                        st["step"] = new[t.storage_offset()]
+            self._steps = new
+        return self._steps
+
+    def _step_amp(self, loss):
+        ps, gs, ms, vs, keys, slots = [], [], [], [], [], []
+        slot = -1
+        for group in self.param_groups:
+            self._check_hyper_group(group)
+            b1, b2 = group["betas"]
+            hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+            for p in group["params"]:
+                slot += 1
+                if p.grad is None:
+                    continue
+                g = p.grad
+                if g.is_sparse:
+                    raise ValueError("FusedAdamW does not take sparse gradients")
+                if not g.is_contiguous():
+                    raise ValueError("FusedAdamW needs contiguous gradients")
+                if g.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                    raise TypeError(f"FusedAdamW takes fp32, fp16 or bf16 gradients, got {g.dtype}")
+                if not p.is_cuda:
+                    raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+                if not ps and torch.cuda.is_current_stream_capturing():  # (seen before any state is made)
+                    raise RuntimeError("FusedAdamW.step() cannot be captured into a graph: lr is a host value recorded with the launch")
+                if ps and p.device != ps[0].device:
+                    raise ValueError(f"FusedAdamW steps parameters on one device, got {ps[0].device} and {p.device}")
+                steps = self._counters(p.device) if not ps else self._steps
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = steps[slot]  # (the array starts at zero)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                else:
+                    t = st["step"]
+                    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 0 and t.data_ptr() == steps.data_ptr() + 4 * slot):
+                        steps[slot].copy_(t.detach().reshape(()))  # a loaded or foreign counter: into its slot, once
+                        st["step"] = steps[slot]
+                ps.append(p)
+                gs.append(g)
+                ms.append(st["exp_avg"])
+                vs.append(st["exp_avg_sq"])
+                keys.append(hyper)
+                if p.numel():
+                    slots.append(slot)
+        if not ps:
+            return loss
+        kernel_groups = {}
+        for k in keys:
+            kernel_groups.setdefault(k, len(kernel_groups))
+        if len(kernel_groups) > ops.MT_MAX_GROUPS:
+            raise ValueError(f"FusedAdamW steps at most {ops.MT_MAX_GROUPS} distinct hyper-parameter combinations at once, got {len(kernel_groups)}")
+        index = [kernel_groups[k] for k in keys]
+        key = (self._steps.data_ptr(), tuple(slots),
+               tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), g.dtype, i) for p, g, m, v, i in zip(ps, gs, ms, vs, index)))
+        if key != self._plan_key:
+            self._plan = ops.mt_plan(ps, gs, ms, vs, index, hold_grads=False, replace=self._plan)
+            self._slots = ops.mt_slots(self._plan, slots, replace=self._slots)
+            self._plan_key = key
+            self.plan_builds += 1
+        if self._out4 is None or self._out4.device != ps[0].device:
+            self._out4 = torch.empty(4, dtype=torch.float64, device=ps[0].device)
+            self.grad_norm, self.clip_coef, self.step_skipped = self._out4[1], self._out4[2], self._out4[3]
+        ops.grad_norm_amp(self._plan, self.max_grad_norm, grad_scale=getattr(self, "grad_scale", None), found_inf=getattr(self, "found_inf", None),
+                          found_acc=getattr(self, "found_acc", None), out=self._out4)
+        ops.adamw_step_amp(self._plan, [ops.AdamWGroup(*k, 0) for k in kernel_groups], self._out4, self._steps, self._slots)
+        return loss
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.amp:
+            return self._step_amp(loss)
         ps, gs, ms, vs, keys = [], [], [], [], []
         for group in self.param_groups:
             self._check_hyper_group(group)  # (a scheduler or the caller may have written into the group since)
@@ -147,6 +261,112 @@ class FusedAdamW(torch.optim.Optimizer):
         for p in ps:
             self.state[p]["step"] += 1
         return loss
+
+
+class LossScaler:
+    """torch.amp.GradScaler's loop for `FusedAdamW(amp=True)` with the state on the device: four fp32 {scale, growth tracker, found, skipped}.
+
+        scaler.scale(loss).backward();  scaler.step(optimizer);  scaler.update()
+
+    scale() multiplies by the device scale.  step() hands the optimizer the scale and the `found` accumulator and calls optimizer.step():
+    the norm kernel is the overflow check, the unscale is folded into the step's coefficient, a step that found an overflow returns
+    before it reads anything.  update() is one launch of torch's _amp_update_scale_ rule (include/oeh.h: oeh_loss_scale_update).  None of
+    the three waits for the device; `get_scale()` and `steps_skipped()` do.  Several optimizers may share one scaler: each skips on its
+    own gradients, update() sees the OR of their flags.  state_dict() has GradScaler's keys, so a checkpoint moves both ways.  An lr
+    schedule that holds still on skipped steps (run_clm.py:603-606) is the loop's: `steps_skipped()` says by how much to correct it."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000, enabled: bool = True):
+        if not (growth_factor > 0.0 and math.isfinite(growth_factor)) or not (backoff_factor > 0.0 and math.isfinite(backoff_factor)):
+            raise ValueError("growth_factor and backoff_factor must be positive and finite")
+        if int(growth_interval) < 1:
+            raise ValueError("growth_interval must be at least 1")
+        self._enabled = bool(enabled)
+        self._growth_factor, self._backoff_factor, self._growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._init = (float(init_scale), 0.0, 0.0, 0.0)  # until the first call names the device
+        self._state: Optional[torch.Tensor] = None
+
+    def is_enabled(self) -> bool:
+        return self._enabled
+
+    def _on(self, dev) -> torch.Tensor:
+        if not torch.device(dev).type == "cuda":
+            raise _lib.OehError("outeffhop_amd ops need GPU tensors: the HIP library is the only implementation")
+        if self._state is None:
+            # (from pinned memory, in stream order: the first call waits for nothing either)
+            self._state = torch.tensor(self._init, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+        elif self._state.device != torch.device(dev):
+            raise ValueError(f"this LossScaler lives on {self._state.device}, got a tensor on {dev}")
+        return self._state
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        """loss times the device scale (differentiable); the loss itself when not enabled."""
+        if not self._enabled:
+            return loss
+        return loss * self._on(loss.device)[0]
+
+    def step(self, optimizer, *args, **kwargs):
+        """optimizer.step() with the scale and the found accumulator handed over; the optimizer skips on the device when its gradients
+        overflowed.  Only a FusedAdamW(amp=True) can do that: anything else raises TypeError."""
+        if not (isinstance(optimizer, FusedAdamW) and optimizer.amp):
+            raise TypeError("LossScaler steps a FusedAdamW(amp=True); use torch.amp.GradScaler for other optimizers")
+        if not self._enabled:
+            return optimizer.step(*args, **kwargs)
+        dev = next((p.device for g in optimizer.param_groups for p in g["params"] if p.grad is not None), None)
+        if dev is None:
+            return optimizer.step(*args, **kwargs)
+        st = self._on(dev)
+        optimizer.grad_scale, optimizer.found_inf, optimizer.found_acc = st[0:1], None, st[2:3]
+        try:
+            return optimizer.step(*args, **kwargs)
+        finally:
+            del optimizer.grad_scale, optimizer.found_inf, optimizer.found_acc
+
+    def update(self) -> None:
+        """Back off after a step that found an overflow, grow after growth_interval clean ones, clear the flag: one launch."""
+        if self._enabled and self._state is not None:
+            ops.loss_scale_update(self._state, self._growth_factor, self._backoff_factor, self._growth_interval)
+
+    def _read(self):
+        return self._init if self._state is None else tuple(self._state.tolist())
+
+    def get_scale(self) -> float:
+        """The scale as a float.  Synchronises."""
+        return float(self._read()[0]) if self._enabled else 1.0
+
+    def steps_skipped(self) -> int:
+        """How many steps update() has seen skipped since the scaler was made.  Synchronises."""
+        return int(self._read()[3])
+
+    def get_growth_factor(self) -> float:
+        return self._growth_factor
+
+    def get_backoff_factor(self) -> float:
+        return self._backoff_factor
+
+    def get_growth_interval(self) -> int:
+        return self._growth_interval
+
+    def state_dict(self) -> dict:
+        """torch.amp.GradScaler's five entries ({} when not enabled).  Synchronises."""
+        if not self._enabled:
+            return {}
+        scale, tracker, _, _ = self._read()
+        return {"scale": float(scale), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": int(tracker)}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        """Take a state_dict() of this class or of torch.amp.GradScaler.  The skip count is not part of it and stays."""
+        if not self._enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])
+        vals = (float(state_dict["scale"]), float(state_dict["_growth_tracker"]))
+        if self._state is None:
+            self._init = vals + self._init[2:]
+        else:
+            self._state[:2].copy_(torch.tensor(vals, dtype=torch.float32))
 
 
 def _check_hyper(lr, betas, eps, weight_decay) -> None:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device time of the optimizer phase - global-norm clip + AdamW step over a whole model's parameters - fused against torch's two forms.
 
-    python tools/adamw_bench.py [--out FILE] [--reps R] [--iters N]
+    python tools/adamw_bench.py [--out FILE] [--reps R] [--iters N] [--amp]
 
 Parameter sets: the shape lists of BERT-base with its MLM head (BertForMaskedLM, decoder weight tied) and of OPT-125m (OPTForCausalLM, lm_head
 tied), written out below - no model import.  fp32 parameters, gradients and moments; two groups as run_clm.py:443-458 splits them (matrices
@@ -21,7 +21,16 @@ unless capturable=True, which would time a different kernel chain.
            clip_grad_norm_ the same way - twice: with the gradient tensors kept from step to step, and as the reference's loop runs it, with
            zero_grad() (set_to_none=True) and a stand-in backward that makes every gradient tensor anew (a clone per tensor: its own cost is
            the line "nothing").  The second says how many plans FusedAdamW built: none while the allocator hands the addresses back.
-No ratio is promised: the three numbers are printed as measured."""
+No ratio is promised: the three numbers are printed as measured.
+
+--amp: the same phase under fp16 loss scaling (a GradScaler loop, run_clm.py:587-606), the same method, fp32 and fp16 gradients.  One step =
+overflow check + unscale + clip + update (+ the scale's update where the candidate has one on the device):
+  amp      ops.grad_norm_amp + ops.adamw_step_amp + ops.loss_scale_update       (5 launches; no pass over the gradients beside the norm's)
+  plain    ops.grad_norm + ops.adamw_step: `fused` above, no loss scaling at all - the floor, measured in the same run
+  parent   torch._amp_foreach_non_finite_check_and_unscale_ over the gradients, then `plain`: the device work of GradScaler + FusedAdamW()
+  torch    the unscale, clip_grad_norm_, then torch's adamw(fused=True, grad_scale=..., found_inf=...)   (fp32 gradients only: it wants one dtype)
+The unscale multiplies by 1.0 here, so that replay after replay finds the same gradients.  The host lines compare GradScaler + FusedAdamW()
+with LossScaler + FusedAdamW(amp=True) in the loop with zero_grad() and the stand-in backward; the first reads found_inf back every step."""
 import argparse
 import os
 import statistics
@@ -98,6 +107,46 @@ class ParamSet:
             self._torch(True)
 
 
+class AmpSet(ParamSet):
+    """A parameter set whose gradients carry a loss scale, in `gdtype`; the gradients are `grads` (a 16-bit one cannot be a fp32 parameter's .grad)"""
+
+    def __init__(self, shapes, dev, seed, gdtype):
+        super().__init__(shapes, dev, seed)
+        self.grads = [p.grad.to(gdtype) for p in self.params]
+        if gdtype != torch.float32:
+            for p in self.params:
+                p.grad = None
+            self.plan = ops.mt_plan(self.params, self.grads, self.m, self.v, self.group)
+        n = len(self.params)
+        self.counters = torch.full((n,), 10.0, device=dev)
+        self.slots = ops.mt_slots(self.plan, range(n))
+        self.state = torch.tensor([65536.0, 0.0, 0.0, 0.0], device=dev)  # the scaler: scale, tracker, found, skipped
+        self.inv_scale, self.found = torch.ones((), device=dev), torch.zeros((), device=dev)  # (0-dim, as GradScaler's own)
+        self.hyper = [ops.AdamWGroup(LR, *BETAS, EPS, WD, 11), ops.AdamWGroup(LR, *BETAS, EPS, 0.0, 11)]
+
+    def amp(self):
+        out4 = ops.grad_norm_amp(self.plan, MAX_NORM, grad_scale=self.state[0:1], found_acc=self.state[2:3])
+        ops.adamw_step_amp(self.plan, self.hyper, out4, self.counters, self.slots)
+        ops.loss_scale_update(self.state, 2.0, 0.5, 2000)
+
+    def plain(self):
+        ops.adamw_step(self.plan, self.hyper, clip=ops.grad_norm(self.plan, MAX_NORM))
+
+    def parent(self):
+        torch._amp_foreach_non_finite_check_and_unscale_(self.grads, self.found, self.inv_scale)
+        self.plain()
+
+    def torch_fused(self):
+        with torch.no_grad():
+            torch._amp_foreach_non_finite_check_and_unscale_(self.grads, self.found, self.inv_scale)
+            torch.nn.utils.clip_grad_norm_(self.params, MAX_NORM)
+            for grp, wd in ((0, WD), (1, 0.0)):
+                idx = [i for i, gi in enumerate(self.group) if gi == grp]
+                torch_adamw([self.params[i] for i in idx], [self.grads[i] for i in idx], [self.m[i] for i in idx], [self.v[i] for i in idx], [],
+                            [self.steps_dev[i] for i in idx], foreach=None, fused=True, capturable=False, differentiable=False, amsgrad=False,
+                            beta1=BETAS[0], beta2=BETAS[1], lr=LR, weight_decay=wd, eps=EPS, maximize=False, grad_scale=self.inv_scale, found_inf=self.found)
+
+
 def replay_ms(g):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -150,16 +199,83 @@ def loop_us(step, iters):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
+def main_amp(a, lib, dev):
+    lines = [f"# adamw_bench --amp: {lib.oeh_build_info().decode()}",
+             f"# one step = overflow check + unscale + global-norm clip + AdamW update over every parameter.  device: event times of graph replays ({a.iters} steps per"
+             f" graph over {SETS} parameter sets in turn), median of {a.reps} alternating replays [min..max]; host: a plain loop, host included; no tracer",
+             "# amp: ops.grad_norm_amp + ops.adamw_step_amp + ops.loss_scale_update; plain: ops.grad_norm + ops.adamw_step (no loss scaling);"
+             " parent: torch's non-finite check and unscale, then plain; torch: unscale + clip_grad_norm_ + adamw(fused=True, grad_scale, found_inf)"]
+    for name, shapes_of in MODELS:
+        shapes = shapes_of()
+        for gdtype in (torch.float32, torch.float16):
+            sets = [AmpSet(shapes, dev, 100 + i, gdtype) for i in range(SETS)]
+            n = sets[0].numel
+            cands = ("amp", "plain", "parent") + (("torch",) if gdtype == torch.float32 else ())
+            graphs, notes = {}, {}
+            for cand in cands:
+                graphs[cand], notes[cand] = timed_graph([getattr(sets[i % SETS], "torch_fused" if cand == "torch" else cand) for i in range(a.iters)])
+            times = {c: [] for c in graphs}
+            for _ in range(a.reps):
+                for c, g in graphs.items():
+                    times[c].append(replay_ms(g) * 1e3 / a.iters)
+            del graphs
+            med = {c: statistics.median(t) for c, t in times.items()}
+            gb = 4 if gdtype == torch.float32 else 2
+            first = len(lines)
+            lines.append(f"{name}, {str(gdtype).split('.')[-1]} gradients: {len(shapes)} tensors, {n / 1e6:.1f} M parameters; amp and plain move {24 + 2 * gb} B/parameter,"
+                         f" parent {24 + 4 * gb}")
+            for c in cands:
+                lines.append(f"  device {c:8s} {med[c]:9.1f} us [{min(times[c]):.1f}..{max(times[c]):.1f}]  amp / this {med['amp'] / med[c]:5.3f}{notes[c]}")
+            if gdtype == torch.float32:
+                # the loop a user runs, host included: zero_grad(), a stand-in backward that makes every gradient anew (scaled), step, update
+                s0 = sets[0]
+                src = [g * 65536.0 for g in s0.grads]
+                groups = lambda: [{"params": [p for p, g in zip(s0.params, s0.group) if g == 0], "weight_decay": WD},  # noqa: E731
+                                  {"params": [p for p, g in zip(s0.params, s0.group) if g == 1], "weight_decay": 0.0}]
+
+                def looped(o, scaler):
+                    def go():
+                        o.zero_grad()
+                        for p, g in zip(s0.params, src):
+                            p.grad = g.clone()
+                        scaler.step(o)
+                        scaler.update()
+                    return go
+
+                ts = torch.amp.GradScaler("cuda")
+                ts.scale(torch.zeros((), device=dev))
+                for label, o, sc in (("GradScaler + FusedAdamW(max_grad_norm)", oa.FusedAdamW(groups(), lr=LR, betas=BETAS, eps=EPS, max_grad_norm=MAX_NORM), ts),
+                                     ("LossScaler + FusedAdamW(max_grad_norm, amp=True)",
+                                      oa.FusedAdamW(groups(), lr=LR, betas=BETAS, eps=EPS, max_grad_norm=MAX_NORM, amp=True), oa.LossScaler())):
+                    us = statistics.median(loop_us(looped(o, sc), 20) for _ in range(3))
+                    lines.append(f"  host   {label:50s} {us:9.1f} us per step with zero_grad() and new gradient tensors; {o.plan_builds} plans built,"
+                                 f" {int(sc.steps_skipped()) if hasattr(sc, 'steps_skipped') else 0} steps skipped")
+                    del o
+                del src, s0
+            for ln in lines[first:]:
+                print(ln, flush=True)
+            del sets
+            torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--amp", action="store_true", help="the phase under fp16 loss scaling: amp, plain, parent and torch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("adamw_bench needs a GPU: there is no CPU timing")
     lib = _lib.load()
     dev = torch.device("cuda", 0)
+    if a.amp:
+        return main_amp(a, lib, dev)
     lines = [f"# adamw_bench: {lib.oeh_build_info().decode()}",
              f"# one step = global-norm clip + AdamW update over every parameter, fp32 gradients.  device: event times of graph replays ({a.iters} steps per graph over"
              f" {SETS} parameter sets in turn), median of {a.reps} alternating replays [min..max]; host: a plain loop of optimizer.step(), host included; no tracer",

@@ -712,6 +712,60 @@ int oeh_drop_resid_ln_bwd(const oeh_ln_train_desc* d, const void* dy, const void
 int oeh_drop_resid_ln_mask(const oeh_ln_train_desc* d, uint8_t* keep /* dense (rows, cols) */, void* stream);   /* tests */
 const char* oeh_drop_resid_ln_variant(const oeh_ln_train_desc* d, int backward);   /* host only, NULL if refused */
 
+/* The softmax rows of the unfused attention path in training (oeh_softmax_train.hip): scale -> additive mask -> clamp -> softmax /
+ * softmax_1 -> clip -> dropout over (B,H,Sq,Sk) scores in ONE pass, and a backward that recomputes the probabilities from the scores and
+ * two fp32 numbers per row - the span of attention.unfused_core between the score product and the product with V (opt_attention.py:215-224
+ * with the clamp, bert_attention.py:265-292), and softmax.softmax_autograd on plain (rows, cols) data (B = H = 1).
+ * A row is (b, h, i); element j of a tensor t sits at t[b * stride[0] + h * stride[1] + i * stride[2] + j] (element strides, the last
+ * dimension contiguous).  x and dx have x_dtype; y, u, dy and du have y_dtype (x_dtype, or OEH_F32: what torch.result_type gives fp16 scores
+ * under an fp32 mask); the mask has mask_dtype and any of its strides may be 0 ((B,1,1,Sk), (B,1,Sq,Sk), (1,1,Sq,Sk)).
+ * Forward, per row in fp32, every operation rounded on its own:
+ *   z = fp32(x) * scale, or fp32(x) / scale_div when scale_div > 0 (as oeh_attn_desc);  z = z + fp32(mask);  clamp: z = max(z, clamp_min)
+ *   m = max_j z;  e = exp(z - m);  den = sum e (softmax_1: + exp(-m));  p = e / den - oeh_softmax_rows' arithmetic and, per launch form, its
+ *   order of summation: without scale, mask, clamp and dropout and with y_dtype == x_dtype, y has oeh_softmax_rows' bits; den = inf: p = 0
+ *   clip: y = clamp(p * (eta - gamma) + gamma, 0, 1);  y <- RN_y_dtype(y);  u <- RN_y_dtype(keep ? fp32(stored y) * inv : 0), inv = 1 / (1 - p_drop)
+ *   in fp32: nn.Dropout on the stored probabilities.  stats[row] <- (m, den) as formed (no lse: an fp32 lse loses log(den) on a saturated row).
+ * Keep bit: the ATTENTION dropout stream of oeh_dropout - counter (j >> 2, i, b * H + h, 0), word j & 3, kept iff word >= floor(p * 2^32):
+ * one seed gives this path and the fused attention kernels the same mask (oeh_attn_dropout_mask).
+ * At least one of y, u; u only with p_drop > 0.
+ * Backward, from x, mask, stats and the descriptor (nothing else of size Sq x Sk from the forward), per row in fp32:
+ *   z, p = exp(z - m) / den as above - the forward's fp32 p bit for bit;  g = fp32(dy) + (keep ? fp32(du) * inv : 0), either may be NULL
+ *   clip: g = (eta - gamma) * g where 0 <= p * (eta - gamma) + gamma <= 1 (closed, torch.clip), else 0
+ *   delta = sum_j p g;  dz = p * (g - delta);  clamp: dz *= 1 above the floor, 0 below, 1/2 at a tie (torch.max);  dx <- RN_x_dtype(dz * scale
+ *   or dz / scale_div)
+ * A row with den = inf (softmax_1 below the exp range, a fully masked softmax_1 row): p = 0, dx = 0 - where the torch chain has a NaN at
+ * the maximum's position; the fused attention backward's convention.  A row with a NaN (or +inf) z: stats, y, u and dx of that row are NaN.
+ * No atomics: every sum by one wave's butterflies or the fixed four-wave step behind them; two calls are bitwise equal.
+ * Launch forms (oeh_softmax_train_variant: "softmax_train/fwd/lanes/G4x8/f16/softmax1/clip/mask/clamp/drop", ".../wave/CH2/...",
+ * ".../block/..."; f16>f32: y_dtype differs): lanes - the row over G lanes of a wave, 64 / G rows per wave: rows of up to 32 of x's 16-byte
+ * vectors with one vector per lane (Sk <= 256 16-bit / 128 fp32 elements), and Sk <= 64 with one element per lane where Sk is no multiple
+ * of the vector or a row of a given tensor is off 16 bytes; wave - one wave per row in registers, 16-byte accesses, up to 512 vectors (4096
+ * 16-bit / 2048 fp32 elements); block - a workgroup per row staged in LDS, everything else.  The variant function takes y / dy as given, u / du with p_drop > 0, a mask where mask_dtype is a storage type, and
+ * every pointer as 16-byte aligned; host only, thread-local storage.
+ * Refusals, before any launch: OEH_EINVAL - p_drop outside [0, 1) or NaN, drop.reserved or reserved != 0 (checked first); desc, x, stats
+ * (backward: dx) NULL; neither y nor u, u (du) with p_drop == 0; the backward with neither dy nor du; a dtype that is none of the three
+ * (mask_dtype only with a mask), y_dtype neither x_dtype nor OEH_F32; Sk < 1, a negative extent or stride; a stride of an output (y, u; dx)
+ * below Sk in a dimension of extent > 1; a bad softmax_base; clip with eta <= gamma; scale_div < 0 or NaN; NaN scale, gamma or eta.
+ * OEH_ENOTSUP - Sk > OEH_SOFTMAX_TRAIN_MAX_COLS, B * H * Sq >= 2^31.  B * H * Sq == 0: OEH_OK without a launch. */
+#define OEH_SOFTMAX_TRAIN_MAX_COLS 15872
+typedef struct oeh_softmax_train_desc {
+  int32_t B, H, Sq, Sk;
+  int32_t x_dtype, y_dtype, mask_dtype;                /* OEH_F16 | OEH_BF16 | OEH_F32 */
+  int32_t softmax_base, clip;
+  float gamma, eta;
+  float scale, scale_div;
+  int32_t clamp; float clamp_min;
+  int32_t reserved;
+  int64_t x_stride[3], y_stride[3], u_stride[3], mask_stride[3];
+  int64_t dy_stride[3], du_stride[3], dx_stride[3];   /* backward only */
+  oeh_dropout drop;                                    /* p == 0: no dropout */
+} oeh_softmax_train_desc;
+int oeh_softmax_train_fwd(const oeh_softmax_train_desc* d, const void* x, const void* mask /* may be NULL */, void* y /* may be NULL */,
+                          void* u /* may be NULL */, float* stats, void* stream);
+int oeh_softmax_train_bwd(const oeh_softmax_train_desc* d, const void* x, const void* mask /* may be NULL */, const float* stats,
+                          const void* dy /* may be NULL */, const void* du /* may be NULL */, void* dx, void* stream);
+const char* oeh_softmax_train_variant(const oeh_softmax_train_desc* d, int backward);   /* host only, NULL if refused */
+
 /* The optimizer phase of a training step (oeh_optim.hip): the global gradient norm with its clip coefficient, and a decoupled-weight-decay
  * Adam step over ALL parameter tensors of a model in one launch - what the reference's loops do after backward()
  * (run_clm.py:440-462 torch.optim.AdamW over a decay and a no-decay group, :589-601 accelerator.clip_grad_norm_ then optimizer.step()).

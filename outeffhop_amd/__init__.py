@@ -6,6 +6,7 @@ Python host surface mirroring the reference's plugin interface:
     Quantized{Bert,OPT}...AttentionWithExtras, QuantEmbedding / QuantizedBertEmbeddings / opt_embed_front, kurtosis / inf_norm / OutlierMeter (the reference's result metrics),
     cross_entropy / FusedCrossEntropyLoss / causal_lm_loss / masked_lm_loss / PerplexityMeter (the models' loss and the perplexity),
     dropout_add_layer_norm / FusedDropoutAddLayerNorm / FusedBertSelfOutput / FusedBertOutput / fuse_block_tails (the block tail in training),
+    masked_softmax / set_fused_softmax_train (the differentiable row softmax of the unfused attention path, opt-in),
     FusedAdamW / clip_grad_norm_ (the optimizer step with the global-norm clip folded in), LossScaler (fp16 loss scaling without a host synchronisation)
 over the C-ABI library `lib/liboeh_hip.so` (include/oeh.h).  There is no CPU implementation in this package:
 every op raises if the HIP library is missing or a tensor is not on a GPU.
@@ -42,7 +43,7 @@ from .quantization import (  # noqa: F401
     val_qparams,
 )
 from .softmax import (SOFTMAX_MAPPING, ClipSoftmax, ClipSoftmax_1, Softmax_1, clipped_softmax, clipped_softmax1, clipped_softmax_1,  # noqa: F401
-                      make_clipped_softmax, make_clipped_softmax1, softmax_1, spec_of)
+                      make_clipped_softmax, make_clipped_softmax1, masked_softmax, set_fused_softmax_train, softmax_1, spec_of)
 from .sparse_activations import EntmaxAlpha, Sparsemax, entmax15, entmax_bisect, sparsemax  # noqa: F401
 from .vit_attention import ViTSelfAttentionWithExtras  # noqa: F401
 

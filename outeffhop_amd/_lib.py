@@ -123,6 +123,19 @@ class oeh_ln_train_desc(C.Structure):
                 ("dsum_stride", C.c_int64), ("eps", C.c_float), ("reserved", C.c_int32), ("drop", oeh_dropout)]
 
 
+SOFTMAX_TRAIN_MAX_COLS = 15872  # include/oeh.h: OEH_SOFTMAX_TRAIN_MAX_COLS
+
+
+class oeh_softmax_train_desc(C.Structure):
+    """include/oeh.h: the rows of oeh_softmax_train_fwd / oeh_softmax_train_bwd (mask + softmax / softmax_1 + clip + dropout for training)."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("Sq", C.c_int32), ("Sk", C.c_int32),
+                ("x_dtype", C.c_int32), ("y_dtype", C.c_int32), ("mask_dtype", C.c_int32),
+                ("softmax_base", C.c_int32), ("clip", C.c_int32), ("gamma", C.c_float), ("eta", C.c_float),
+                ("scale", C.c_float), ("scale_div", C.c_float), ("clamp", C.c_int32), ("clamp_min", C.c_float), ("reserved", C.c_int32),
+                ("x_stride", C.c_int64 * 3), ("y_stride", C.c_int64 * 3), ("u_stride", C.c_int64 * 3), ("mask_stride", C.c_int64 * 3),
+                ("dy_stride", C.c_int64 * 3), ("du_stride", C.c_int64 * 3), ("dx_stride", C.c_int64 * 3), ("drop", oeh_dropout)]
+
+
 MT_CHUNK, MT_MAX_GROUPS, MT_ENTRY_BYTES, MT_RECORD_BYTES = 4096, 8, 16, 56  # include/oeh.h: OEH_MT_CHUNK, OEH_MT_MAX_GROUPS, OEH_MT_ENTRY_BYTES, OEH_MT_RECORD_BYTES
 
 
@@ -150,6 +163,7 @@ EXPORTS = (
     "oeh_resid_ln_quant", "oeh_resid_ln_variant",
     "oeh_xent_fwd", "oeh_xent_bwd", "oeh_xent_variant",
     "oeh_drop_resid_ln_fwd", "oeh_drop_resid_ln_bwd_work_bytes", "oeh_drop_resid_ln_bwd", "oeh_drop_resid_ln_mask", "oeh_drop_resid_ln_variant",
+    "oeh_softmax_train_fwd", "oeh_softmax_train_bwd", "oeh_softmax_train_variant",
     "oeh_mt_plan_bytes", "oeh_mt_plan", "oeh_mt_variant", "oeh_grad_norm_work_bytes", "oeh_grad_norm", "oeh_grad_scale", "oeh_adamw_step",
     "oeh_grad_norm_amp", "oeh_adamw_amp_work_bytes", "oeh_adamw_step_amp", "oeh_loss_scale_update",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
@@ -266,6 +280,12 @@ def load() -> C.CDLL:
     lib.oeh_drop_resid_ln_mask.restype = C.c_int
     lib.oeh_drop_resid_ln_variant.argtypes = [C.POINTER(oeh_ln_train_desc), C.c_int]
     lib.oeh_drop_resid_ln_variant.restype = C.c_char_p
+    lib.oeh_softmax_train_fwd.argtypes = [C.POINTER(oeh_softmax_train_desc), vp, vp, vp, vp, vp, vp]
+    lib.oeh_softmax_train_fwd.restype = C.c_int
+    lib.oeh_softmax_train_bwd.argtypes = [C.POINTER(oeh_softmax_train_desc), vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_softmax_train_bwd.restype = C.c_int
+    lib.oeh_softmax_train_variant.argtypes = [C.POINTER(oeh_softmax_train_desc), C.c_int]
+    lib.oeh_softmax_train_variant.restype = C.c_char_p
     lib.oeh_mt_plan_bytes.argtypes = [C.POINTER(oeh_mt_tensor), i32]
     lib.oeh_mt_plan_bytes.restype = C.c_int64
     lib.oeh_mt_plan.argtypes = [C.POINTER(oeh_mt_tensor), i32, vp, C.POINTER(i64)]

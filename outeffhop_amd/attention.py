@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from . import softmax as _softmax
 from ._watch import cached
 from .ops import AttnFakeQuant, SoftmaxSpec
 from .softmax import spec_of
@@ -580,20 +581,56 @@ def fused_train_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, softm
                            dropout_p=dropout_p)
 
 
+def _dropout_p(dropout) -> Optional[float]:
+    """The probability a module's attention dropout applies NOW (0 in eval) where it is nn.Dropout or a partial of F.dropout, else None."""
+    if isinstance(dropout, nn.Dropout):
+        return float(dropout.p) if dropout.training else 0.0
+    if isinstance(dropout, partial) and dropout.func is nn.functional.dropout and not dropout.args and set(dropout.keywords) <= {"p", "training"}:
+        return float(dropout.keywords.get("p", 0.5)) if dropout.keywords.get("training", True) else 0.0
+    return None
+
+
 def unfused_core(
     q, k, v, *, softmax_fn, scale: float = 1.0, scale_div: float = 0.0, attention_mask=None, clamp_min: bool = False,
     scores_tap=None, probs_tap=None, dropout=None, probs_after_tap=None, head_mask=None, extra_scores=None,
-    fq_scores=None, fq_probs=None,
+    fq_scores=None, fq_probs=None, need_probs: bool = True,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Observable path (output_attentions, forward hooks on the Identity taps, head_mask, training dropout,
     relative position scores, user-supplied softmax callables): the (B,H,Sq,Sk) tensors exist, the two
     contractions are rocBLAS batched GEMMs and the softmax is the HIP row kernel behind SOFTMAX_MAPPING.
     Op order of bert_attention.py:222-292 / opt_attention.py:204-263.
-    Returns (context (B,H,Sq,d), probs before dropout/head-mask, probs actually multiplied with V)."""
+    Returns (context (B,H,Sq,d), probs before dropout/head-mask, probs actually multiplied with V).
+
+    With softmax.FUSED_SOFTMAX_TRAIN on, the span from the scale to the dropout is ONE differentiable HIP kernel (softmax.masked_softmax)
+    when there is no score or probability quantiser, no hook on scores_tap and the softmax callable has a spec.  Its own dropout - the
+    fused attention kernels' stream, not nn.Dropout's - runs only with FUSED_DROPOUT on as well and no hook on probs_tap; a caller that
+    drops `probs` passes need_probs=False and then gets None for it."""
     ops._need_gpu(q, k, v, allow_grad=True)  # GPU only, like the fused path: this package has no CPU implementation; differentiable
     scores = torch.matmul(q, k.transpose(-1, -2))
     if extra_scores is not None:
         scores = scores + extra_scores
+    spec = spec_of(softmax_fn) if _softmax.FUSED_SOFTMAX_TRAIN else None
+    if spec is not None and fq_scores is None and fq_probs is None and (scores_tap is None or not has_hooks(scores_tap)):
+        p = _dropout_p(dropout) if FUSED_DROPOUT and (probs_tap is None or not has_hooks(probs_tap)) else None
+        in_kernel = p is not None and 0.0 < p < 1.0
+        probs, used = _softmax.masked_softmax(scores, spec, scale=scale, scale_div=scale_div or 0.0, mask=attention_mask,
+                                              clamp_min=clamp_min and attention_mask is not None, dropout_p=p if in_kernel else 0.0,
+                                              want_probs=need_probs or not in_kernel)
+        out_dtype = getattr(softmax_fn, "out_dtype", None)  # (softmax.UpcastSoftmax: the dtype its callable form returns)
+        if out_dtype is not None:
+            probs = probs if probs is None or probs.dtype == out_dtype else probs.to(out_dtype)
+            used = used if used.dtype == out_dtype else used.to(out_dtype)
+        if not in_kernel:
+            if probs_tap is not None:
+                probs = probs_tap(probs)
+            used = probs
+            if dropout is not None:
+                used = dropout(used)
+        if probs_after_tap is not None:
+            used = probs_after_tap(used)
+        if head_mask is not None:
+            used = used * head_mask
+        return torch.matmul(used, v), probs, used
     if scale_div:
         scores = scores / scale_div
     elif scale != 1.0:

@@ -1940,3 +1940,122 @@ def attn_dropout_mask(B: int, H: int, Sq: int, Sk: int, p: float, seed: int, dev
         rc = lib.oeh_attn_dropout_mask(C.byref(d), C.byref(drop), _ptr(keep), _stream())
     _lib.check(rc, "oeh_attn_dropout_mask")
     return keep.view(torch.bool)
+
+
+# ---- the softmax rows of the unfused path in training (include/oeh.h: oeh_softmax_train_fwd / oeh_softmax_train_bwd): scale + mask + clamp +
+# softmax / softmax_1 + clip + dropout in one pass, and the backward from the scores and two fp32 numbers per row
+SOFTMAX_TRAIN_MAX_COLS = _lib.SOFTMAX_TRAIN_MAX_COLS  # rows longer than this are refused (OEH_ENOTSUP)
+SOFTMAX_TRAIN_CALLS = 0  # launches of `softmax_train_fwd` (softmax.FUSED_SOFTMAX_TRAIN)
+
+
+def _st3(t: Optional[torch.Tensor], shape=None):
+    """The (b, h, i) element strides of a 4-D tensor; with `shape`: of a tensor broadcast against it (0 where its own extent is 1)."""
+    if t is None:
+        return (0, 0, 0)
+    return tuple(0 if (shape is not None and t.shape[k] == 1 and shape[k] != 1) else t.stride(k) for k in range(3))
+
+
+def _softmax_train_desc(x, y_dtype, mask, spec: SoftmaxSpec, scale, scale_div, clamp_min, p, seed) -> _lib.oeh_softmax_train_desc:
+    d = _lib.oeh_softmax_train_desc()
+    d.B, d.H, d.Sq, d.Sk = x.shape
+    d.x_dtype, d.y_dtype = _DT[x.dtype], _DT[y_dtype]
+    d.mask_dtype = _DT[mask.dtype] if mask is not None else -1
+    d.softmax_base, d.clip, d.gamma, d.eta = int(spec.base), int(bool(spec.clip)), float(spec.gamma), float(spec.eta)
+    d.scale, d.scale_div = float(scale), float(scale_div)
+    d.clamp, d.clamp_min = (0, 0.0) if clamp_min is None else (1, float(clamp_min))
+    d.x_stride = _st3(x)
+    d.mask_stride = _st3(mask, x.shape)
+    drop = _dropout(p, seed)
+    d.drop.p, d.drop.seed = (0.0, 0) if drop is None else (drop.p, drop.seed)
+    return d
+
+
+def _softmax_train_in(op: str, x, mask, y_dtype):
+    if x.dim() != 4 or (x.shape[3] > 1 and x.stride(3) != 1):
+        raise ValueError(f"{op} takes (B,H,Sq,Sk) scores whose last dimension is contiguous")
+    _need_dtype(x)
+    if y_dtype not in (x.dtype, torch.float32):
+        raise ValueError(f"{op}: the output dtype is the scores' or float32")
+    if mask is not None:
+        if mask.dim() != 4 or mask.dtype not in _DT or mask.shape[3] != x.shape[3] or (mask.shape[3] > 1 and mask.stride(3) != 1) or \
+                any(mask.shape[k] not in (1, x.shape[k]) for k in range(3)):
+            raise ValueError(f"{op}: the additive mask is a 4-D fp16 / bf16 / fp32 tensor that broadcasts over (B,H,Sq) and has contiguous (Sk) rows")
+
+
+def softmax_train_fwd(x: torch.Tensor, spec: SoftmaxSpec = SoftmaxSpec(), *, scale: float = 1.0, scale_div: float = 0.0, mask: Optional[torch.Tensor] = None,
+                      clamp_min: Optional[float] = None, p: float = 0.0, seed: Optional[int] = None, out_dtype=None, want_y: bool = True):
+    """(y, u, stats) of the softmax rows of (B,H,Sq,Sk) scores in ONE kernel (`include/oeh.h: oeh_softmax_train_fwd`): y = clip(softmax[_1](max(x * scale
+    [or x / scale_div] + mask, clamp_min))) in `out_dtype` (x's, or float32), u = dropout(y) (None with p == 0; its keep mask is
+    `attn_dropout_mask(B, H, Sq, Sk, p, seed)`), stats (B,H,Sq,2) fp32 = the row's maximum and denominator, what `softmax_train_bwd` reads.
+    y is None without want_y (p > 0 only).  No autograd here (see `softmax.masked_softmax`)."""
+    global SOFTMAX_TRAIN_CALLS
+    dev = _need_gpu(x, mask, allow_grad=True)
+    y_dtype = x.dtype if out_dtype is None else out_dtype
+    x, mask = x.detach(), None if mask is None else mask.detach()
+    _softmax_train_in("softmax_train_fwd", x, mask, y_dtype)
+    d = _softmax_train_desc(x, y_dtype, mask, spec, scale, scale_div, clamp_min, p, seed)
+    drop = d.drop.p > 0.0
+    if not want_y and not drop:
+        raise ValueError("softmax_train_fwd: nothing to compute (want_y=False without dropout)")
+    y = torch.empty(x.shape, dtype=y_dtype, device=x.device) if want_y else None
+    u = torch.empty(x.shape, dtype=y_dtype, device=x.device) if drop else None
+    stats = torch.empty(tuple(x.shape[:3]) + (2,), dtype=torch.float32, device=x.device)
+    d.y_stride, d.u_stride = _st3(y), _st3(u)
+    if x.numel():  # (an empty tensor has no address to hand over)
+        with _on_device(dev):
+            rc = _lib.load().oeh_softmax_train_fwd(C.byref(d), _ptr(x), _ptr(mask), _ptr(y), _ptr(u), _ptr(stats), _stream())
+        _lib.check(rc, "oeh_softmax_train_fwd")
+        SOFTMAX_TRAIN_CALLS += 1
+    return y, u, stats
+
+
+def softmax_train_bwd(x: torch.Tensor, stats: torch.Tensor, dy: Optional[torch.Tensor], du: Optional[torch.Tensor], spec: SoftmaxSpec = SoftmaxSpec(), *,
+                      scale: float = 1.0, scale_div: float = 0.0, mask: Optional[torch.Tensor] = None, clamp_min: Optional[float] = None, p: float = 0.0,
+                      seed: Optional[int] = None) -> torch.Tensor:
+    """dx of `softmax_train_fwd` from its scores, mask, stats and options and the gradients that arrived on y and / or u (either may be None;
+    both have the forward's out_dtype).  One kernel, no atomics: the same bits on every call (`include/oeh.h: oeh_softmax_train_bwd`)."""
+    dev = _need_gpu(x, mask, stats, dy, du, allow_grad=True)
+    g = dy if dy is not None else du
+    if g is None:
+        raise ValueError("softmax_train_bwd needs dy or du")
+    x, mask = x.detach(), None if mask is None else mask.detach()
+    _softmax_train_in("softmax_train_bwd", x, mask, g.dtype)
+    if stats.shape != tuple(x.shape[:3]) + (2,) or stats.dtype != torch.float32 or not stats.is_contiguous():
+        raise ValueError("stats must be the contiguous fp32 (B,H,Sq,2) row statistic of softmax_train_fwd")
+    grads = []
+    for t_, what in ((dy, "dy"), (du, "du")):
+        if t_ is not None:
+            if t_.shape != x.shape or t_.dtype != g.dtype:
+                raise ValueError(f"{what} must have the scores' shape and the forward's out_dtype")
+            t_ = t_.detach()
+            t_ = t_ if (t_.shape[3] == 1 or t_.stride(3) == 1) and all(s >= 0 for s in t_.stride()) else t_.contiguous()
+        grads.append(t_)
+    dy, du = grads
+    d = _softmax_train_desc(x, g.dtype, mask, spec, scale, scale_div, clamp_min, p, seed)
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    d.dy_stride, d.du_stride, d.dx_stride = _st3(dy), _st3(du), _st3(dx)
+    if x.numel():
+        with _on_device(dev):
+            rc = _lib.load().oeh_softmax_train_bwd(C.byref(d), _ptr(x), _ptr(mask), _ptr(stats), _ptr(dy), _ptr(du), _ptr(dx), _stream())
+        _lib.check(rc, "oeh_softmax_train_bwd")
+    return dx
+
+
+def softmax_train_variant(B: int, H: int, Sq: int, Sk: int, dtype=torch.float16, *, backward: bool = False, spec: SoftmaxSpec = SoftmaxSpec(),
+                          out_dtype=None, mask_dtype=None, clamp: bool = False, p: float = 0.0, row_stride: Optional[int] = None) -> Optional[str]:
+    """Name of the launch form the training softmax takes for contiguous (B,H,Sq,Sk) scores of `dtype` (rows `row_stride` elements apart,
+    default Sk) with 16-byte aligned pointers: "softmax_train/fwd/lanes/G4x8/f16/softmax1", ".../wave/CH2/...", ".../block/...", or None
+    if refused.  Host only."""
+    d = _lib.oeh_softmax_train_desc()
+    d.B, d.H, d.Sq, d.Sk = int(B), int(H), int(Sq), int(Sk)
+    d.x_dtype = _DT[dtype]
+    d.y_dtype = _DT[dtype if out_dtype is None else out_dtype]
+    d.mask_dtype = -1 if mask_dtype is None else _DT[mask_dtype]
+    d.softmax_base, d.clip, d.gamma, d.eta = int(spec.base), int(bool(spec.clip)), float(spec.gamma), float(spec.eta)
+    d.scale, d.clamp = 1.0, int(bool(clamp))
+    rs = int(Sk) if row_stride is None else int(row_stride)
+    st = (H * Sq * rs, Sq * rs, rs)
+    d.x_stride = d.y_stride = d.u_stride = d.mask_stride = d.dy_stride = d.du_stride = d.dx_stride = st
+    d.drop.p = float(p)
+    r = _lib.load().oeh_softmax_train_variant(C.byref(d), int(bool(backward)))
+    return None if r is None else r.decode()

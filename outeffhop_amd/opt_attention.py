@@ -10,6 +10,7 @@ fp32 inside the kernel - the semantics that branch intended - so OPT + softmax1 
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Optional, Tuple
 
 import torch
@@ -17,7 +18,7 @@ from torch import nn
 
 from .attention import (AttentionGateType, GateBookkeeping, GateState, attention_core, autograd_needed, fused_qkv, fused_train_core, gated_merge, has_hooks,
                         init_gate, kv_source, linear_fp32, module_gate, unfused_core)
-from .softmax import make_clipped_softmax, make_clipped_softmax1, spec_of
+from .softmax import UpcastSoftmax, make_clipped_softmax, make_clipped_softmax1, spec_of
 
 
 class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
@@ -102,9 +103,9 @@ class OPTAttentionWithExtras(GateBookkeeping, nn.Module):
                 ctx = fused_train_core(q, k, v, clamp_min=True, detect_causal=True, dropout_p=self.dropout if self.training else 0.0, **kw)
             if ctx is None:
                 hm = None if layer_head_mask is None else layer_head_mask.view(1, -1, 1, 1)
-                drop = (lambda p: nn.functional.dropout(p, p=self.dropout, training=self.training))
+                drop = partial(nn.functional.dropout, p=self.dropout, training=self.training)
                 if q.dtype == torch.float16 and spec_of(self.softmax_fn) is not None:  # upcast branch of the reference (:227-230), without its TypeError
-                    kw["softmax_fn"] = (lambda x, dim=-1, _f=self.softmax_fn: _f(x.float(), dim=dim).to(torch.float16))
+                    kw["softmax_fn"] = UpcastSoftmax(self.softmax_fn, torch.float16)
                 ctx, _, used = unfused_core(q, k, v, clamp_min=attention_mask is not None, scores_tap=self.attn_scores,
                                             probs_tap=self.attn_probs_before_dropout, dropout=drop, probs_after_tap=self.attn_probs_after_dropout,
                                             head_mask=hm, **kw)

@@ -38,6 +38,164 @@ def softmax_autograd(data: torch.Tensor, spec: SoftmaxSpec, dim: int = -1) -> to
     return p
 
 
+# ---- the differentiable row softmax on the HIP kernels (include/oeh.h: oeh_softmax_train_fwd / oeh_softmax_train_bwd), opt-in: with
+# FUSED_SOFTMAX_TRAIN on, a registry callable whose input is part of an autograd graph - and attention.unfused_core for the whole span from
+# the scale to the dropout - runs `masked_softmax` instead of the op chain above.  Off by default: nobody has trained through it yet.
+FUSED_SOFTMAX_TRAIN = False
+
+# calls since import (tests read it to see which path a call took): the fused function's two directions, and `masked_softmax`'s op chain
+CALLS = {"forward": 0, "backward": 0, "torch": 0}
+
+
+def set_fused_softmax_train(on: bool) -> bool:
+    """Switch the differentiable HIP row softmax on or off; returns the previous setting."""
+    global FUSED_SOFTMAX_TRAIN
+    prev, FUSED_SOFTMAX_TRAIN = FUSED_SOFTMAX_TRAIN, bool(on)
+    return prev
+
+
+def _kernel_covers(scores: torch.Tensor, mask: Optional[torch.Tensor], dim: int = -1, dropout_p: float = 0.0, capturing: Optional[bool] = None) -> bool:
+    """True when the HIP kernels take this call: GPU scores of fp16 / bf16 / fp32 with 1 <= Sk <= ops.SOFTMAX_TRAIN_MAX_COLS along `dim` and
+    fewer than 2^31 rows; an additive mask only with 4-D scores and the softmax over the last dimension - a 4-D fp16 / bf16 / fp32 tensor
+    on the same GPU that needs no gradient, has contiguous (Sk) rows and broadcasts over (B,H,Sq) -; 0 <= dropout_p < 1, and no dropout
+    while a stream is being captured (the seed is a host value recorded with the launch: a replayed graph would repeat the mask)."""
+    if not scores.is_cuda or scores.dim() == 0 or scores.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        return False
+    nd = scores.dim()
+    if not -nd <= dim < nd:
+        return False
+    dim %= nd
+    cols = scores.shape[dim]
+    if cols < 1 or cols > ops.SOFTMAX_TRAIN_MAX_COLS or scores.numel() // cols >= 2 ** 31:
+        return False
+    if mask is not None:
+        if nd != 4 or dim != 3 or mask.dim() != 4 or mask.requires_grad or mask.device != scores.device:
+            return False
+        if mask.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            return False
+        if mask.shape[3] != cols or (cols > 1 and mask.stride(3) != 1) or any(mask.shape[k] not in (1, scores.shape[k]) for k in range(3)):
+            return False
+        if any(st < 0 for st in mask.stride()):
+            return False
+    if not 0.0 <= dropout_p < 1.0:
+        return False
+    if dropout_p > 0.0:
+        if capturing is None:
+            capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            return False
+    return True
+
+
+def _rows4(t: torch.Tensor, dim: int) -> torch.Tensor:
+    """`t` with `dim` moved last as the (B,H,Sq,Sk) tensor the kernels address (the last dimension contiguous): itself where it is one, else
+    its rows as (1,1,rows,Sk) - a view where torch can make one."""
+    t = t.movedim(dim, -1)
+    if t.dim() == 4 and (t.shape[3] == 1 or t.stride(3) == 1) and all(st >= 0 for st in t.stride()):
+        return t
+    t = t.reshape(1, 1, -1, t.shape[-1])
+    return t if t.shape[3] == 1 or t.stride(3) == 1 else t.contiguous()
+
+
+class _MaskedSoftmax(torch.autograd.Function):
+    """Saves the scores and the (rows, 2) fp32 statistic and refers to the mask: not y - the product with V keeps what it multiplied."""
+
+    @staticmethod
+    def forward(ctx, scores, mask, spec, scale, scale_div, floor, p, seed, want_probs, dim, out_dtype):
+        x = _rows4(scores.detach(), dim)
+        y, u, stats = ops.softmax_train_fwd(x, spec, scale=scale, scale_div=scale_div, mask=mask, clamp_min=floor, p=p, seed=seed, out_dtype=out_dtype,
+                                            want_y=want_probs)
+        ctx.save_for_backward(scores, stats)
+        ctx.mask = mask
+        ctx.kw = dict(scale=scale, scale_div=scale_div, clamp_min=floor, p=p, seed=seed)
+        ctx.spec, ctx.dim, ctx.two = spec, dim, p > 0.0
+        ctx.mark_non_differentiable(stats)
+        CALLS["forward"] += 1
+        moved = scores.movedim(dim, -1).shape
+        back = lambda t: None if t is None else t.reshape(moved).movedim(-1, dim)  # noqa: E731
+        return back(y), back(u), stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, du, _dstats):
+        scores, stats = ctx.saved_tensors
+        if not ctx.two:
+            du = None
+        if dy is None and du is None:
+            return (None,) * 11
+        x = _rows4(scores, ctx.dim)
+        g4 = lambda t: None if t is None else t.movedim(ctx.dim, -1).reshape(x.shape)  # noqa: E731  (x's (B,H,Sq,Sk); ops copies what it cannot address)
+        dx = ops.softmax_train_bwd(x, stats, g4(dy), g4(du), ctx.spec, mask=ctx.mask, **ctx.kw)
+        CALLS["backward"] += 1
+        moved = scores.movedim(ctx.dim, -1).shape
+        return (dx.reshape(moved).movedim(-1, ctx.dim),) + (None,) * 10
+
+
+def _chain(scores, spec, scale, scale_div, mask, clamp_min, dropout_p, training, dim):
+    """Today's ops, in attention.unfused_core's order: scale, + mask, max(., finfo.min), the registry softmax, nn.Dropout."""
+    s = scores
+    if scale_div:
+        s = s / scale_div
+    elif scale != 1.0:
+        s = s * scale
+    if mask is not None:
+        s = s + mask
+    if clamp_min:
+        s = torch.max(s, torch.tensor(torch.finfo(s.dtype).min, device=s.device))
+    ops._need_gpu(s, allow_grad=True)
+    probs = softmax_autograd(s, spec, dim) if ops.grad_recording(s) else ops.softmax_rows(s, spec, dim=dim)
+    used = torch.nn.functional.dropout(probs, dropout_p, training) if dropout_p > 0.0 else probs
+    CALLS["torch"] += 1
+    return probs, used
+
+
+def masked_softmax(scores: torch.Tensor, spec: SoftmaxSpec, *, scale: float = 1.0, scale_div: float = 0.0, mask: Optional[torch.Tensor] = None,
+                   clamp_min: bool = False, dropout_p: float = 0.0, seed: Optional[int] = None, training: bool = True, want_probs: bool = True,
+                   dim: int = -1):
+    """(probs, used) of the span between the two products of the unfused attention path: used = dropout(probs), probs = clip(softmax[_1](
+    max(scores * scale [or scores / scale_div] + mask, finfo.min))) along `dim`, in torch.result_type(scores, mask) - one HIP kernel forward
+    and one backward (include/oeh.h: oeh_softmax_train_fwd), differentiable in `scores`.  clamp_min: the floor is finfo.min of the result
+    dtype.  dropout_p with training: the keep mask of ops.attn_dropout_mask for `seed` (default: autograd_attention.draw_seed()); used is
+    probs without it.  want_probs=False (with dropout only) skips the write of probs and returns None for it.
+
+    What `_kernel_covers` does not take runs the op chain with `softmax_autograd` and nn.Dropout semantics: a CPU tensor (raises, as the
+    registry callables do), float64, a mask that requires grad, is not 4-D or whose last stride is not 1, more than
+    ops.SOFTMAX_TRAIN_MAX_COLS columns, dropout while a stream is being captured."""
+    p = float(dropout_p) if training else 0.0
+    if not _kernel_covers(scores, mask, dim, p):
+        return _chain(scores, spec, scale, scale_div, mask, clamp_min, p, training, dim)
+    out_dtype = scores.dtype if mask is None else torch.result_type(scores, mask)
+    floor = float(torch.finfo(out_dtype).min) if clamp_min else None
+    if p > 0.0 and seed is None:
+        from .autograd_attention import draw_seed
+
+        seed = draw_seed()
+    want_probs = bool(want_probs) or p == 0.0
+    dim %= scores.dim()
+    if ops.grad_recording(scores):
+        probs, used, _ = _MaskedSoftmax.apply(scores, mask, spec, float(scale), float(scale_div), floor, p, seed if p > 0.0 else None, want_probs, dim, out_dtype)
+    else:
+        x = _rows4(scores, dim)
+        probs, used, _ = ops.softmax_train_fwd(x, spec, scale=scale, scale_div=scale_div, mask=mask, clamp_min=floor, p=p, seed=seed, out_dtype=out_dtype,
+                                               want_y=want_probs)
+        CALLS["forward"] += 1
+        moved = scores.movedim(dim, -1).shape
+        probs, used = (None if t is None else t.reshape(moved).movedim(-1, dim) for t in (probs, used))
+    return probs, (probs if p == 0.0 else used)
+
+
+class UpcastSoftmax:
+    """`fn(x.float(), dim).to(out_dtype)` around a registry callable: the upcast branch of the reference's OPT attention under fp16
+    (opt_attention.py:227-230).  `spec_of` sees the inner callable's spec: the HIP kernels compute every row in fp32 and round once, which
+    is what the upcast asks for (attention.unfused_core casts to `out_dtype` where a mask promoted the scores)."""
+
+    def __init__(self, fn, out_dtype):
+        self.fn, self.out_dtype = fn, out_dtype
+
+    def __call__(self, x, dim=-1):
+        return self.fn(x.float(), dim=dim).to(self.out_dtype)
+
+
 class SoftmaxFn:
     """Callable registry entry; `spec` is what the fused kernel consumes."""
 
@@ -54,8 +212,10 @@ class SoftmaxFn:
             raise TypeError(f"softmax() got an unexpected keyword argument '{next(iter(kw))}'")
         if dtype is not None:
             data = data.to(dtype)
-        if ops.grad_recording(data):  # autograd is recording: the differentiable torch-op form (the HIP kernel is forward-only)
+        if ops.grad_recording(data):  # autograd is recording: the differentiable torch-op form (the HIP row kernel is forward-only) ...
             ops._need_gpu(data, allow_grad=True)
+            if FUSED_SOFTMAX_TRAIN and _kernel_covers(data, None, dim, 0.0):  # ... or, opted in, the differentiable HIP kernels
+                return masked_softmax(data, self.spec, dim=dim)[0]
             return softmax_autograd(data, self.spec, dim)
         return ops.softmax_rows(data, self.spec, dim=dim)
 
@@ -213,6 +373,8 @@ def spec_of(fn) -> Optional[SoftmaxSpec]:
     that bind only `eta` / `gamma` / `dim` by keyword (the modules pass `dim=-1` at the call, which overrides a bound `dim`)."""
     if isinstance(fn, SoftmaxFn):
         return fn.spec
+    if isinstance(fn, UpcastSoftmax):
+        return spec_of(fn.fn)
     if fn is torch.nn.functional.softmax or fn is torch.softmax:
         return SoftmaxSpec(0, False, 0.0, 1.0)
     if fn is clipped_softmax or fn is clipped_softmax1:

@@ -13,7 +13,11 @@ check_indices against a float64 evaluation of the stored sum, with the helpers' 
 Launch forms (oeh_ln_row.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements):
   cols 8, 72, 768, 1024   one wave per row, four rows per workgroup: B * S = 1, 6, 15 leave waves of the last workgroup without a row
   cols 1032, 8192         one workgroup per row
-  cols 1, 4 (16-bit)      element accesses; also: table row strides, output strides and bases off the 16-byte vector"""
+  cols 1, 4 (16-bit)      element accesses; also: table row strides, output strides and bases off the 16-byte vector
+Of oeh_embed_kernel's 84 instances (IN x CH x FORM x 1, 2, 3 lookups) this list reaches the first and the last CH of the two 16-byte forms
+and, with elements, CH = 1 and - through the stride tests - part of CH = 4 and, with three lookups, CH = 16: not fp32 wave CH = 2, not the
+workgroup form's middle CH, not CH = 32 with elements (52 of the 84 in a kernel trace).  tests/test_ln_instances_gpu.py runs every compiled instance at both ends of its range, from the
+registry of tests/_ln_inst.py; this file keeps the (B, S) grids, the table forms, the optional parts, ids outside a table and refusals."""
 import itertools
 import types
 

@@ -10,11 +10,14 @@ the distance of CPU fp32 F.layer_norm from float64 on the same case (err64) as t
 The factor 4 covers the kernel's different summation tree and the two extra roundings of rstd.  The measured ratios are printed (-s).
 
 Launch forms (oeh_ln_row.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements):
-  cols 8, 72, 768, 1024   one wave per row (cols <= 1024, cols % VEC == 0), CH = 1 .. 4 accesses per lane; rows 1, 3, 5 leave waves of the
-                          last workgroup without a row, 64 rows are 16 workgroups
-  cols 1032, 2048, 8192   one workgroup per row (cols <= 8192), CH = 1 .. 8
+  cols 8, 72, 768, 1024   one wave per row (cols <= 1024, cols % VEC == 0): CH = 1 and 4 accesses per lane in fp32, 1 and 2 in 16 bits;
+                          rows 1, 3, 5 leave waves of the last workgroup without a row, 64 rows are 16 workgroups
+  cols 1032, 2048, 8192   one workgroup per row (cols <= 8192): CH = 2 and 8 in fp32, 1 and 4 in 16 bits
   cols 1, 770             element accesses (cols % VEC != 0), CH = 1, 4; also: a row stride that is no multiple of VEC, a base pointer one
-                          element off a 16-byte boundary (CH = 1, 4, 16, 32 over the column list)"""
+                          element off a 16-byte boundary (CH = 1, 4, 16, 32 over test_row_strides_and_offset_base's column list)
+This list does not reach every CH of a form - fp32 wave CH = 2 (256 < cols <= 512) and the workgroup form's middle CH (2048 < cols <=
+4096) are not in it.  tests/test_ln_instances_gpu.py runs every compiled instance at both ends of its range, from the registry of
+tests/_ln_inst.py; this file keeps the row counts, the optional parts, the 16-bit grid, aliasing, offsets and refusals."""
 import numpy as np
 import pytest
 
@@ -55,7 +58,7 @@ def _round_storage(dtype):
     return None if dtype == torch.float32 else (lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype).float().numpy())
 
 
-def _inputs(rows, cols, dtype, seed):
+def _inputs(rows, cols, dtype, seed, device="cuda"):
     """x, r ~ N(0, 1) with a x40 and a x-25 outlier channel (where the row has them), gamma around 1, beta around 0."""
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(rows, cols, generator=g)
@@ -65,7 +68,7 @@ def _inputs(rows, cols, dtype, seed):
         x[:, cols - 2] *= -25.0
     gamma = 1.0 + 0.25 * torch.randn(cols, generator=g)
     beta = 0.1 * torch.randn(cols, generator=g)
-    return x.to(dtype).cuda(), r.to(dtype).cuda(), gamma.cuda(), beta.cuda()
+    return x.to(dtype).to(device), r.to(dtype).to(device), gamma.to(device), beta.to(device)
 
 
 def _spec_of(ops, t, n_bits=8):
@@ -89,8 +92,10 @@ def _yardstick_sum(ops, x, r, spec):
     return ops.fake_quant(s, spec, want_idx=True)
 
 
-def _check_call(ops, x, r, gamma, beta, with_sum_q, with_out_q, label, n_bits_out=8):
-    """One fused call with everything dumped, checked against the yardsticks.  Returns (ratio, band share, flipped share)."""
+def _check_call(ops, x, r, gamma, beta, with_sum_q, with_out_q, label, n_bits_out=8, want_sum=True, out=None, sum_out=None):
+    """One fused call with everything dumped, checked against the yardsticks.  Returns (ratio, band share, flipped share).  out, sum_out:
+    where the call writes (views of the caller's allocations).  want_sum=False: the call without the sum output, which has no dumps, runs
+    as well and gives the checked call's y bit for bit."""
     dtype = x.dtype
     fq_sum = _spec_of(ops, x if r is None else torch.add(x, r)) if with_sum_q else None
     s_want, sidx_want = _yardstick_sum(ops, x, r, fq_sum)
@@ -98,9 +103,12 @@ def _check_call(ops, x, r, gamma, beta, with_sum_q, with_out_q, label, n_bits_ou
     fq_out = ops.FakeQuantSpec(*R.grid_from_minmax(float(y32.min()), float(y32.max()), n_bits_out)) if with_out_q else None
     dump = n_bits_out <= 8
     if dump:
-        s, y, sidx, yidx = ops.resid_ln_quant(x, r, gamma, beta, EPS, fq_sum=fq_sum, fq_out=fq_out, want_idx=True)
+        s, y, sidx, yidx = ops.resid_ln_quant(x, r, gamma, beta, EPS, fq_sum=fq_sum, fq_out=fq_out, want_idx=True, out=out, sum_out=sum_out)
     else:
-        (s, y), sidx, yidx = ops.resid_ln_quant(x, r, gamma, beta, EPS, fq_sum=fq_sum, fq_out=fq_out, want_sum=True), None, None
+        (s, y), sidx, yidx = ops.resid_ln_quant(x, r, gamma, beta, EPS, fq_sum=fq_sum, fq_out=fq_out, want_sum=True, out=out, sum_out=sum_out), None, None
+    if not want_sum:
+        y_only = ops.resid_ln_quant(x, r, gamma, beta, EPS, fq_sum=fq_sum, fq_out=fq_out)
+        assert torch.is_tensor(y_only) and np.array_equal(_bits(y_only), _bits(y)), f"{label}: y differs without the sum output"
     assert s.shape == x.shape and y.shape == x.shape and s.dtype == dtype and y.dtype == dtype
     assert np.array_equal(_bits(s), _bits(s_want)), f"{label}: the sum differs from torch add + ops.fake_quant"
     if with_sum_q and dump:

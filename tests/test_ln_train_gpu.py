@@ -21,7 +21,13 @@ Worst ratios measured on an MI355X: y 3.65, dx 1.37, dr 1.45, dr - dr0 1.60, mea
 Launch forms (oeh_ln_row.h: ln_plan; VEC = 4 fp32 / 8 16-bit elements): cols 8, 72, 768, 1024 one wave per row; 1032, 2048, 8192 one
 workgroup per row; 1, 770, a row stride that is no multiple of VEC and a base pointer one element off a 16-byte boundary element accesses.
 The backward's slab loop (ops.drop_resid_ln_variant(..., backward=True) ends in G<workgroups>x<rows per slab>): one workgroup; several
-workgroups of one row-step each; more rows than the grid bound takes in one step, with a ragged last slab."""
+workgroups of one row-step each; more rows than the grid bound takes in one step, with a ragged last slab; and the workgroup counts
+around the column kernel's 32 slices (test_column_kernel_slice_split).
+The column list reaches the first and the last CH of each 16-byte form and CH = 1 and 4 with elements (CH = 16 through the stride tests at
+1032 columns), every one with p = 0.1 - not fp32 wave CH = 2, not the workgroup form's middle CH, not CH = 32 with elements, and the backward
+without dropout at 72 columns only (39 of the forward's 56 instances and 22 of the backward's in a kernel trace).
+tests/test_ln_instances_gpu.py runs every compiled instance of both row kernels, with and without dropout, at both ends of its range, from
+the registry of tests/_ln_inst.py."""
 import re
 
 import numpy as np
@@ -74,7 +80,7 @@ def _name(dtype):
     return str(dtype).split(".")[-1]
 
 
-def _inputs(rows, cols, dtype, seed):
+def _inputs(rows, cols, dtype, seed, device="cuda"):
     """x, r ~ N(0, 1) with the x40 and x-25 outlier channels of tests/test_ln_gpu.py (where the row has them), gamma around 1, beta around
     0, and the two incoming gradients dy, dsum ~ N(0, 1)."""
     g = torch.Generator().manual_seed(seed)
@@ -87,12 +93,14 @@ def _inputs(rows, cols, dtype, seed):
     beta = 0.1 * torch.randn(cols, generator=g)
     dy = torch.randn(rows, cols, generator=g)
     dsum = torch.randn(rows, cols, generator=g)
-    return x.to(dtype).cuda(), r.to(dtype).cuda(), gamma.cuda(), beta.cuda(), dy.to(dtype).cuda(), dsum.to(dtype).cuda()
+    return tuple(t.to(device) for t in (x.to(dtype), r.to(dtype), gamma, beta, dy.to(dtype), dsum.to(dtype)))
 
 
 def _reference(s, gamma, beta, dy, dsum, keep, inv, eps=EPS):
     """name -> (float64 value, err64 = max distance of CPU fp32 torch from it) on the stored sum s; "ds32": CPU fp32's ds without dsum."""
     s32 = s.detach().cpu().float().requires_grad_()
+    if beta is None:  # (y + 0 is y in every evaluation; dbeta does not depend on beta)
+        beta = torch.zeros_like(gamma)
     g32, b32 = gamma.detach().cpu().float().requires_grad_(), beta.detach().cpu().float().requires_grad_()
     dy32 = dy.detach().cpu().float()
     y32, mean32, rstd32 = torch.native_layer_norm(s32, (s32.shape[-1],), g32, b32, eps)  # F.layer_norm, with its two statistics
@@ -110,8 +118,9 @@ def _reference(s, gamma, beta, dy, dsum, keep, inv, eps=EPS):
     return out
 
 
-def _check_case(ops, x, r, gamma, beta, dy, dsum, p, seed, label):
-    """One forward and one backward call on the given tensors (any views), checked against every yardstick.  Returns name -> ratio."""
+def _check_case(ops, x, r, gamma, beta, dy, dsum, p, seed, label, want_dr=True, want_dbeta=True):
+    """One forward and one backward call on the given tensors (any views), checked against every yardstick.  Returns name -> ratio.  r, beta
+    and dsum may be None; without want_dr / want_dbeta the backward returns None for that output and the others are checked."""
     dtype, (rows, cols) = x.dtype, x.shape
     s, y, mean, rstd = ops.drop_resid_ln_fwd(x, r, gamma, beta, EPS, p=p, seed=seed)
     assert s.shape == x.shape and y.shape == x.shape and s.dtype == dtype and y.dtype == dtype and mean.shape == (rows,) and rstd.dtype == torch.float32
@@ -122,19 +131,23 @@ def _check_case(ops, x, r, gamma, beta, dy, dsum, p, seed, label):
     d = torch.where(keep_t, x.float() * torch.tensor(inv, device=x.device), torch.zeros((), device=x.device))
     s_want = (d if r is None else d + r.float()).to(dtype)
     assert np.array_equal(_bits(s), _bits(s_want)), f"{label}: the sum differs from the torch expression"
-    dx, dr, dgamma, dbeta = ops.drop_resid_ln_bwd(dy, s, gamma, mean, rstd, dsum=dsum, p=p, seed=seed)
-    assert dx.dtype == dtype and dr.dtype == dtype and dgamma.dtype == torch.float32 and dbeta.shape == (cols,)
+    dx, dr, dgamma, dbeta = ops.drop_resid_ln_bwd(dy, s, gamma, mean, rstd, dsum=dsum, p=p, seed=seed, want_dr=want_dr, want_dbeta=want_dbeta)
+    assert dx.dtype == dtype and dgamma.dtype == torch.float32 and dgamma.shape == (cols,)
+    assert (dr.dtype == dtype and dr.shape == x.shape) if want_dr else dr is None
+    assert (dbeta.dtype == torch.float32 and dbeta.shape == (cols,)) if want_dbeta else dbeta is None
     assert not _f64(dx)[~keep].any(), f"{label}: a dropped position of dx is not zero"
     ref = _reference(s, gamma, beta, dy, dsum, keep, inv)
     got = dict(y=y, mean=mean, rstd=rstd, dx=dx, dr=dr, dgamma=dgamma, dbeta=dbeta)
     ratios = {}
     for k in KEYS:
+        if got[k] is None:
+            continue
         stored = _name(dtype) if k in ("y", "dx", "dr") else "float32"
         try:
             ratios[k] = R.check_values(_f64(got[k]), *ref[k], stored)
         except AssertionError as e:
             raise AssertionError(f"{label} {k}: {e}") from None
-    if dsum is not None:
+    if dsum is not None and want_dr:
         _, dr0, _, _ = ops.drop_resid_ln_bwd(dy, s, gamma, mean, rstd, p=p, seed=seed)
         ds32 = ref["ds32"]  # CPU fp32: one add, then the exact difference
         err = float(np.abs(((ds32 + dsum.cpu().float()).double() - ds32.double()).numpy() - _f64(dsum)).max())
@@ -191,6 +204,26 @@ def test_backward_slab_loop(ops, cols, dt):
         x, r, gamma, beta, dy, dsum = _inputs(rows, cols, dtype, 9300 + cols + rows)
         _merge(worst, _check_case(ops, x, r, gamma, beta, dy, dsum, P, 77 + rows, f"{rows}x{cols} {dt} {name}"))
     _show(f"slab loop cols {cols} {dt}", worst)
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("cols", (8, 1032))
+def test_column_kernel_slice_split(ops, cols, dt):
+    """The column kernel cuts the list of workgroup partials into 32 slices of ceil(workgroups / 32): 2 and 31 partials (slices of one, the
+    rest empty), 32 (every slice one), 33 (slices of two: slice 16 holds one partial, 17 .. 31 none), 64 and 65.  The counts are read back
+    from the plan's name; the wave form's last workgroup has one row and three waves that add nothing.  dgamma and dbeta against float64
+    by the rule of `_check_case`, with dbeta and without."""
+    dtype = DTYPES[dt]
+    per_step = 4 if cols <= 1024 else 1
+    worst = {}
+    for wgs in (2, 31, 32, 33, 64, 65):
+        rows = per_step * (wgs - 1) + 1
+        name = ops.drop_resid_ln_variant(rows, cols, dtype, backward=True, p=P)
+        assert tuple(int(v) for v in re.search(r"/G(\d+)x(\d+)$", name).groups()) == (wgs, 1), name
+        x, r, gamma, beta, dy, dsum = _inputs(rows, cols, dtype, 9400 + cols + rows)
+        for want_dbeta in (True, False):
+            _merge(worst, _check_case(ops, x, r, gamma, beta, dy, dsum if wgs % 2 else None, P, 55 + rows, f"{rows}x{cols} {dt} {name}", want_dbeta=want_dbeta))
+    _show(f"column kernel slices cols {cols} {dt}", worst)
 
 
 def _mask_through_forward(ops, rows, cols, dtype, p, seed, how):

@@ -328,6 +328,35 @@ typedef struct {
 int oeh_proj_quant_i8(const void* a, int32_t pairs, const void* w, const float* bias, int64_t B, int32_t S, int32_t K, int32_t E, int32_t n_seg,
                       const oeh_proj_seg* segs, int64_t lda, int64_t ldw, void* stream);
 
+/* The elementwise tail of a QuantLinear WITH an activation function (oeh_act_quant.hip) - OPT's fc1 + ReLU (quantized_opt.py:292-294), BERT's
+ * intermediate dense + GELU (quantized_bert.py:609-617); hijacker.py:78-134: F.linear -> activation -> output quantiser - in ONE pass over
+ * the (rows, cols) output of the GEMM, x in `dtype`, columns contiguous, x_stride elements between rows.  Per element, every operation
+ * rounded on its own:
+ *   v = fma(x, alpha, bias[column])        bias given (cols fp32 values): x is a raw accumulator - oeh_quantize_heads_i8's form;
+ *   v = x                                  bias == NULL (alpha ignored)
+ *   a = v | max(v, 0) | 0.5 v (1 + erf(v / sqrt 2))        act = OEH_ACT_NONE | OEH_ACT_RELU (a NaN stays a NaN) | OEH_ACT_GELU (the erf
+ *                                          form, in fp32; the tanh form is not implemented)
+ *   a = RN_dtype(a)                        16-bit `dtype` with an activation: what the separate activation op stores
+ *   c = clamp(rint(a / scale) + zero_point, 0, 255)         oeh_fake_quant's arithmetic (8-bit grid)
+ *   y   (optional): scale * (c - zero_point) in `dtype`, y_stride elements between rows;
+ *   out (optional): c - 128 as int8, (rows, cols) contiguous - the operand of oeh_proj_quant_i8 with pairs == 3.
+ * A NaN takes index 0, +-inf saturate (oeh_fake_quant's behaviour).  Bitwise reproducible, no work buffer, safe under graph capture.
+ * Launch forms (oeh_act_quant_variant: "actq/relu/f32/y+i8/once", "actq/gelu/f16/i8/loop"; host only, NULL if refused, the string lives
+ * in thread-local storage until the next call on this thread; it assumes 16-byte aligned pointers): a thread takes 16 consecutive columns;
+ * "loop" when the 2048 workgroups of a launch take more than one such chunk per thread.
+ * Refusals, before any launch, in this order: OEH_EINVAL - x NULL, out and y both NULL, rows < 0, cols < 1, a dtype other than OEH_F16 /
+ * OEH_BF16 / OEH_F32, a negative stride, an unknown activation, scale <= 0, a zero point that is no integer in [0, 255], y_stride < cols
+ * with rows > 1; OEH_ENOTSUP - cols % 16 != 0; OEH_EALIGN - x, out, y or bias not 16-byte aligned, a row stride of x or y that is no
+ * multiple of 16 bytes.  rows == 0: OEH_OK without a launch. */
+#define OEH_ACT_NONE 0
+#define OEH_ACT_RELU 1
+#define OEH_ACT_GELU 2
+int oeh_act_quant(const void* x, int8_t* out /* may be NULL */, void* y /* may be NULL */, int64_t rows, int32_t cols, int64_t x_stride,
+                  int64_t y_stride, int32_t dtype, int32_t act, float scale, float zero_point, float alpha, const float* bias /* may be NULL */,
+                  void* stream);
+const char* oeh_act_quant_variant(int64_t rows, int32_t cols, int64_t x_stride, int64_t y_stride, int32_t dtype, int32_t act, int32_t want_y,
+                                  int32_t want_out);  /* which launch form, or NULL if refused; host only */
+
 /* Attention core for TRAINING (oeh_attn_bwd.hip): the forward with its row statistic, and the fused backward that recomputes the
  * probabilities from it - nothing of size Sq x Sk is stored.  Replaces the torch-op chain opt_attention.py:204-263 /
  * bert_attention.py:222-292 under autograd.  `desc` as for oeh_attn_fwd with: dtype OEH_F16 | OEH_BF16, D == 64, softmax_base and

@@ -19,6 +19,7 @@ STATS_WAVE_COLS, STATS_CHUNK, STATS_RECORD_BYTES = 2040, 8192, 48  # include/oeh
 QMSE_CHUNK, QMSE_SLICE, QMSE_MAX_BLOCKS, QMSE_CAND_BYTES, QMSE_F64_K = 8192, 256, 1024, 16, 4  # include/oeh.h: OEH_QMSE_CHUNK, OEH_QMSE_SLICE, OEH_QMSE_MAX_BLOCKS, OEH_QMSE_CAND_BYTES, OEH_QMSE_F64_K
 OEH_F16, OEH_BF16, OEH_F32, OEH_I8 = 0, 1, 2, 3
 OEH_SOFTMAX_VANILLA, OEH_SOFTMAX_ONE = 0, 1
+OEH_ACT_NONE, OEH_ACT_RELU, OEH_ACT_GELU = 0, 1, 2  # include/oeh.h: the activations of oeh_act_quant
 
 
 class OehError(RuntimeError):
@@ -166,6 +167,7 @@ EXPORTS = (
     "oeh_softmax_train_fwd", "oeh_softmax_train_bwd", "oeh_softmax_train_variant",
     "oeh_mt_plan_bytes", "oeh_mt_plan", "oeh_mt_variant", "oeh_grad_norm_work_bytes", "oeh_grad_norm", "oeh_grad_scale", "oeh_adamw_step",
     "oeh_grad_norm_amp", "oeh_adamw_amp_work_bytes", "oeh_adamw_step_amp", "oeh_loss_scale_update",
+    "oeh_act_quant", "oeh_act_quant_variant",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
@@ -264,6 +266,10 @@ def load() -> C.CDLL:
     lib.oeh_embed_sum_quant.restype = C.c_int
     lib.oeh_embed_sum_variant.argtypes = [C.POINTER(oeh_embed_desc)]
     lib.oeh_embed_sum_variant.restype = C.c_char_p
+    lib.oeh_act_quant.argtypes = [vp, vp, vp, i64, i32, i64, i64, i32, i32, f32, f32, f32, vp, vp]
+    lib.oeh_act_quant.restype = C.c_int
+    lib.oeh_act_quant_variant.argtypes = [i64, i32, i64, i64, i32, i32, i32, i32]
+    lib.oeh_act_quant_variant.restype = C.c_char_p
     lib.oeh_xent_fwd.argtypes = [C.POINTER(oeh_xent_desc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.oeh_xent_fwd.restype = C.c_int
     lib.oeh_xent_bwd.argtypes = [C.POINTER(oeh_xent_desc), vp, vp, vp, vp, vp, i64, vp, vp]

@@ -880,6 +880,57 @@ def _own_rows(t: torch.Tensor, cols: int, what: str):
     return v, st
 
 
+_ACT = {"none": _lib.OEH_ACT_NONE, "relu": _lib.OEH_ACT_RELU, "gelu": _lib.OEH_ACT_GELU}
+
+
+def _act_code(act: str) -> int:
+    if act not in _ACT:
+        raise ValueError(f"act must be one of {sorted(_ACT)}, got {act!r}")
+    return _ACT[act]
+
+
+def act_quant(x: torch.Tensor, spec: FakeQuantSpec, *, act: str = "none", alpha: float = 1.0, bias: Optional[torch.Tensor] = None,
+              want_values: bool = True, want_index: bool = False):
+    """fake_quant(act(alpha * x + bias)) over the last dimension's rows in ONE kernel (`include/oeh.h: oeh_act_quant`): the elementwise tail of
+    a QuantLinear with an activation function.  x (..., cols) fp16 / bf16 / fp32 with cols % 16 == 0, read in place where its leading
+    dimensions collapse to one row stride; `bias` (cols, fp32): x is a raw GEMM accumulator and alpha * x + bias is the value, otherwise x
+    itself; act "none" | "relu" | "gelu" (the erf form); `spec` a frozen 8-bit grid.  Returns the dequantised values in x's dtype
+    (want_values), the centred int8 indices idx - 128 (want_index: the operand of `QuantLinear.linear_index`), or the pair (values, indices)."""
+    dev = _need_gpu(x, bias)
+    _need_dtype(x)
+    code = _act_code(act)
+    if not (want_values or want_index):
+        raise ValueError("act_quant needs want_values or want_index")
+    if spec.qmax != 255.0:
+        raise ValueError("the grid must be 8-bit")
+    cols = x.shape[-1] if x.dim() else 0
+    if cols < 1:
+        raise ValueError("act_quant needs a last dimension of at least 1")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cols or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous fp32 vector of one value per column")
+    xv, xs = _rows_view(x.detach(), cols)
+    rows = xv.shape[0]
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_values else None
+    idx = torch.empty(x.shape, dtype=torch.int8, device=x.device) if want_index else None
+    if rows:  # (an empty tensor has no address to hand over)
+        with _on_device(dev):
+            rc = _lib.load().oeh_act_quant(_ptr(xv), _ptr(idx), _ptr(y), rows, cols, xs, cols, _DT[x.dtype], code, float(spec.scale),
+                                           float(spec.zero_point), float(alpha), _ptr(bias), _stream())
+        _lib.check(rc, "oeh_act_quant")
+    if want_values and want_index:
+        return y, idx
+    return y if want_values else idx
+
+
+def act_quant_variant(rows: int, cols: int, dtype=torch.float32, *, act: str = "none", row_stride: Optional[int] = None, want_values: bool = True,
+                      want_index: bool = False) -> Optional[str]:
+    """Name of the launch form `act_quant` takes for (rows, cols) tensors of `dtype` whose rows are `row_stride` (default: cols) elements
+    apart ("actq/relu/f32/y+i8/once", "actq/gelu/f16/i8/loop"), or None if refused.  Host only."""
+    st = cols if row_stride is None else int(row_stride)
+    r = _lib.load().oeh_act_quant_variant(int(rows), int(cols), st, int(cols), _DT[dtype], _act_code(act), int(bool(want_values)), int(bool(want_index)))
+    return None if r is None else r.decode()
+
+
 def _ln_rows_in(op: str, x, residual, weight, bias, out, sum_out, allow_grad: bool):
     """The opening `resid_ln_quant` and `drop_resid_ln_fwd` share: device and dtype, cols, the optional tensors' shape and dtype, the row views of
     x and residual, gamma / beta as fp32.  Returns (dev, cols, xv, xs, rv, rs, g, b)."""

@@ -12,6 +12,7 @@ Host-side mirror of the part of the reference's `quantization/` package that the
   Quantized{Bert,OPT}...AttentionWithExtras                 models/quantized_bert.py:221-440, quantized_opt.py:54-274
   QuantLayerNorm                                            quantization/autoquant_utils.py:64-72
   QuantizedBertSelfOutput / QuantizedBertOutput             models/quantized_bert.py:541-606
+  quantize_intermediate / QuantizedBertFeedForward          models/quantized_bert.py:609-700
   QuantizedOPTDecoderLayer                                  models/quantized_opt.py:277-384
 
 Same class / attribute / buffer names (`activation_quantizer.quantizer._delta`, `_zero_float`, ...) so calibrated
@@ -903,7 +904,7 @@ class QuantLinear(QuantizedModule, nn.Linear):
             # cores, exact int32 sums; the per-column integer (128 - zp) * sum_k Iw turns them into the sums over idx - zp
             iw8, add, s32 = self._int8_weights(xzero)
             _count(self, "_int8_index_calls")  # (tests: which form ran)
-            y = ops.proj_quant_values(rel2, iw8, self.bias.detach(), float(np.float32(xscale) * np.float32(s32)), aq.quantizer.spec(), pairs=False, acc_add=add)
+            y = ops.proj_quant_values(rel2, iw8, self._bias32(), float(np.float32(xscale) * np.float32(s32)), aq.quantizer.spec(), pairs=False, acc_add=add)
             return y.view(shape).to(out_dtype)
         if (FUSED_PROJ and fixed8 and K % 32 == 0 and rel2.shape[0] % 16 == 0 and rel2.dtype == torch.float16 and rel2.stride(1) == 1
                 and self.bias is not None):
@@ -921,7 +922,106 @@ class QuantLinear(QuantizedModule, nn.Linear):
         res = torch.add(self.bias.detach(), acc, alpha=alpha).view(shape).to(out_dtype)
         return aq(res) if self._qa else res
 
+    def _bias32(self):
+        """The bias as the kernels' epilogues read it: fp32.  An fp32 module's own tensor; a 16-bit module's converted once per bias."""
+        b = self.bias.detach()
+        if b.dtype == torch.float32:
+            return b
+        return cached(self.__dict__, "_bias32_cache", (), lambda: [(self._parameters, "bias")], lambda: self.bias.detach().to(torch.float32).contiguous())
+
+    def _own_modules(self):
+        hit = self.__dict__.get("_own_modules_cache")
+        if hit is None:
+            hit = self.__dict__["_own_modules_cache"] = list(self.modules())
+        return hit
+
+    def fused_act(self) -> Optional[str]:
+        """The activation name `ops.act_quant` takes ("none" | "relu" | "gelu") when this module's elementwise tail - scale, bias, activation
+        function, output quantiser - may run as ONE pass, else None: FUSED_FFN on, a frozen 8-bit asymmetric output quantiser, eval, no
+        forward hook on the module or on a member (a hook must see its module's own output), whole 16-column chunks, and an activation the
+        kernel has (the tanh GELU is not one).  Host only; `forward_index` and `forward` add what they ask of the input."""
+        if not FUSED_FFN or self.training or not self.out_fixed8 or self.out_features % 16 != 0 or has_hooks(*self._own_modules()):
+            return None
+        f = self.activation_function
+        if f is None:
+            return "none"
+        if type(f) is nn.ReLU:
+            return "relu"
+        if type(f) is nn.GELU and getattr(f, "approximate", "none") == "none":
+            return "gelu"
+        return None
+
+    def _tail_input_ok(self, x) -> bool:
+        return x.is_cuda and x.dtype in ops._DT and x.dim() >= 2 and x.shape[-1] == self.in_features and not ops.grad_recording(x, self.weight, self.bias)
+
+    def _gemm_quant_index(self, x, sp):
+        """Route (a) of `forward_index`: the whole module as ONE launch of `ops.proj_quant_i8` - fp32 activations, one segment, int8 out - so that
+        the accumulator never reaches memory.  Only for ReLU into a grid whose zero point is 0 (`_tensorize_min_max` clamps x_min to <= 0, so a
+        post-ReLU range always gives one): the quantiser's clamp at index 0 then IS the ReLU, fq(relu(v)) == fq(v) index for index, and no
+        activation is computed anywhere.  A NaN value takes index 0 in the epilogue (the saturating quotient's median drops it) - what
+        fq(relu(NaN)) = fq(NaN) gives in the separate ops as well.  None where the kernel does not apply."""
+        K, N = self.in_features, self.out_features
+        if not (FUSED_PROJ and sp.zero_point == 0.0 and self.bias is not None and self.pair_gemm_ok(x) and K % 32 == 0 and N % 64 == 0):
+            return None
+        x2 = x.reshape(-1, K)
+        rows = x2.shape[0]
+        if rows == 0 or rows % 16 != 0:
+            return None
+        if x2.stride(1) != 1 or (x2.stride(0) * 4) % 16 != 0:
+            x2 = x2.contiguous()
+        if x2.data_ptr() % 16 != 0:
+            x2 = x2.clone(memory_format=torch.contiguous_format)
+        iw, s32 = self._int_weights()
+        try:
+            idx = ops.proj_quant_i8(x2, iw, self.bias.detach(), rows // 16, 16, [(s32, sp, False, False)], pairs=True)[0]
+        except _OehError as e:  # a size / alignment the kernel refuses: the GEMM + the one-pass tail
+            if e.code not in (-95, -14):
+                raise
+            return None
+        _count(self, "_gemm_quant_calls")
+        return idx.permute(0, 2, 1, 3).reshape(*x.shape[:-1], N)  # (a view: the kernel wrote (rows, N))
+
+    def _fused_tail(self, x, act: str, sp: FakeQuantSpec, want_values: bool, want_index: bool):
+        """Route (b): the GEMM as the unfused forward runs it, then ONE `ops.act_quant` launch for scale, bias, activation and quantiser."""
+        weight, bias = self.get_params()
+        _count(self, "_act_quant_calls")
+        if self.pair_gemm_ok(x):
+            acc, s32, b = self.linear_pairs(x, raw=True)
+            if b is not None:
+                return ops.act_quant(acc, sp, act=act, alpha=s32, bias=b.detach(), want_values=want_values, want_index=want_index)
+            res = acc * s32
+        else:
+            res = nn.functional.linear(x.contiguous(), weight.contiguous(), bias=bias)
+        return ops.act_quant(res, sp, act=act, want_values=want_values, want_index=want_index)
+
+    def forward_index(self, x):
+        """This module's output as (the centred int8 indices idx - 128 of its output quantiser, that quantiser's FakeQuantSpec) - what the next
+        QuantLinear's `linear_index` takes on the integer matrix cores - or None when the fused tail does not apply (`fused_act`, a GPU
+        tensor outside a recorded autograd graph).  Route (a), `_gemm_quant_index`, where it applies; else route (b), `_fused_tail`."""
+        act = self.fused_act()
+        if act is None or not self._tail_input_ok(x):
+            return None
+        sp = self.activation_quantizer.quantizer.spec()
+        _count(self, "_fused_ffn_calls")
+        idx = self._gemm_quant_index(x, sp) if act == "relu" else None
+        if idx is None:
+            idx = self._fused_tail(x, act, sp, False, True)
+        return idx, sp
+
+    def int8_consumer_ok(self, rows: int) -> bool:
+        """`linear_index` on a producer's int8 indices computes this module's forward: `int8_index_ok`, and what `pair_gemm_ok` asks of the
+        weights and the mode - for a model of any of the three dtypes (the integer GEMM reads no float activations)."""
+        qz = self.weight_quantizer.quantizer
+        return (not self.training and self._qw and self.activation_function is None and type(qz) is SymmetricUniformQuantizer and qz.is_initialized
+                and qz.n_bits <= 8 and self.weight.is_cuda and not ops.grad_recording(self.weight, self.bias) and not has_hooks(*self._own_modules())
+                and self.int8_index_ok(rows))
+
     def forward(self, x, offsets=None):
+        if self.activation_function is not None and FUSED_FFN:
+            act = self.fused_act()
+            if act is not None and self._tail_input_ok(x):
+                _count(self, "_fused_ffn_calls")
+                return self._fused_tail(x, act, self.activation_quantizer.quantizer.spec(), True, False)
         weight, bias = self.get_params()
         if self.pair_gemm_ok(x):
             fused = self._pair_gemm_quantised(x)
@@ -1135,7 +1235,8 @@ def embed_front(owner: nn.Module, lookups, sum_quantizers, ln: Optional[nn.Modul
 def quantize_model(model: nn.Module, **quant_params) -> nn.Module:
     """The cases of the reference's recursive rewriter (autoquant_utils.py:236-270) that the attention classes and the block tails need:
     nn.Linear (query/key/value, q_proj/k_proj/v_proj/out_proj, dense, fc2), nn.LayerNorm, nn.Embedding (the model fronts), and
-    Sequential(Linear, ReLU) - OPT's fc1 with its activation folded into the QuantLinear (quantized_opt.py:292-294)."""
+    Sequential(Linear, ReLU | GELU) - OPT's fc1 (quantized_opt.py:292-294) and BERT's intermediate (quantized_bert.py:609-617) with the
+    activation folded into the QuantLinear."""
     def copy_params(q, src, clone):
         q.weight.data = src.weight.data.clone() if clone else src.weight.data
         if getattr(src, "bias", None) is not None:
@@ -1150,7 +1251,7 @@ def quantize_model(model: nn.Module, **quant_params) -> nn.Module:
         return copy_params(q, model, False)
     if type(model) is nn.LayerNorm and model.elementwise_affine:
         return copy_params(QuantLayerNorm(model.normalized_shape, eps=model.eps, **quant_params), model, False)
-    if type(model) is nn.Sequential and len(model) == 2 and type(model[0]) is nn.Linear and isinstance(model[1], nn.ReLU):
+    if type(model) is nn.Sequential and len(model) == 2 and type(model[0]) is nn.Linear and isinstance(model[1], (nn.ReLU, nn.GELU)):
         lin = model[0]
         q = QuantLinear(lin.in_features, lin.out_features, bias=lin.bias is not None, activation=model[1], **quant_params)
         return nn.Sequential(copy_params(q, lin, True))
@@ -1728,10 +1829,13 @@ class _QuantizedBertTail(QuantizedModel):
         self.LayerNorm = quantize_model(org_model.LayerNorm, **quant_params)
         self._fused_ln_calls = 0
 
-    def forward(self, hidden_states, input_tensor):
-        hidden_states = self.dense(hidden_states)
-        hidden_states = self.dropout(hidden_states)
+    def finish(self, dense_out, input_tensor):
+        """Everything after `dense`."""
+        hidden_states = self.dropout(dense_out)
         return resid_ln_tail(self, hidden_states, input_tensor, self.res_act_quantizer, self.LayerNorm)
+
+    def forward(self, hidden_states, input_tensor):
+        return self.finish(self.dense(hidden_states), input_tensor)
 
 
 class QuantizedBertSelfOutput(_QuantizedBertTail):
@@ -1740,6 +1844,52 @@ class QuantizedBertSelfOutput(_QuantizedBertTail):
 
 class QuantizedBertOutput(_QuantizedBertTail):
     """quantized_bert.py:574-606."""
+
+
+def feed_forward(fc1_act: nn.Module, fc2: nn.Module, x2d: torch.Tensor):
+    """fc2(fc1_act(x2d)) for the two QuantLinears of a block's feed-forward, x2d (rows, E).  With FUSED_FFN, where fc1_act's fused tail applies
+    (`QuantLinear.forward_index`) and fc2 can take its int8 indices (`QuantLinear.int8_consumer_ok`: weights that fit a signed byte,
+    K % 64 == 0, rows % 16 == 0, a frozen 8-bit output quantiser, no hooks): fc1's quantiser writes the indices and fc2 runs on the integer
+    matrix cores with its own quantiser in the epilogue - the (rows, FFN) float tensor between them is never written.  Anything else: the two
+    modules' own forwards.  fc1_act counts `_fused_ffn_calls` (and `_gemm_quant_calls` | `_act_quant_calls`: which route), fc2 `_int8_index_calls`."""
+    if (FUSED_FFN and isinstance(fc1_act, QuantLinear) and isinstance(fc2, QuantLinear) and x2d.dim() == 2 and fc2.in_features == fc1_act.out_features
+            and fc1_act.fused_act() is not None and fc2.int8_consumer_ok(x2d.shape[0])):
+        got = fc1_act.forward_index(x2d)
+        if got is not None:
+            idx8, sp = got
+            return fc2.linear_index(idx8, sp.scale, out_dtype=x2d.dtype, xzero=sp.zero_point)
+    return fc2(fc1_act(x2d))
+
+
+def quantize_intermediate(org_module, **quant_params) -> nn.Module:
+    """BERT's intermediate (dense + intermediate_act_fn) as one QuantLinear with the activation under its output quantiser
+    (quantized_bert.py:609-617): a Sequential of that one module.  The activation may be a module or the function F.gelu; another plain
+    callable is refused."""
+    act = org_module.intermediate_act_fn
+    if not isinstance(act, nn.Module):
+        if act is not nn.functional.gelu:
+            raise NotImplementedError(f"quantize_intermediate: the activation {act!r} is neither a module nor F.gelu")
+        act = nn.GELU()
+    return quantize_model(nn.Sequential(org_module.dense, act), **quant_params)
+
+
+class QuantizedBertFeedForward(QuantizedModel):
+    """The feed_forward_chunk of a quantised BERT layer (quantized_bert.py:620-700): intermediate (dense + GELU, one QuantLinear) ->
+    QuantizedBertOutput.  `org_layer` has `.intermediate` (dense, intermediate_act_fn) and `.output` (dense, dropout, LayerNorm), as a
+    BertLayer does; the members keep those names."""
+
+    def __init__(self, org_layer, **quant_params):
+        super().__init__()
+        self.intermediate = quantize_intermediate(org_layer.intermediate, **quant_params)
+        self.output = QuantizedBertOutput(org_layer.output, **quant_params)
+
+    def forward(self, attention_output):
+        out = self.output
+        if FUSED_FFN and not has_hooks(out, self.intermediate):  # (`finish` bypasses the forward of `output`, feed_forward that of the Sequential)
+            shape = attention_output.shape
+            h = feed_forward(self.intermediate[0], out.dense, attention_output.reshape(-1, shape[-1]))
+            return out.finish(h.view(*shape[:-1], h.shape[-1]), attention_output)
+        return out(self.intermediate(attention_output), attention_output)
 
 
 class QuantizedOPTDecoderLayer(QuantizedModel):
@@ -1773,7 +1923,7 @@ class QuantizedOPTDecoderLayer(QuantizedModel):
         else:
             hidden_states = residual = resid_ln_tail(self, hidden_states, residual, self.self_attn_res_act_quantizer, self.self_attn_layer_norm)
         residual = residual.reshape(-1, shape[-1])
-        hidden_states = self.fc2(self.fc1_act(hidden_states.reshape(-1, shape[-1])))
+        hidden_states = feed_forward(self.fc1_act, self.fc2, hidden_states.reshape(-1, shape[-1]))
         hidden_states = nn.functional.dropout(hidden_states, p=self.dropout, training=self.training)
         if self.do_layer_norm_before:
             return self.ffn_res_act_quantizer(residual + hidden_states).view(shape)
@@ -1926,6 +2076,18 @@ INT8_STORAGE = True
 # QuantLinear on fp32 inputs with quantised (8-bit integer x scale) weights: one fp16 GEMM on operand pairs instead of the fp32
 # library GEMM (ops.split_pairs; include/oeh.h: oeh_split_pairs).  False: torch's fp32 linear (tests compare the two).
 PAIR_GEMM = True
+# The feed-forward of a quantised block (`feed_forward`: OPT's fc1 + ReLU -> fc2, BERT's intermediate + GELU -> output.dense): fc1's scale,
+# bias, activation function and output quantiser as ONE pass (ops.act_quant; for ReLU into a zero-point-0 grid the whole fc1 as one
+# ops.proj_quant_i8 launch) that hands fc2 the quantiser's int8 indices for the integer matrix cores (QuantLinear.linear_index).  False -
+# the default until the measurements of DESIGN.md section 19 argue otherwise: the separate ops (tests compare the two).
+FUSED_FFN = False
+
+
+def set_fused_ffn(on: bool) -> bool:
+    """Switch FUSED_FFN; returns the previous setting (tests and tools restore it)."""
+    global FUSED_FFN
+    prev, FUSED_FFN = FUSED_FFN, bool(on)
+    return prev
 
 
 # ------------------------------------------------------------------------------------------------------------

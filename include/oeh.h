@@ -899,6 +899,57 @@ int oeh_adamw_step_amp(const void* plan_dev, int64_t n_chunks, int32_t n_tensors
                        const int32_t* slot, void* work, void* stream);
 int oeh_loss_scale_update(float* state4, double growth_factor, double backoff_factor, int32_t growth_interval, void* stream);
 
+/* The conditional per-token gate in TRAINING (oeh_gate_train.hip): the per-head predictors, the sigmoid and the product with the context in
+ * one entry point per direction - what attention.gate_autograd (H small Linear / Linear-ReLU-Linear modules on strided slices, stack,
+ * sigmoid) and attention.gated_merge (context * gate) do as torch ops, with autograd's chain behind them (bert_attention.py:294-331).
+ * hidden (B,T,H*d): element strides for batch and token, last dimension contiguous.  ctx (B,H,T,d) and dctx by (batch, head, token) element
+ * strides; out, dout and dhidden (B,T,H*d) by (batch, token) strides.  All five have `dtype`.  The predictor weights are fp32 device arrays
+ * laid out as for oeh_gate_fwd (units == 0: w1 (H,d), b1 (H); units = m > 0: w1 (H,m,d), b1 (H,m), w2 (H,m), b2 (H)).
+ * Forward (two launches): gate_out (B,H,T) fp32 contiguous <- sigmoid(logit) WITHOUT the scaling - oeh_gate_fwd's own launch with scaling 1,
+ *   so its bits; out[b, t, h d + j] <- RN_dtype(fp32(ctx[b,h,t,j]) * (gate_out[b,h,t] * scaling)).
+ * Backward (two launches), s = scaling:
+ *   dctx <- RN_dtype(fp32(dout) * (gate_out * s)): the forward's product applied to dout, fp32, one rounding.
+ *   Everything that feeds a sum over tokens is formed in FLOAT64 from the stored inputs, each operation rounded on its own:
+ *     dot = sum_j dout_j * ctx_j, j ascending (the products are exact);  the logit z once more from hidden (nothing of the hidden layer is
+ *     stored): units == 0: z = sum_k x_k w1[h][k] + b1[h], k ascending;  units > 0: a_j = sum_k x_k w1[h][j][k], u_j = a_j + b1_j,
+ *     r_j = max(u_j, 0), z = sum_j r_j w2_j + b2, j ascending;  pi = 1 / (1 + exp(-z));  dz = ((s * dot) * pi) * (1 - pi)
+ *   units == 0:  dw1[h] = sum_{b,t} dz * x;  db1[h] = sum dz;  dhidden_h = RN_fp32(dz) * w1[h]
+ *   units  > 0:  dw2_j = sum dz * r_j;  db2 = sum dz;  dw1[j] = w2_j * sum [u_j > 0] dz * x;  db1_j = w2_j * sum [u_j > 0] dz (the ReLU passes
+ *                nothing at 0, as torch's);  dhidden_h = sum_j da_j * w1[j] in fp32, j ascending, da_j = [u_j > 0] RN_fp32(dz) * w2_j
+ *   dhidden (may be NULL: skipped, the other outputs keep their bits) <- RN_dtype.  The sums over (b, t): a workgroup (one wave, 64 tokens
+ *   of one head per tile) walks `tiles per workgroup` consecutive tiles and adds its tokens in ascending order in float64, then leaves ONE
+ *   record per head in `work`; at most OEH_GATE_TRAIN_MAX_GROUPS workgroups per launch.  The second launch adds the records of an output
+ *   element over the workgroups - 16 slices of the list, each in ascending order, then a pairwise tree - in float64 and rounds to fp32
+ *   once: each parameter gradient is the fp32 number next to the float64 result.  No atomics: two calls give the same bits.
+ *   (A per-token chain in fp32 in front of float64 sums was measured first: a sum of n fp32 dz values carries the square root of n of
+ *   their roundings, several times what a CPU fp32 evaluation of a one-element output happens to be off by - DESIGN.md 20.  The pi formed
+ *   here differs from the stored gate_out by that one's fp32 rounding; dctx uses the stored one.)
+ * work: oeh_gate_apply_bwd_work_bytes(B, T, H, d, units) bytes (or a negative OEH_E* code), 8-byte aligned, the caller's, one per stream.
+ * oeh_gate_apply_variant: "gate_train/fwd/D64/M16/f16", "gate_train/bwd/D64/M16/f16/G64x2" (backward: workgroups per head x tiles per
+ * workgroup); host only, NULL if refused, thread-local storage; every pointer taken as given and aligned.
+ * Refusals, before any launch, in this order: OEH_EINVAL - d or a required pointer NULL (forward: hidden, w1, b1, ctx, gate_out, out;
+ * backward: dout, ctx, hidden, gate_out, w1, b1, dctx, dw1, db1, work; with units > 0 also w2, b2 and backward dw2, db2), B, T, H or d < 1,
+ * units < 0, a dtype that is none of the three, reserved != 0, a negative stride, a scaling that is not finite; OEH_ENOTSUP - d not 32 or
+ * 64, units > 64, H > 65535 (the head is a grid dimension), B * T * H >= 2^31; OEH_EALIGN - a row of hidden, ctx, out / dout, dctx or dhidden (pointer or stride) off 16 bytes, work
+ * off 8 bytes. */
+#define OEH_GATE_TRAIN_MAX_GROUPS 1024
+typedef struct oeh_gate_train_desc {
+  int32_t B, T, H, d;
+  int32_t units; int32_t dtype;                        /* OEH_F16 | OEH_BF16 | OEH_F32 */
+  float scaling; int32_t reserved;
+  int64_t hidden_stride[2];                            /* batch, token */
+  int64_t ctx_stride[3];                               /* batch, head, token */
+  int64_t out_stride[2];                               /* forward: out;  backward: dout */
+  int64_t dctx_stride[3], dhidden_stride[2];           /* backward only */
+} oeh_gate_train_desc;
+int oeh_gate_apply_fwd(const oeh_gate_train_desc* d, const void* hidden, const float* w1, const float* b1, const float* w2 /* units > 0 */,
+                       const float* b2 /* units > 0 */, const void* ctx, float* gate_out, void* out, void* stream);
+int64_t oeh_gate_apply_bwd_work_bytes(int32_t B, int32_t T, int32_t H, int32_t d, int32_t units);
+int oeh_gate_apply_bwd(const oeh_gate_train_desc* d, const void* dout, const void* ctx, const void* hidden, const float* gate_out, const float* w1,
+                       const float* b1, const float* w2, const float* b2, void* dctx, void* dhidden /* may be NULL */, float* dw1, float* db1,
+                       float* dw2, float* db2, void* work, void* stream);
+const char* oeh_gate_apply_variant(const oeh_gate_train_desc* d, int backward);   /* host only, NULL if refused */
+
 /* library information (host side, no device work) */
 int oeh_abi_version(void);
 const char* oeh_build_info(void);       /* "gfx950 hipcc <version> ..." */

@@ -137,6 +137,17 @@ class oeh_softmax_train_desc(C.Structure):
                 ("dy_stride", C.c_int64 * 3), ("du_stride", C.c_int64 * 3), ("dx_stride", C.c_int64 * 3), ("drop", oeh_dropout)]
 
 
+GATE_TRAIN_MAX_GROUPS = 1024  # include/oeh.h: OEH_GATE_TRAIN_MAX_GROUPS
+
+
+class oeh_gate_train_desc(C.Structure):
+    """include/oeh.h: the tensors of oeh_gate_apply_fwd / oeh_gate_apply_bwd (per-token gate predictors + context * gate for training)."""
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("d", C.c_int32), ("units", C.c_int32), ("dtype", C.c_int32),
+                ("scaling", C.c_float), ("reserved", C.c_int32),
+                ("hidden_stride", C.c_int64 * 2), ("ctx_stride", C.c_int64 * 3), ("out_stride", C.c_int64 * 2),
+                ("dctx_stride", C.c_int64 * 3), ("dhidden_stride", C.c_int64 * 2)]
+
+
 MT_CHUNK, MT_MAX_GROUPS, MT_ENTRY_BYTES, MT_RECORD_BYTES = 4096, 8, 16, 56  # include/oeh.h: OEH_MT_CHUNK, OEH_MT_MAX_GROUPS, OEH_MT_ENTRY_BYTES, OEH_MT_RECORD_BYTES
 
 
@@ -168,6 +179,7 @@ EXPORTS = (
     "oeh_mt_plan_bytes", "oeh_mt_plan", "oeh_mt_variant", "oeh_grad_norm_work_bytes", "oeh_grad_norm", "oeh_grad_scale", "oeh_adamw_step",
     "oeh_grad_norm_amp", "oeh_adamw_amp_work_bytes", "oeh_adamw_step_amp", "oeh_loss_scale_update",
     "oeh_act_quant", "oeh_act_quant_variant",
+    "oeh_gate_apply_fwd", "oeh_gate_apply_bwd_work_bytes", "oeh_gate_apply_bwd", "oeh_gate_apply_variant",
     "oeh_embed_sum_quant", "oeh_embed_sum_variant",
 )
 
@@ -314,6 +326,14 @@ def load() -> C.CDLL:
     lib.oeh_adamw_step_amp.restype = C.c_int
     lib.oeh_loss_scale_update.argtypes = [vp, f64, f64, i32, vp]
     lib.oeh_loss_scale_update.restype = C.c_int
+    lib.oeh_gate_apply_fwd.argtypes = [C.POINTER(oeh_gate_train_desc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oeh_gate_apply_fwd.restype = C.c_int
+    lib.oeh_gate_apply_bwd_work_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.oeh_gate_apply_bwd_work_bytes.restype = C.c_int64
+    lib.oeh_gate_apply_bwd.argtypes = [C.POINTER(oeh_gate_train_desc)] + [vp] * 16
+    lib.oeh_gate_apply_bwd.restype = C.c_int
+    lib.oeh_gate_apply_variant.argtypes = [C.POINTER(oeh_gate_train_desc), C.c_int]
+    lib.oeh_gate_apply_variant.restype = C.c_char_p
     if lib.oeh_abi_version() != ABI_VERSION:
         raise OehError(f"liboeh_hip.so ABI {lib.oeh_abi_version()} != {ABI_VERSION} (stale build?)")
     _lib = lib

@@ -151,11 +151,13 @@ def gate_autograd(mod: nn.Module, hidden_states: torch.Tensor, num_heads: int) -
     that gradients reach `alpha`: probabilities broadcastable to (B,H,T,1) WITHOUT the scaling factor, bookkeeping attributes set."""
     gt = mod.attn_gate_type
     if gt == AttentionGateType.unconditional_per_head:
+        GATE_TRAIN_CALLS["torch"] += 1
         gate = torch.sigmoid(mod.alpha)
         mod.last_gate_avg_prob = gate.view(-1)
         return gate.view(1, -1, 1, 1)
     if gt not in _CONDITIONAL:
         return None
+    GATE_TRAIN_CALLS["torch"] += 1
     if mod.attn_gate_linear_all_features:
         gate = torch.sigmoid(mod.alpha(hidden_states)).permute(0, 2, 1).contiguous().unsqueeze(3)
     else:
@@ -238,18 +240,169 @@ def module_gate(mod: nn.Module, hidden_states: torch.Tensor, num_heads: int, in_
     """The gate of one forward of a float module: (gate values | None, ops.GatePredictor | None).  `in_kernel`: this forward may
     evaluate a conditional per-token gate inside the attention kernel (it fuses, and the predictor's input is the query side's) -
     then the predictor, scaling inside, and `GateState.finish_predictor` after the launch.  Otherwise the values, times
-    gate_scaling_factor unless the gate is unconditional (context *= gate * scaling, bert_attention.py:327)."""
+    gate_scaling_factor unless the gate is unconditional (context *= gate * scaling, bert_attention.py:327) - or, with FUSED_GATE_TRAIN on
+    in a differentiable forward the training kernels take (`gate_train_units`), a `DeferredGate` in their place: `gated_merge` runs it."""
     gp = GateState.predictor(mod, hidden_states, num_heads, mod.gate_scaling_factor) if in_kernel else None
     if gp is not None:
         return None, gp
+    if FUSED_GATE_TRAIN and not in_kernel:  # (a differentiable forward is never fusable: its gate goes to gated_merge)
+        units = gate_train_units(mod, hidden_states, num_heads)
+        if units is not None:
+            return DeferredGate(mod, hidden_states, num_heads, float(mod.gate_scaling_factor), units), None
     gate = GateState.evaluate(mod, hidden_states, num_heads)
     if gate is not None and mod.attn_gate_type != AttentionGateType.unconditional_per_head:
         gate = gate * mod.gate_scaling_factor
     return gate, None
 
 
-def gated_merge(ctx: torch.Tensor, gate: Optional[torch.Tensor]) -> torch.Tensor:
-    """The tail of the differentiable cores (fused_train_core, unfused_core): (B,H,S,d) context * gate -> (B,S,H*d)."""
+# ---- the conditional per-token gate in training on the fused kernels (opt-in): with FUSED_GATE_TRAIN on, a differentiable forward of a module
+# whose gate is conditional_per_token with separate per-head predictors (Linear(d,1) or Linear-ReLU-Linear, not attn_gate_linear_all_features),
+# head dim 32 or 64, at most 64 hidden units, fp16 / bf16 / fp32 layer input with a contiguous last dimension runs predictors + sigmoid + context *
+# gate as ops.gate_apply_fwd and its backward as ops.gate_apply_bwd (`GateApply`; DESIGN.md 20) instead of `gate_autograd`'s per-head loop and a
+# torch multiply.  Everything else - the switch off, conditional_per_head, all-features and unconditional gates, another head dim, wider
+# predictors, float64, the quantised modules (quantization.py calls GateState.evaluate itself) - keeps `gate_autograd`.  GATE_TRAIN_CALLS counts
+# the launches of each kind.  Off by default: the gate enters the product as gate_out * scaling in fp32, where the torch path rounds the gate to a
+# 16-bit context's dtype first.
+FUSED_GATE_TRAIN = False
+GATE_TRAIN_CALLS = {"forward": 0, "backward": 0, "torch": 0}
+
+
+def set_fused_gate_train(on: bool = True) -> bool:
+    """Run the per-token gate of differentiable forwards on the fused HIP kernels (True) or keep the torch-op path (False, the default).
+    Returns the previous setting."""
+    global FUSED_GATE_TRAIN
+    prev, FUSED_GATE_TRAIN = FUSED_GATE_TRAIN, bool(on)
+    return prev
+
+
+def _predictor_units(alpha) -> Optional[int]:
+    """Hidden units of the per-head predictors of `build_gate` (0: Linear(d, 1)), or None when `alpha` is anything else."""
+    if not isinstance(alpha, nn.ModuleList) or len(alpha) == 0:
+        return None
+    first = alpha[0]
+    if type(first) is nn.Linear:
+        ok = all(type(f) is nn.Linear and f.out_features == 1 and f.bias is not None and f.in_features == first.in_features for f in alpha)
+        return 0 if ok else None
+    if type(first) is nn.Sequential and len(first) == 3 and type(first[0]) is nn.Linear:
+        m, d = first[0].out_features, first[0].in_features
+        for f in alpha:
+            if not (type(f) is nn.Sequential and len(f) == 3 and type(f[0]) is nn.Linear and type(f[1]) is nn.ReLU and type(f[2]) is nn.Linear):
+                return None
+            if (f[0].out_features, f[0].in_features, f[2].in_features, f[2].out_features) != (m, d, m, 1) or f[0].bias is None or f[2].bias is None:
+                return None
+        return m
+    return None
+
+
+def gate_train_scope(mod: nn.Module, hidden_states: torch.Tensor, num_heads: int) -> Optional[int]:
+    """The part of the route predicate that does not depend on where the tensors live: the predictors' hidden units (0: Linear) when the
+    gate is conditional_per_token with separate predictors inside the kernels' scope and autograd is recording for the layer input or a
+    predictor parameter, else None."""
+    if mod.attn_gate_type != AttentionGateType.conditional_per_token or mod.attn_gate_linear_all_features:
+        return None
+    units = _predictor_units(mod.alpha)
+    if units is None or units > ops.GATE_TRAIN_MAX_UNITS or has_hooks(*mod.alpha):
+        return None
+    if hidden_states.dim() != 3 or hidden_states.dtype not in (torch.float16, torch.bfloat16, torch.float32) or hidden_states.stride(2) != 1:
+        return None
+    if hidden_states.shape[2] % num_heads or hidden_states.shape[2] // num_heads not in ops.GATE_TRAIN_DIMS:
+        return None
+    first = mod.alpha[0] if units == 0 else mod.alpha[0][0]
+    if first.in_features != hidden_states.shape[2] // num_heads or not all(p.is_floating_point() and p.dtype != torch.float64 for p in mod.alpha.parameters()):
+        return None
+    if not ops.grad_recording(hidden_states, *mod.alpha.parameters()):
+        return None
+    return units
+
+
+def gate_train_units(mod: nn.Module, hidden_states: torch.Tensor, num_heads: int) -> Optional[int]:
+    """The route predicate of the fused gate training path: `gate_train_scope`, and the layer input and every predictor parameter on one
+    GPU (like `fused_supported`: anything else keeps `gate_autograd`, which says what it needs).  Does not look at the switch."""
+    if not hidden_states.is_cuda:
+        return None
+    units = gate_train_scope(mod, hidden_states, num_heads)
+    if units is None or any(p.device != hidden_states.device for p in mod.alpha.parameters()):
+        return None
+    return units
+
+
+def _or_all(values) -> int:
+    out = 0
+    for v in values:
+        out |= int(v)
+    return out
+
+
+class DeferredGate:
+    """What `module_gate` returns in place of gate values when the fused training path takes the gate: `gated_merge` evaluates it together
+    with the product, once the context exists."""
+    __slots__ = ("mod", "hidden", "num_heads", "scaling", "units")
+
+    def __init__(self, mod, hidden, num_heads, scaling, units):
+        self.mod, self.hidden, self.num_heads, self.scaling, self.units = mod, hidden, num_heads, scaling, units
+
+    def params(self):
+        out = []
+        for f in self.mod.alpha:
+            out += [f.weight, f.bias] if self.units == 0 else [f[0].weight, f[0].bias, f[2].weight, f[2].bias]
+        return out
+
+    def takes(self, ctx: torch.Tensor) -> bool:
+        """The context is one the kernels take: the layer input's dtype and device, (B,H,T,d), last dimension contiguous, and the rows of
+        both tensors 16-byte aligned (pointer and strides) - what the entry point would refuse with OEH_EALIGN."""
+        B, T, E = self.hidden.shape
+        if ctx.dtype != self.hidden.dtype or ctx.device != self.hidden.device or tuple(ctx.shape) != (B, self.num_heads, T, E // self.num_heads) or ctx.stride(3) != 1:
+            return False
+        eb = ctx.element_size()
+        return all((t.data_ptr() | _or_all(st * eb for st in t.stride()[:-1])) % 16 == 0 for t in (ctx, self.hidden))
+
+
+class GateApply(torch.autograd.Function):
+    """(merged, gate_out) = (ctx (B,H,T,d) * sigmoid(predictors(hidden_states)) * scaling as (B,T,H*d), the probabilities (B,H,T) fp32) on the
+    fused training kernels (ops.gate_apply_fwd / ops.gate_apply_bwd).  params: per head (weight, bias) of a Linear(d,1) predictor (units == 0)
+    or (fc1.weight, fc1.bias, fc2.weight, fc2.bias).  gate_out is not differentiable (bookkeeping only)."""
+
+    @staticmethod
+    def forward(fctx, ctx, hidden_states, scaling, units, *params):
+        f32 = lambda ts: torch.stack([t.detach() for t in ts]).float().contiguous()  # noqa: E731
+        if units == 0:
+            w1, b1, w2, b2 = f32([p[0] for p in params[0::2]]), f32([p[0] for p in params[1::2]]), None, None
+        else:
+            w1, b1 = f32(params[0::4]), f32(params[1::4])
+            w2, b2 = f32([p[0] for p in params[2::4]]), f32([p[0] for p in params[3::4]])
+        out, gate_out = ops.gate_apply_fwd(ctx, hidden_states, w1, b1, w2, b2, scaling)
+        GATE_TRAIN_CALLS["forward"] += 1
+        fctx.save_for_backward(ctx, hidden_states, gate_out, w1, b1, w2, b2)
+        fctx.scaling, fctx.units, fctx.param_dtypes = scaling, units, [p.dtype for p in params]
+        fctx.mark_non_differentiable(gate_out)
+        return out, gate_out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, dout, _dgate):
+        ctx, hidden_states, gate_out, w1, b1, w2, b2 = fctx.saved_tensors
+        dctx, dhidden, dw1, db1, dw2, db2 = ops.gate_apply_bwd(dout, ctx, hidden_states, gate_out, w1, b1, w2, b2, fctx.scaling,
+                                                               want_dhidden=fctx.needs_input_grad[1])
+        GATE_TRAIN_CALLS["backward"] += 1
+        grads = []
+        for h in range(w1.shape[0]):
+            if fctx.units == 0:
+                grads += [dw1[h:h + 1], db1[h:h + 1]]
+            else:
+                grads += [dw1[h], db1[h], dw2[h:h + 1], db2[h:h + 1]]
+        grads = [g if g.dtype == dt else g.to(dt) for g, dt in zip(grads, fctx.param_dtypes)]
+        return (dctx, dhidden, None, None, *grads)
+
+
+def gated_merge(ctx: torch.Tensor, gate) -> torch.Tensor:
+    """The tail of the differentiable cores (fused_train_core, unfused_core): (B,H,S,d) context * gate -> (B,S,H*d).  gate: the values, None,
+    or a `DeferredGate` (FUSED_GATE_TRAIN): then `GateApply` - or, for a context the kernels do not take after all, `gate_autograd` now."""
+    if isinstance(gate, DeferredGate):
+        if gate.takes(ctx):
+            merged, gate_out = GateApply.apply(ctx, gate.hidden, gate.scaling, gate.units, *gate.params())
+            _note_gate(gate.mod, gate_out.unsqueeze(3), gate.num_heads)  # (fp32 and detached here; the torch path's is in the model's dtype, in the graph)
+            return merged
+        gate = gate_autograd(gate.mod, gate.hidden, gate.num_heads) * gate.scaling
     if gate is not None:
         ctx = ctx * gate.to(ctx.dtype)
     return ctx.transpose(1, 2).reshape(ctx.shape[0], ctx.shape[2], -1)

@@ -2110,3 +2110,106 @@ def softmax_train_variant(B: int, H: int, Sq: int, Sk: int, dtype=torch.float16,
     d.drop.p = float(p)
     r = _lib.load().oeh_softmax_train_variant(C.byref(d), int(bool(backward)))
     return None if r is None else r.decode()
+
+
+# ---- the per-token gate in training (include/oeh.h: oeh_gate_apply_fwd / oeh_gate_apply_bwd): predictors + sigmoid + context * gate, both directions
+GATE_TRAIN_DIMS = (32, 64)   # head dims the kernels take (OEH_ENOTSUP otherwise)
+GATE_TRAIN_MAX_UNITS = 64    # hidden units of an MLP predictor
+_gate_train_work = {}  # (device index, stream handle) -> the per-workgroup parameter-gradient records of that stream's backward
+
+
+def _gate_train_desc(B: int, T: int, H: int, d: int, units: int, dtype, scaling: float, hidden_stride, ctx_stride, out_stride,
+                     dctx_stride=(0, 0, 0), dhidden_stride=(0, 0)) -> _lib.oeh_gate_train_desc:
+    """hidden / out (dout) / dhidden: (batch, token) element strides; ctx / dctx: (batch, head, token).  The library validates the rest."""
+    g = _lib.oeh_gate_train_desc()
+    g.B, g.T, g.H, g.d, g.units, g.dtype = int(B), int(T), int(H), int(d), int(units), _DT[dtype]
+    g.scaling = float(scaling)
+    g.hidden_stride, g.ctx_stride, g.out_stride = tuple(hidden_stride), tuple(ctx_stride), tuple(out_stride)
+    g.dctx_stride, g.dhidden_stride = tuple(dctx_stride), tuple(dhidden_stride)
+    return g
+
+
+def _gate_train_in(op: str, ctx: torch.Tensor, hidden: torch.Tensor, w1, b1, w2, b2):
+    """Shapes of one gate call: ctx (B,H,T,d) and hidden (B,T,H*d) of one storage dtype with contiguous last dimensions, the stacked fp32
+    predictor weights of `attention.GateState.packed_weights`.  Returns (B, H, T, d, units)."""
+    _need_dtype(ctx)
+    if ctx.dim() != 4 or hidden.dim() != 3 or hidden.dtype != ctx.dtype:
+        raise ValueError(f"{op}: ctx (B,H,T,d) and hidden (B,T,H*d) of one dtype")
+    B, H, T, d = ctx.shape
+    if tuple(hidden.shape) != (B, T, H * d) or ctx.stride(3) != 1 or hidden.stride(2) != 1:
+        raise ValueError(f"{op}: hidden must be (B,T,H*d) and both last dimensions contiguous")
+    units = 0 if w1.dim() == 2 else int(w1.shape[1])
+    shapes = ((w1, (H, d)), (b1, (H,))) if units == 0 else ((w1, (H, units, d)), (b1, (H, units)), (w2, (H, units)), (b2, (H,)))
+    for w, shape in shapes:
+        if w is None or tuple(w.shape) != shape or w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError(f"{op}: predictor weights must be the stacked contiguous fp32 arrays of oeh_gate_fwd, expected {shape}")
+    return B, H, T, d, units
+
+
+def gate_apply_fwd(ctx: torch.Tensor, hidden: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: Optional[torch.Tensor] = None,
+                   b2: Optional[torch.Tensor] = None, scaling: float = 1.0):
+    """(out, gate_out) of the conditional per-token gate applied to a context (`include/oeh.h: oeh_gate_apply_fwd`): gate_out (B,H,T) fp32 =
+    sigmoid(predictor_h(hidden[:, :, h d:(h + 1) d])) WITHOUT the scaling - the bits of `gate_fwd(..., scaling=1)` - and out (B,T,H*d) =
+    ctx (B,H,T,d, any batch / head / token strides) * (gate_out * scaling) in ctx's dtype, heads merged.  w1 (H,d) | (H,m,d), b1 (H) | (H,m),
+    w2 (H,m), b2 (H): contiguous fp32.  No autograd here (see `attention.GateApply`)."""
+    dev = _need_gpu(ctx, hidden, w1, b1, w2, b2, allow_grad=True)
+    B, H, T, d, units = _gate_train_in("gate_apply_fwd", ctx, hidden, w1, b1, w2, b2)
+    ctx, hidden = ctx.detach(), hidden.detach()
+    out = torch.empty((B, T, H * d), dtype=ctx.dtype, device=ctx.device)
+    gate_out = torch.empty((B, H, T), dtype=torch.float32, device=ctx.device)
+    g = _gate_train_desc(B, T, H, d, units, ctx.dtype, scaling, hidden.stride()[:2], ctx.stride()[:3], out.stride()[:2])
+    with _on_device(dev):
+        rc = _lib.load().oeh_gate_apply_fwd(C.byref(g), _ptr(hidden), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(ctx), _ptr(gate_out), _ptr(out), _stream())
+    _lib.check(rc, "oeh_gate_apply_fwd")
+    return out, gate_out
+
+
+def gate_apply_bwd(dout: torch.Tensor, ctx: torch.Tensor, hidden: torch.Tensor, gate_out: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                   w2: Optional[torch.Tensor] = None, b2: Optional[torch.Tensor] = None, scaling: float = 1.0, *, want_dhidden: bool = True,
+                   dctx: Optional[torch.Tensor] = None, dhidden: Optional[torch.Tensor] = None):
+    """(dctx, dhidden, dw1, db1, dw2, db2) of `gate_apply_fwd` from the output gradient dout (B,T,H*d), the forward's inputs and its gate_out
+    (`include/oeh.h: oeh_gate_apply_bwd`).  dctx: contiguous (B,H,T,d) in ctx's dtype; dhidden: (B,T,H*d) (None without want_dhidden: the
+    other outputs keep their bits); the parameter gradients: fp32 in the weights' stacked layouts (dw2, db2 None for a Linear predictor),
+    summed in float64 and rounded once.  Nothing of the hidden layer is read: it is formed again from hidden.  Two HIP kernels, no atomics:
+    the same bits on every call.  dctx / dhidden: the caller's output tensors of those shapes in ctx's dtype, any (batch, head, token) /
+    (batch, token) strides with a contiguous last dimension and 16-byte aligned rows."""
+    dev = _need_gpu(dout, ctx, hidden, gate_out, w1, b1, w2, b2, dctx, dhidden, allow_grad=True)
+    B, H, T, d, units = _gate_train_in("gate_apply_bwd", ctx, hidden, w1, b1, w2, b2)
+    if tuple(dout.shape) != (B, T, H * d) or dout.dtype != ctx.dtype:
+        raise ValueError("gate_apply_bwd: dout must be (B,T,H*d) in ctx's dtype")
+    if tuple(gate_out.shape) != (B, H, T) or gate_out.dtype != torch.float32 or not gate_out.is_contiguous():
+        raise ValueError("gate_apply_bwd: gate_out must be the contiguous fp32 (B,H,T) tensor of gate_apply_fwd")
+    dout = dout.detach()
+    if dout.stride(2) != 1:
+        dout = dout.contiguous()
+    ctx, hidden = ctx.detach(), hidden.detach()
+    for t_, shape, what in ((dctx, (B, H, T, d), "dctx"), (dhidden, (B, T, H * d), "dhidden")):
+        if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != ctx.dtype or t_.stride(-1) != 1):
+            raise ValueError(f"gate_apply_bwd: {what} must be {shape} in ctx's dtype with a contiguous last dimension")
+    if dctx is None:
+        dctx = torch.empty((B, H, T, d), dtype=ctx.dtype, device=ctx.device)
+    want_dhidden = want_dhidden or dhidden is not None
+    if dhidden is None and want_dhidden:
+        dhidden = torch.empty((B, T, H * d), dtype=ctx.dtype, device=ctx.device)
+    dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
+    dw2, db2 = (torch.empty_like(w2), torch.empty_like(b2)) if units > 0 else (None, None)
+    g = _gate_train_desc(B, T, H, d, units, ctx.dtype, scaling, hidden.stride()[:2], ctx.stride()[:3], dout.stride()[:2], dctx.stride()[:3],
+                         dhidden.stride()[:2] if want_dhidden else (0, 0))
+    lib = _lib.load()
+    nbytes = int(lib.oeh_gate_apply_bwd_work_bytes(B, T, H, d, units))
+    _lib.check(min(nbytes, 0), "oeh_gate_apply_bwd_work_bytes")
+    work = _scratch(_gate_train_work, dev, max(nbytes, 8))
+    with _on_device(dev):
+        rc = lib.oeh_gate_apply_bwd(C.byref(g), _ptr(dout), _ptr(ctx), _ptr(hidden), _ptr(gate_out), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(dctx),
+                                    _ptr(dhidden), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(work), _stream())
+    _lib.check(rc, "oeh_gate_apply_bwd")
+    return dctx, dhidden, dw1, db1, dw2, db2
+
+
+def gate_apply_variant(B: int, T: int, H: int, d: int, units: int = 0, dtype=torch.float16, *, backward: bool = False) -> Optional[str]:
+    """Name of the launch form the training gate takes for contiguous tensors: "gate_train/fwd/D64/M16/f16", "gate_train/bwd/D64/M16/f16/G64x2"
+    (backward: workgroups per head x 64-token tiles per workgroup), or None if refused.  Host only."""
+    E = int(H) * int(d)
+    g = _gate_train_desc(B, T, H, d, units, dtype, 1.0, (T * E, E), (T * E, T * d, d), (T * E, E), (T * E, T * d, d), (T * E, E))
+    r = _lib.load().oeh_gate_apply_variant(C.byref(g), int(bool(backward)))
+    return None if r is None else r.decode()
